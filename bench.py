@@ -16,16 +16,26 @@ slide).
                        all-gather of the produced frames at the end, inside the timed region.  The total
                        work is the same for every N > 1 ("scaling": "strong"); the like-for-like
                        single-GPU figure (64 members on one GPU) is `python bench.py --gpus 1
-                       --total-members 64` and is also reported by the default N=1 run as
+                       --total-members 64` and is also reported by an N=1 `--full` run as
                        `ensemble64_single_gpu`.
   --members-per-gpu M  weak-scaling mode instead: every rank runs M members.
-value = frames produced by all ranks / max-over-ranks wall time of exactly K steps (+ the gather).
+value = frames produced by all ranks / max-over-ranks wall time of exactly K steps (+ the gather);
+ms_per_step = that wall time / K.
+
+A plain run sets up, warms up (W steps), times the K steps and prints the JSON line; nothing else.
+  --dump-outputs DIR   after the timed steps, the frames the last timed step produced (what `RolloutEngine.produced`
+                       hands a caller), all members, f32 [members, atoms, 3], as DIR/frames_last_step.npy (rank 0;
+                       inputs and weights are seeded, so the same arguments give the same inputs on every run)
+  --full               also every measurement leg below (`roofline`, `rooflines`, `kernels`, `other_conv_mode`, the
+                       N=1 legs `ensemble64_single_gpu`, `cfg2_1000_steps`, `shape_A`, `cfg4_training`, `cfg5_shape_c`,
+                       `per_rank_share_8gpu`, and `cpu_baseline` with its first-frame parity check); the `--skip-*`
+                       options drop single legs of a --full run.  A plain run prints these keys as null / {}.
 
 Weights: synthetic near-identity set (weights.py) — no trained checkpoint exists offline and
 random-init weights collapse the cloud to one point, which would change E (the cost driver) after
 one step.  The architecture, arithmetic and update rule (next frame = model output) are unchanged.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel of the timed path against HBM.  Factored conv (what conv_mode "auto" runs at
                 this size; csrc/moment.hip): K1 `moment_kernel`, S_t = sum_(e->t) x_src (x) h_e — algorithmic bytes
                 per launch E*k*4 (H in) + R*64*k*4 (S out) + E*4 (src) + (R+1)*4 (row_ptr), DESIGN.md §4.5.
@@ -106,15 +116,20 @@ def parse(argv=None):
                     help="notebook = the model the reference's notebook ran (no LSTM, conv1 only; use with "
                          "--atoms 28 --window 1 --kernel-width 512 --chain for the nb:370 shape)")
     ap.add_argument("--chain", action="store_true", help="random-walk C-alpha chain frame instead of the uniform box")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step as DIR/frames_last_step.npy (f32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurement legs (rooflines and per-kernel timers, the other conv mode, the N=1 "
+                         "ensemble / config / rank-share legs, the CPU baseline); a plain run only times the K steps")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--skip-roofline", action="store_true", help="--full: skip the per-kernel timer / roofline leg")
     ap.add_argument("--skip-ensemble-leg", action="store_true",
-                    help="N=1 default run: skip the 64-member single-GPU leg (cfg3's like-for-like baseline)")
+                    help="--full N=1 run: skip the 64-member single-GPU leg (cfg3's like-for-like baseline)")
     ap.add_argument("--skip-rank-share-leg", action="store_true",
-                    help="N=1 default run: skip the leg that runs 8 members (one rank's share of configs[2] at 8 GPUs) in a "
+                    help="--full N=1 run: skip the leg that runs 8 members (one rank's share of configs[2] at 8 GPUs) in a "
                          "child process through a world-size-1 RCCL group")
     ap.add_argument("--skip-config-legs", action="store_true",
-                    help="N=1 default run: skip the cfg4 (training), cfg5 (50k-atom box) and shape-A (N=28) legs")
+                    help="--full N=1 run: skip the cfg4 (training), cfg5 (50k-atom box) and shape-A (N=28) legs")
     ap.add_argument("--cpu-budget-s", type=float, default=120.0,
                     help="bound on the full reference-faithful CPU step; estimated first from one conv application")
     return ap.parse_args(argv)
@@ -796,6 +811,29 @@ def profiled_traffic(kernel: str, atoms: int, members: int, conv_mode: str, gemm
     return profiled_entry(kernel, atoms, members, conv_mode, gemm_mode).get("hbm_bytes_per_launch")
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy.  One that would take the whole run past DUMP_MAX_BYTES is written
+    as a fixed sample of its rows (last axis kept; seed 0, sorted: the same rows on every run)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            raise ValueError(f"--dump-outputs: {name} is {arr.dtype}, not float32 / float64")
+        what = str(tuple(arr.shape))
+        if arr.nbytes > budget:
+            rows = arr.reshape(-1, arr.shape[-1])
+            k = max(1, budget // rows[0].nbytes)
+            arr = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))]
+            what = f"{k} sampled rows of {rows.shape[0]}"
+        np.save(d / f"{name}.npy", arr)
+        note(f"wrote {d / name}.npy ({what}, {arr.dtype})")
+
+
 def worker(a):
     # Before the first HIP call of this process (HSA reads it when the runtime opens): the host driver of this pool
     # only supports dmabuf IPC, and RCCL's / torch's cross-process device-memory handles fail with
@@ -883,7 +921,10 @@ def worker(a):
 
     wins = member_windows(my_members, perturbed=total_members > 1)
     aa = torch.from_numpy(syn.amino_acids(N, seed=1))
-    max_steps = a.warmup + a.steps + (0 if a.skip_roofline else a.steps)
+    # the measurement legs run only under --full (a plain run: set-up, warm-up, the K timed steps, the line)
+    roofline_leg = a.full and not a.skip_roofline
+    cpu_leg = a.full and rank == 0 and world == 1 and not a.skip_cpu_baseline and a.variant == "intree"
+    max_steps = a.warmup + a.steps + (a.steps if roofline_leg else 0)
     cap = default_edge_cap(M, N, a.threshold)
     def groups_for(members):
         # four members per group (8 members: 2 groups 582 vs 4 groups 577 frames/s; 64 members: 4 / 8 / 16 groups
@@ -916,7 +957,7 @@ def worker(a):
     eng.step(a.warmup)
     eng.synchronize()
     # first produced frame of member 0 (kept for the cpu_baseline leg's parity figure)
-    first_frame_gpu = eng.traj[W, 0].detach().cpu().numpy() if (a.warmup > 0 and total_members == 1) else None
+    first_frame_gpu = eng.traj[W, 0].detach().cpu().numpy() if (cpu_leg and a.warmup > 0 and total_members == 1) else None
     m_max = -(-total_members // world)
     t_first_gather = None
     if use_dist:     # the collective of the timed region, once, untimed, on the same path (the groups' frames concatenated,
@@ -971,6 +1012,8 @@ def worker(a):
     value = frames / elapsed
     if rank == 0:
         note(f"timed region: {value:.1f} frames/s ({elapsed / a.steps * 1e3:.3f} ms/step)")
+        if a.dump_outputs:       # the last timed step's frames, every member (full is the gathered trajectory)
+            dump_outputs(a.dump_outputs, {"frames_last_step": full[-1].detach().cpu().numpy()})
 
     # ---- roofline leg: K more steps of the SAME rollout, plain launches bracketed by HIP events on
     # the launch stream (events cannot sit inside a hipGraph replay).  Rank 0 only.
@@ -1065,7 +1108,7 @@ def worker(a):
         return r
 
     # rank 0 only: the other ranks idle at the final barrier through the measurement legs
-    if not a.skip_roofline and rank == 0:
+    if roofline_leg and rank == 0:
         kernels, e2 = timed_leg(eng_r, a.warmup + a.steps, M_r)
         if mode == "materialized":
             roofs["conv_materialized"] = conv_roofline(kernels, e2)
@@ -1111,9 +1154,9 @@ def worker(a):
             dominant = have[max(have, key=lambda k: kernels[k]["ms_per_step"])]
 
     # ---- cfg3's like-for-like single-GPU figure: the SAME 64-member ensemble the N > 1 runs shard, on
-    # this one GPU (default N=1 run only; `--gpus 1 --total-members 64` makes it the headline instead)
+    # this one GPU (N=1 --full run with the default workload only; `--gpus 1 --total-members 64` makes it the headline instead)
     ensemble_leg = None
-    default_single = (world == 1 and a.total_members is None and a.members_per_gpu is None
+    default_single = (a.full and world == 1 and a.total_members is None and a.members_per_gpu is None
                       and a.variant == "intree" and not a.chain)
     if default_single and not a.skip_ensemble_leg:
         eng.close()
@@ -1178,7 +1221,7 @@ def worker(a):
         share_leg = leg_rank_share(a, ensemble_leg)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.skip_cpu_baseline and a.variant == "intree":
+    if cpu_leg:
         cpu = cpu_baseline(sd, a.depth, base, aa, a.threshold, a.cpu_budget_s, first_frame_gpu)
         if cpu.get("parity_first_frame"):
             pf = cpu["parity_first_frame"]

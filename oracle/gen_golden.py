@@ -191,6 +191,7 @@ def gen_checkpoint(gk, out: Path):
     """A `best.pt`-shaped checkpoint (graph_kernel.py:630-639) written from the reference's own
     KernelNN wrapped as `main` wraps it (DataParallel -> `module.` key prefix, :528), stored as
     plain arrays, plus the reference forward it must reproduce once loaded."""
+    from oracle.golden_io import save_golden
     from molecular_dynamics_neural_operator_amd import synthetic as syn
     THR, N, W = 8.0, 28, 10
     win = syn.jitter_window(syn.chain_frame(N, seed=0), W, seed=0)
@@ -209,7 +210,7 @@ def gen_checkpoint(gk, out: Path):
     with torch.no_grad():
         out_ref = model(pd).numpy()
     arrays = {"msd/" + k: v.detach().numpy() for k, v in ckpt["model_state_dict"].items()}
-    np.savez_compressed(
+    save_golden(                       # over 1 MiB as one file: written in parts (oracle/golden_io.py)
         out / "checkpoint_best_pt.npz", epoch=ckpt["epoch"], ctor=np.array([64, 32, 2, 6, 7, 3, 20, 4]),
         scheduler_step_size=50, scheduler_gamma=0.8, optimizer_lr=0.01, optimizer_weight_decay=5e-4,
         x_position=win, x_aminoacid=aa.numpy(), edge_index=pd.edge_index.numpy(), edge_attr=pd.edge_attr.numpy(),
@@ -225,6 +226,7 @@ def gen_train_step(gk, ds, out: Path):
     parameter's gradient as left in `.grad`, and the parameters after the step.  Two sizes: width 8 /
     k 16 (weights stored) and width 64 / k 128 (the HIP training kernels' width; weights regenerated from
     the seed by the test, checksums stored)."""
+    from oracle.golden_io import save_golden
     from molecular_dynamics_neural_operator_amd import synthetic as syn
     THR, N, W = 8.0, 28, 10
     base = syn.chain_frame(N, seed=0)
@@ -278,7 +280,7 @@ def gen_train_step(gk, ds, out: Path):
                 arrays.update(_sd_np({k: v for k, v in after.items() if v.numel() <= 4096}, f"{tag}.a."))
             print(f"train_step {tag}: loss {avg_loss:.6f} mse {avg_mse:.6f}; |grad| max "
                   f"{max(float(g.abs().max()) for g in grads.values()):.3e}")
-    np.savez_compressed(
+    save_golden(                       # over 1 MiB as one file: written in parts (oracle/golden_io.py)
         out / "train_step_b1.npz", sample_index=idx, window=W, threshold=THR, lr=0.01, weight_decay=5e-4,
         point_cloud=np.transpose(traj, (0, 2, 1)).copy(), contact_map=cms, amino_acids=aa.numpy(),
         rmsd=np.zeros(T, np.float32),

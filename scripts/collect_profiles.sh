@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --skip-cpu-baseline --skip-ensemble-leg --skip-config-legs"
+B="python3 $ROOT/bench.py --full --skip-cpu-baseline --skip-ensemble-leg --skip-config-legs"
 for M in 1 8; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_m$M -- $B --steps 50 --warmup 5 --total-members $M > $OUT/bench_m$M.json 2> $OUT/trace_m$M.err
   echo "trace m$M done"

@@ -62,16 +62,16 @@ int main() {
     const int reps = 36;      // three steps' worth of applications
     printf("H %.1f MB, S %.1f MB, W3R %.1f MB; us per application (H read | S write | S read | W read | all four)\n", HB / 1e6, SB / 1e6, WB / 1e6);
     for (int pol = 0; pol < 4; ++pol) {
-        const bool s_store_nt = pol & 1, s_load_nt = pol & 2;
+        const bool S_nt_store = pol & 1, S_nt_load = pol & 2;
         for (size_t c_mib : {0ul, 64ul, 96ul, 128ul, 160ul, 192ul, 224ul, 240ul}) {
             const size_t cached16 = (c_mib << 20) / 16;
             auto app = [&](int phase_mask) {
                 if (phase_mask & 1) read_kernel<<<blocks(HB), 256, 0, st>>>(h, HB / 16, cached16, out, pw16);
                 if (phase_mask & 2) {
-                    if (s_store_nt) write_kernel<true><<<blocks(SB), 256, 0, st>>>(s, SB / 16, pw16, 1.f);
+                    if (S_nt_store) write_kernel<true><<<blocks(SB), 256, 0, st>>>(s, SB / 16, pw16, 1.f);
                     else write_kernel<false><<<blocks(SB), 256, 0, st>>>(s, SB / 16, pw16, 1.f);
                 }
-                if (phase_mask & 4) read_kernel<<<blocks(SB), 256, 0, st>>>(s, SB / 16, s_load_nt ? 0 : SB / 16, out, pw16);
+                if (phase_mask & 4) read_kernel<<<blocks(SB), 256, 0, st>>>(s, SB / 16, S_nt_load ? 0 : SB / 16, out, pw16);
                 if (phase_mask & 8) read_kernel<<<blocks(WB), 256, 0, st>>>(w, WB / 16, WB / 16, out, pw16);
             };
             for (int i = 0; i < 6; ++i) app(15);
@@ -90,7 +90,7 @@ int main() {
             }
             hipStreamSynchronize(st);
             printf("S stores %s, S loads %s, H cached %3zu MiB: application %.1f us, of which H read %.1f us (%.2f TB/s)\n",
-                   s_store_nt ? "nt " : "def", s_load_nt ? "nt " : "def", c_mib, ms / reps * 1e3, ms_h / reps * 1e3, HB / (ms_h / reps) / 1e9);
+                   S_nt_store ? "nt " : "def", S_nt_load ? "nt " : "def", c_mib, ms / reps * 1e3, ms_h / reps * 1e3, HB / (ms_h / reps) / 1e9);
         }
     }
     return 0;

@@ -1,4 +1,4 @@
-"""Print the headline and the per-kernel breakdown of a bench.py JSON line (file argument)."""
+"""Print the headline and the per-kernel breakdown of a `bench.py --full` JSON line (file argument)."""
 import json
 import sys
 

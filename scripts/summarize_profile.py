@@ -189,7 +189,7 @@ def mfma_summary(sub, dest, what, keep):
 
 
 mfma_summary("pmc_mfma_m1", out / f"{tag}_m1_pmc_mfma.json",
-             "python3 bench.py --skip-cpu-baseline --skip-ensemble-leg --single-mode --steps 3 --warmup 1 --no-graph "
+             "python3 bench.py --full --skip-cpu-baseline --skip-ensemble-leg --single-mode --steps 3 --warmup 1 --no-graph "
              "(1 member, N=504, split_f16)", ("gemm_split_f16_kernel", "moment_kernel", "project_f16_kernel", "project_kernel"))
 mfma_summary("pmc_mfma_train", out / f"{tag}_train_pmc_mfma.json",
              "python3 scripts/train_synthetic.py --frames 600 (cfg4 batch: 43.7k edges, k=1024, bf16)", ("gemm_pp_kernel",))

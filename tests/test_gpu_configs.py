@@ -904,9 +904,9 @@ def test_bench_multi_rank_line_schema(dev):
     box has (a one-GPU box: the ranks share the card, gloo; the box allows six GPU processes at once, this test
     holds one, so four ranks is what fits — the 8-rank rendezvous itself is rehearsed on CPU in test_dist_gloo.py):
     default strong scaling over the ensemble, an uneven shard (7 members over 4 ranks), `multi_gpu_timing` per
-    rank, rank 0's `roofline`, and NONE of the single-GPU legs (they belong to the N = 1 line)."""
+    rank, rank 0's `roofline` (a --full leg), and NONE of the single-GPU legs (they belong to the N = 1 line)."""
     line = _run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--total-members", "7", "--atoms", "28", "--chain",
-                       "--kernel-width", "128", "--depth", "2"])
+                       "--kernel-width", "128", "--depth", "2", "--full"])
     assert line["n_gpus"] == 4 and line["scaling"] == "strong" and line["value"] > 0 and line["higher_is_better"]
     assert line["metric"] == "rolled-out MD frames/sec" and line["unit"] == "frames/s" and line["dtype"] == "f32"
     assert line["steps"] == 2 and line["warmup"] == 1 and line["vs_baseline"] is None
@@ -1311,3 +1311,38 @@ def test_member_groups_on_concurrent_streams_give_the_same_frames(dev):
         assert torch.equal(eng.edges_per_step, want_edges)
         assert torch.equal(eng.traj[:W].cpu(), tm) and eng.steps_done == steps
         eng.close()
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_them(dev, tmp_path):
+    """A plain `bench.py` run: exactly --steps timed steps, `ms_per_step` on the line, none of the --full legs, and
+    --dump-outputs holding the frames of the last timed step — those RolloutEngine computes from the same seeded window
+    and weights after the warm-up and the K steps."""
+    from molecular_dynamics_neural_operator_amd import synthetic as syn
+    from molecular_dynamics_neural_operator_amd.graph_kernel import KernelNN
+    from molecular_dynamics_neural_operator_amd.rollout import RolloutEngine, default_edge_cap
+    from molecular_dynamics_neural_operator_amd.weights import near_identity_state_dict
+    N, W, K, warm = 60, 10, 3, 2
+    out = tmp_path / "dump"
+    line = _run_bench(["--gpus", "1", "--steps", str(K), "--warmup", str(warm), "--atoms", str(N), "--kernel-width", "128",
+                       "--depth", "2", "--dump-outputs", str(out)], timeout=300)
+    assert line["steps"] == K and line["warmup"] == warm and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]          # one member: frames/s = 1/step
+    for leg in ("roofline", "rooflines", "kernels", "other_conv_mode", "ensemble64_single_gpu", "baseline_1gpu_same_workload",
+                "per_rank_share_8gpu", "projected_speedup_8gpu", "cfg2_1000_steps", "cfg4_training", "cfg5_shape_c", "shape_A",
+                "cpu_baseline"):
+        assert line[leg] in (None, {}), leg
+    got = np.load(out / "frames_last_step.npy")
+    assert got.dtype == np.float32 and got.shape == (1, N, 3) and np.isfinite(got).all()
+    model = KernelNN(64, 128, 2, 6, 7, 3, 20, 4)
+    model.load_state_dict(near_identity_state_dict(64, 128, seed=0, kernel_gain=1e-3, feature_gain=0.1))
+    model.eval().to(dev)
+    model.gemm_mode, model.conv_mode = "split_f16", "auto"
+    eng = RolloutEngine(model, 1, N, W, 8.0, max_steps=warm + K, edge_cap=default_edge_cap(1, N, 8.0), device=dev)
+    eng.reset(torch.from_numpy(syn.jitter_window(syn.box_frame(N, seed=1), W, seed=1)), torch.from_numpy(syn.amino_acids(N, seed=1)))
+    eng.step(warm)
+    eng.synchronize()
+    eng.step(K)
+    eng.synchronize()
+    want = eng.produced(warm + K - 1, 1)[0].cpu().numpy()
+    eng.close()
+    close(got, want, name="bench --dump-outputs vs RolloutEngine")

@@ -308,3 +308,55 @@ def test_hdf5_writer_round_trip_and_errors(tmp_path):
         hdf5_io.read_datasets(str(tmp_path / "junk.h5"), ["contact_map"])
     with pytest.raises(hdf5_io.Hdf5Error, match="not written"):
         hdf5_io.write_datasets(str(tmp_path / "c.h5"), {"z": np.zeros(3, np.complex64)})
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's command line: the measurement legs are off unless --full; --dump-outputs writes float arrays as
+    DIR/<name>.npy, and one past the size budget as the same seeded sample of its rows on every call."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    x = np.random.default_rng(1).standard_normal((2, 5, 3)).astype(np.float32)
+    bench.dump_outputs(tmp_path / "small", {"frames": x})
+    got = np.load(tmp_path / "small" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 3 * 4)                   # room for 4 rows of 3 float32
+    big = np.arange(2 * 50 * 3, dtype=np.float64).reshape(2, 50, 3)
+    bench.dump_outputs(tmp_path / "s1", {"frames": big})
+    bench.dump_outputs(tmp_path / "s2", {"frames": big})
+    s1, s2 = np.load(tmp_path / "s1" / "frames.npy"), np.load(tmp_path / "s2" / "frames.npy")
+    assert s1.dtype == np.float64 and s1.nbytes <= bench.DUMP_MAX_BYTES and s1.shape[1] == 3 and np.array_equal(s1, s2)
+    rows = big.reshape(-1, 3)
+    idx = (s1[:, 0] / 3).astype(int)
+    assert np.array_equal(rows[idx], s1) and np.all(np.diff(idx) > 0)
+    with pytest.raises(ValueError, match="not float32"):
+        bench.dump_outputs(tmp_path / "i", {"ids": np.arange(3)})
+
+
+def test_golden_fixtures_fit_the_file_limit_and_parts_round_trip(tmp_path, monkeypatch):
+    """Every committed fixture is at most 1 MiB; a fixture stored in parts (oracle/golden_io.py) loads back as the same
+    arrays in the same order, an array split into pieces included."""
+    from conftest import GOLDEN
+    from oracle import golden_io
+    sizes = {p.name: p.stat().st_size for p in GOLDEN.iterdir() if p.is_file()}
+    assert all(s <= golden_io.MAX_FILE_BYTES for s in sizes.values()), sizes
+    monkeypatch.setattr(golden_io, "MAX_FILE_BYTES", 3000)
+    monkeypatch.setattr(golden_io, "PART_RAW_BYTES", 2048)
+    cm = np.empty(3, dtype=object)
+    cm[:] = [np.arange(4), np.arange(7), np.arange(2)]
+    arrays = {"small": np.arange(5, dtype=np.int64), "big": np.random.default_rng(0).standard_normal((100, 7)).astype(np.float32),
+              "contact_map": cm, "lr": 0.01}
+    written = golden_io.save_golden(tmp_path / "f.npz", **arrays)
+    assert len(written) > 1 and not (tmp_path / "f.npz").exists()
+    assert all(p.stat().st_size <= 3000 for p in written)
+    assert any("big@1" in np.load(p, allow_pickle=True).files for p in written)
+    back = golden_io.load_golden(tmp_path / "f.npz")
+    assert back.files == list(arrays)
+    assert back["big"].dtype == np.float32 and back["big"].tobytes() == arrays["big"].tobytes()
+    assert np.array_equal(back["small"], arrays["small"]) and float(back["lr"]) == 0.01
+    assert all(np.array_equal(a, b) for a, b in zip(back["contact_map"], cm))
+    monkeypatch.setattr(golden_io, "MAX_FILE_BYTES", 1 << 20)
+    assert golden_io.save_golden(tmp_path / "f.npz", **arrays) == [tmp_path / "f.npz"]      # fits: one file, parts gone
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["f.npz"]

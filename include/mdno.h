@@ -42,7 +42,8 @@ extern "C" {
 
 #define MDNO_AGGR_ADD  0
 #define MDNO_AGGR_MEAN 1
-#define MDNO_AGGR_MAX  2   /* mdno_nnconv_fwd only (inference): per-channel max over a node's messages, 0 for no message */
+#define MDNO_AGGR_MAX  2   /* mdno_nnconv_fwd (not inside the model): per-channel max over a node's messages, 0 for no
+                              message; backward: mdno_nnconv_msg_grad */
 
 /* How the two wide edge-MLP GEMMs are evaluated (fp32 in, fp32 out either way):
  *   SPLIT_BF16  every fp32 operand is split exactly into 3 bf16 planes and the product accumulated
@@ -546,6 +547,39 @@ int mdno_node_prologue_bwd(const mdno_kernelnn_params* p, const float* frames, i
 size_t mdno_fc_out_bwd_workspace_bytes(int rows, int width, int out_width);
 int mdno_fc_out_bwd(const float* x, const float* w, const float* g, int rows, int width, int out_width,
                     float* dx, float* d_w, float* d_b, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Backward of the stand-alone layers (csrc/layer_grad.hip): NNConv_old (graph_kernel.py:125-214, message :202-203,
+ * update :205-209, aggregation by torch_geometric's MessagePassing.propagate) for any Cin, Cout and aggr add / mean /
+ * max, and DenseNet (:217-242) with ReLU.  Forward as mdno_nnconv_fwd (relu = 0):
+ *   y[t] = aggr_{e -> t}(m_e) + x[t] . root + bias,  m_e = x[src e] . W_e,  W_e f32 [Cin, Cout] row-major per edge
+ * in the graph's destination-sorted (CSR) order; g = dLoss/dy f32 [R, Cout].  The edge count is row_ptr[num_rows]
+ * (read on the device).  Fixed summation orders, no atomics: bitwise reproducible.
+ *   mdno_nnconv_msg_grad      gm f32 [E, Cout] = dLoss/dm_e:  add  g[dst e];  mean  g[dst e] / max(deg, 1);
+ *                             max  the row's messages recomputed (i ascending), per channel the maximum and the number
+ *                             of edges that reach it ("ties"): those edges get g[t][o] / ties, the others 0 — torch's
+ *                             scatter_reduce(amax, include_self=False) backward.  x, src, w_e are read for max only.
+ *   mdno_nnconv_bwd_x_edges   dx [R, Cin] = g . root^T + sum_{e: src e = r} W_e . gm_e, edges grouped by source as for
+ *                             mdno_nnconv_bwd_x (row_ptr_s, eid_s from mdno_csr_by_source); root may be NULL (g is then
+ *                             unused).  Cout <= 4096.
+ *   mdno_nnconv_bwd_we_edges  d_we [E, Cin*Cout] = x[src e] (x) gm_e                  (all overwritten)
+ *   mdno_scale_rows           out[r][c] = a[r][c] * scale[r]  (gs = g * inv_deg for mdno_nnconv_bwd_x / _we at 64x64)
+ *   mdno_relu_mask_bwd        out = g where y > 0, else 0: torch's ReLU backward on the output, any element count
+ *                             (DenseNet's hidden layers, graph_kernel.py:239-242)
+ *   mdno_scatter_rows         out[perm[p]] = in[p]: the inverse of mdno_permute_rows (a gradient back into COO order)
+ * d root = x^T . g and d bias = colsum(g) are mdno_gemm_atb / mdno_colsum; through the edge network dA = dY . W is
+ * mdno_linear_fwd with W transposed (mdno_transpose) and dW = dY^T . A is mdno_gemm_atb.
+ * ---------------------------------------------------------------------------------------- */
+int mdno_nnconv_msg_grad(const float* x, const int32_t* row_ptr, const int32_t* src, int num_rows, const float* w_e,
+                         const float* g, int Cin, int Cout, int aggr, float* gm, void* stream);
+int mdno_nnconv_bwd_x_edges(const float* gm, const float* g, const int32_t* row_ptr_s, const int32_t* eid_s,
+                            int num_rows, const float* w_e, const float* root, int Cin, int Cout, float* dx,
+                            void* stream);
+int mdno_nnconv_bwd_we_edges(const float* x, const float* gm, const int32_t* row_ptr, const int32_t* src, int num_rows,
+                             int Cin, int Cout, float* d_we, void* stream);
+int mdno_scale_rows(const float* a, const float* scale, int64_t rows, int n, float* out, void* stream);
+int mdno_relu_mask_bwd(const float* g, const float* y, int64_t count, float* out, void* stream);
+int mdno_scatter_rows(const float* in, const int32_t* perm, int64_t rows, int width, float* out, void* stream);
 
 #ifdef __cplusplus
 }

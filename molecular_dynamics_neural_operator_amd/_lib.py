@@ -12,7 +12,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("MDNO_LIB", _HERE / "libmdno.so"))
 
 OK, EINVAL, ELAUNCH, EWORKSPACE, EUNSUPPORTED = 0, -1, -2, -3, -4
-AGGR = {"add": 0, "mean": 1, "max": 2}      # "max": mdno_nnconv_fwd only (inference)
+AGGR = {"add": 0, "mean": 1, "max": 2}      # "max": mdno_nnconv_fwd (stand-alone conv) and mdno_nnconv_msg_grad
 STATUS_EDGE_OVERFLOW, STATUS_BAD_AMINOACID = 1, 2
 ABI_VERSION = 15
 GEMM_MODES = {"split_bf16": 0, "f32": 1, "split_f16": 2}
@@ -134,6 +134,12 @@ SIGNATURES = {
     "mdno_collate_samples": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mdno_lploss_rel_fwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "mdno_lploss_rel_bwd": (_I, [_P, _P, _P, _P, _L, _I, _I, _P, _P]),
+    "mdno_nnconv_msg_grad": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "mdno_nnconv_bwd_x_edges": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
+    "mdno_nnconv_bwd_we_edges": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "mdno_scale_rows": (_I, [_P, _P, _L, _I, _P, _P]),
+    "mdno_relu_mask_bwd": (_I, [_P, _P, _L, _P, _P]),
+    "mdno_scatter_rows": (_I, [_P, _P, _L, _I, _P, _P]),
 }
 
 _lib = None

@@ -17,8 +17,10 @@ Differences from the reference, all explicit:
   * B=1 semantics per sample: a list of samples or a collated batch runs as independent
     block-diagonal members of one forward (``validate``, graph_kernel.py:476-493 -> ``training.validate_epoch``).
   * ``KernelNN.forward`` in training mode with autograd enabled runs the differentiable path of
-    ``training.py`` (HIP forward + backward of the kernel-integral block, fp32); stand-alone
-    ``NNConv_old`` / ``DenseNet`` forwards are inference-only and raise in that situation.
+    ``training.py`` (HIP forward + backward of the kernel-integral block, fp32).  Stand-alone
+    ``NNConv_old`` / ``DenseNet`` forwards are inference-only and raise in that situation unless the module's
+    ``differentiable`` flag is set (constructor keyword, attribute, or ``enable_autograd(model)``): they then run
+    through autograd Functions whose backward is HIP (csrc/layer_grad.hip), in fp32.
 """
 from __future__ import annotations
 
@@ -59,6 +61,102 @@ def _no_training(module: nn.Module) -> None:
         raise NotImplementedError(
             "a stand-alone NNConv_old / DenseNet forward is inference-only (the differentiable HIP path is "
             "KernelNN.forward in training mode, training.py): call .eval() or run under torch.no_grad()")
+
+
+def enable_autograd(module: nn.Module, on: bool = True) -> nn.Module:
+    """Set the ``differentiable`` flag of every ``NNConv_old`` and ``DenseNet`` inside ``module`` (itself included), so
+    that a model built from these layers by other code trains through autograd.  Returns ``module``."""
+    for m in module.modules():
+        if isinstance(m, (NNConv_old, DenseNet)):
+            m.differentiable = bool(on)
+    return module
+
+
+def _wants_grad(module: nn.Module, *tensors) -> bool:
+    """The differentiable path applies: the flag is set, autograd records, and an input or a parameter needs a gradient."""
+    if not getattr(module, "differentiable", False) or not torch.is_grad_enabled():
+        return False
+    return any(t is not None and t.requires_grad for t in tensors) or any(p.requires_grad for p in module.parameters())
+
+
+def _refuse_double_backward() -> None:
+    # autograd runs a Function's backward with grad mode on exactly when the caller asked for create_graph=True
+    if torch.is_grad_enabled():
+        raise NotImplementedError("NNConv_old / DenseNet: double backward (create_graph=True) is not implemented; the "
+                                  "HIP backward is first order only")
+
+
+class _PermuteRowsFn(torch.autograd.Function):
+    """out[p] = x[perm[p]] (per-edge rows into the graph's CSR order, mdno_permute_rows); the backward puts the
+    gradient rows back (mdno_scatter_rows)."""
+
+    @staticmethod
+    def forward(ctx, x, perm):
+        ctx.save_for_backward(perm)
+        return ops.permute_rows(x, perm, perm.numel())
+
+    @staticmethod
+    def backward(ctx, g):
+        _refuse_double_backward()
+        perm, = ctx.saved_tensors
+        return ops.scatter_rows(g, perm, perm.numel()), None
+
+
+class _DenseNetFn(torch.autograd.Function):
+    """A chain of Linear layers, each followed by a ReLU where ``relus`` says so (DenseNet, graph_kernel.py:239-242; the
+    model's edge-MLP Linear-ReLU-Linear-ReLU-Linear is the three-layer case).  The forward keeps every layer's output
+    (h1, h2, ...) for the backward; all products are fp32 (mdno_linear_fwd, gemm_mode "f32").  ``wb`` = w0, b0, w1, b1, ...
+    in torch Linear layout, a bias may be None."""
+
+    @staticmethod
+    def forward(ctx, relus, x, *wb):
+        acts = [ops.f32(x)]
+        for j, relu in enumerate(relus):
+            acts.append(ops.linear(acts[-1], wb[2 * j], wb[2 * j + 1], relu=relu, gemm_mode="f32"))
+        ctx.relus = relus
+        ctx.save_for_backward(*acts, *wb)
+        return acts[-1]
+
+    @staticmethod
+    def backward(ctx, g):
+        _refuse_double_backward()
+        relus = ctx.relus
+        L = len(relus)
+        saved = ctx.saved_tensors
+        acts, wb = saved[:L + 1], saved[L + 1:]
+        grads = [None] * (2 * L)
+        g = ops.f32(g)
+        for j in reversed(range(L)):
+            if relus[j]:
+                g = ops.relu_mask_bwd(g, acts[j + 1])
+            if ctx.needs_input_grad[2 + 2 * j]:
+                grads[2 * j] = ops.gemm_atb(g, acts[j])                 # dW_j = g^T . a_j  [out, in]
+            if wb[2 * j + 1] is not None and ctx.needs_input_grad[3 + 2 * j]:
+                grads[2 * j + 1] = ops.colsum(g)
+            if j > 0 or ctx.needs_input_grad[1]:
+                g = ops.linear(g, ops.transpose(wb[2 * j]), None, gemm_mode="f32")     # g . W_j
+        return (None, g if ctx.needs_input_grad[1] else None, *grads)
+
+
+class _NNConvFn(torch.autograd.Function):
+    """y = nnconv(x, graph, w_e, root, bias, aggr) (mdno_nnconv_fwd, relu off) with the HIP backward of ops.nnconv_bwd:
+    gradients for x [R,Cin], w_e [E,Cin*Cout] (CSR order), root and bias, whichever need one."""
+
+    @staticmethod
+    def forward(ctx, x, w_e, root, bias, graph, aggr, generic):
+        x, w_e = ops.f32(x), ops.f32(w_e)
+        y = ops.nnconv(x, graph, w_e, root, bias, aggr)
+        ctx.graph, ctx.aggr, ctx.generic = graph, aggr, generic
+        ctx.save_for_backward(x, w_e, root)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        _refuse_double_backward()
+        x, w_e, root = ctx.saved_tensors
+        dx, d_we, d_root, d_bias = ops.nnconv_bwd(x, ctx.graph, w_e, root, g, ctx.aggr, need=ctx.needs_input_grad[:4],
+                                                  generic=ctx.generic)
+        return dx, d_we, d_root, d_bias, None, None, None
 
 
 # --------------------------------------------------------------------------- loss
@@ -135,8 +233,10 @@ class DenseNet(nn.Module):
     front of it) and a ReLU ``out_nonlinearity`` run layer by layer on the library's Linear kernel.  Other
     nonlinearities and batch statistics (BatchNorm1d in training mode) are not implemented."""
 
-    def __init__(self, layers, nonlinearity, out_nonlinearity=None, normalize=False):
+    def __init__(self, layers, nonlinearity, out_nonlinearity=None, normalize=False, differentiable=False):
         super().__init__()
+        # True: with autograd recording and a gradient wanted, forward runs the differentiable HIP path (_DenseNetFn)
+        self.differentiable = differentiable
         self.n_layers = len(layers) - 1
         assert self.n_layers >= 1
         self.layers = nn.ModuleList()
@@ -160,9 +260,12 @@ class DenseNet(nn.Module):
         l0, l2, l4 = self.layers[0], self.layers[2], self.layers[4]
         return (l0.weight, l0.bias, l2.weight, l2.bias, l4.weight, l4.bias)
 
-    def _layerwise(self, x):
-        """Any depth / eval-mode BatchNorm / ReLU output: one Linear kernel per layer (graph_kernel.py:239-242)."""
+    def _layer_plan(self):
+        """[(w, b, relu)] per Linear: an eval-mode BatchNorm1d folded into the Linear in front of it (as torch
+        expressions, so that its gradient reaches bn.weight / bn.bias), ReLU after it where the module has one.
+        Raises on anything else (batch statistics, other nonlinearities)."""
         mods = list(self.layers)
+        plan = []
         i = 0
         while i < len(mods):
             lin = mods[i]
@@ -184,10 +287,24 @@ class DenseNet(nn.Module):
                     raise NotImplementedError(f"DenseNet: nonlinearity {type(mods[i]).__name__} (the HIP path has ReLU)")
                 relu = True
                 i += 1
+            plan.append((w, b, relu))
+        return plan
+
+    def _layerwise(self, x):
+        """Any depth / eval-mode BatchNorm / ReLU output: one Linear kernel per layer (graph_kernel.py:239-242)."""
+        for w, b, relu in self._layer_plan():
             x = ops.linear(x, w, b, relu=relu)
         return x
 
+    def _forward_grad(self, x):
+        """The differentiable path: _DenseNetFn over the layer plan (fp32 products, HIP backward)."""
+        plan = self._layer_plan()
+        wb = [t for w, b, _ in plan for t in (w, b)]
+        return _DenseNetFn.apply(tuple(r for _, _, r in plan), x, *wb)
+
     def forward(self, x):
+        if _wants_grad(self, x):
+            return self._forward_grad(x)
         _no_training(self)
         if not self._hip_ok:
             with torch.no_grad():
@@ -205,8 +322,14 @@ class DenseNet(nn.Module):
 class NNConv_old(nn.Module):
     """Edge-conditioned convolution, ``out_i = aggr_j(x_j . net(e_ji)) + x_i . root + bias``."""
 
-    def __init__(self, in_channels, out_channels, net, aggr="add", root_weight=True, bias=True, **kwargs):
+    # the backward at 64x64 add / mean runs the model's tuned training kernels; True sends it through the generic ones
+    _generic_backward = False
+
+    def __init__(self, in_channels, out_channels, net, aggr="add", root_weight=True, bias=True, differentiable=False,
+                 **kwargs):
         super().__init__()
+        # True: with autograd recording and a gradient wanted, forward runs the differentiable HIP path (_NNConvFn)
+        self.differentiable = differentiable
         if kwargs.get("flow", "source_to_target") != "source_to_target" or kwargs.get("node_dim", -2) != -2:
             raise NotImplementedError("only flow='source_to_target', node_dim=-2 (the reference's defaults)")
         self.in_channels = in_channels
@@ -230,6 +353,8 @@ class NNConv_old(nn.Module):
         uniform(size, self.bias)
 
     def forward(self, x, edge_index, edge_attr):
+        if _wants_grad(self, x, edge_attr):
+            return self._forward_grad(x, edge_index, edge_attr)
         _no_training(self)
         x = x.unsqueeze(-1) if x.dim() == 1 else x
         pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
@@ -243,6 +368,26 @@ class NNConv_old(nn.Module):
             else:       # any other edge network: evaluated in COO order, rows then put in the conv's edge order
                 w_e = self.net(pseudo).index_select(0, graph.perm[:pseudo.shape[0]].long()).contiguous()
             return ops.nnconv(x, graph, w_e, self.root, self.bias, self.aggr, relu=False)
+
+    def _forward_grad(self, x, edge_index, edge_attr):
+        """The differentiable path: the edge network evaluated in the conv's CSR edge order (a DenseNet through
+        _DenseNetFn; any other module by torch autograd in COO order, its rows then permuted), then _NNConvFn.  x and
+        edge_attr may themselves need gradients."""
+        x = x.unsqueeze(-1) if x.dim() == 1 else x
+        pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
+        if self.aggr not in ("add", "mean", "max"):
+            raise NotImplementedError(f"aggr={self.aggr!r}: the HIP path implements 'add', 'mean' and 'max'")
+        with torch.no_grad():
+            graph = ops.coo_to_csr(edge_index, x.shape[0])
+        perm = graph.perm[:pseudo.shape[0]]
+        if isinstance(self.net, DenseNet):
+            w_e = self.net._forward_grad(_PermuteRowsFn.apply(pseudo.float(), perm))
+        else:
+            w_e = _PermuteRowsFn.apply(self.net(pseudo).float(), perm)
+        if w_e.shape[-1] != self.in_channels * self.out_channels:
+            raise MdnoError(f"NNConv_old: net gives {w_e.shape[-1]} values per edge, expected "
+                            f"{self.in_channels} x {self.out_channels}")
+        return _NNConvFn.apply(x.float(), w_e, self.root, self.bias, graph, self.aggr, bool(self._generic_backward))
 
     def __repr__(self):
         return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)

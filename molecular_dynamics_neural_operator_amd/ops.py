@@ -788,3 +788,105 @@ def lploss_rel_bwd(out: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, grad
     check(lib.mdno_lploss_rel_bwd(ptr(out), ptr(y), ptr(stats), ptr(gl), B, D, int(bool(size_average)), ptr(g),
                                   stream_ptr(out.device)), "mdno_lploss_rel_bwd")
     return g
+
+
+# ------------------------------------------------------------------------------------------------
+# Backward of the stand-alone NNConv_old / DenseNet (include/mdno.h "Backward of the stand-alone layers",
+# csrc/layer_grad.hip); graph_kernel.py's autograd Functions call these.
+def nnconv_msg_grad(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, g: torch.Tensor, aggr: str) -> torch.Tensor:
+    """gm f32 [E, Cout] = dLoss/dm_e in the graph's CSR edge order (max: ties share g evenly)."""
+    lib = _lib.load()
+    x, g = f32(x), f32(g)
+    R, cin = x.shape
+    cout = g.shape[1]
+    gm = torch.empty((max(graph.edge_count(), 1), cout), dtype=torch.float32, device=x.device)
+    check(lib.mdno_nnconv_msg_grad(ptr(x), ptr(graph.row_ptr), ptr(graph.src), R, ptr(w_e), ptr(g), cin, cout, AGGR[aggr],
+                                   ptr(gm), stream_ptr(x.device)), "mdno_nnconv_msg_grad")
+    return gm
+
+
+def nnconv_bwd_x_edges(gm: torch.Tensor, g: torch.Tensor, by_src: CSRGraph, w_e: torch.Tensor,
+                       root: Optional[torch.Tensor], cin: int) -> torch.Tensor:
+    """dx [R, Cin] = g . root^T + sum over each row's out-edges of W_e . gm_e (any Cin, Cout)."""
+    lib = _lib.load()
+    g = f32(g)
+    R, cout = g.shape
+    dx = torch.empty((R, cin), dtype=torch.float32, device=g.device)
+    check(lib.mdno_nnconv_bwd_x_edges(ptr(gm), ptr(g), ptr(by_src.row_ptr), ptr(by_src.perm), R, ptr(w_e),
+                                      ptr(f32(root)) if root is not None else None, cin, cout, ptr(dx),
+                                      stream_ptr(g.device)), "mdno_nnconv_bwd_x_edges")
+    return dx
+
+
+def nnconv_bwd_we_edges(x: torch.Tensor, gm: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
+    """d_we [E, Cin*Cout] = x[src e] (x) gm_e, CSR edge order."""
+    lib = _lib.load()
+    x = f32(x)
+    R, cin = x.shape
+    cout = gm.shape[1]
+    e = graph.edge_count()
+    d_we = torch.empty((e, cin * cout), dtype=torch.float32, device=x.device)
+    if e > 0:
+        check(lib.mdno_nnconv_bwd_we_edges(ptr(x), ptr(gm), ptr(graph.row_ptr), ptr(graph.src), R, cin, cout, ptr(d_we),
+                                           stream_ptr(x.device)), "mdno_nnconv_bwd_we_edges")
+    return d_we
+
+
+def scale_rows(a: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    lib = _lib.load()
+    a = f32(a)
+    rows, n = a.shape
+    out = torch.empty_like(a)
+    check(lib.mdno_scale_rows(ptr(a), ptr(f32(scale)), rows, n, ptr(out), stream_ptr(a.device)), "mdno_scale_rows")
+    return out
+
+
+def relu_mask_bwd(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """g where y > 0, else 0 (any shape)."""
+    lib = _lib.load()
+    g, y = f32(g), f32(y)
+    out = torch.empty_like(g)
+    check(lib.mdno_relu_mask_bwd(ptr(g), ptr(y), g.numel(), ptr(out), stream_ptr(g.device)), "mdno_relu_mask_bwd")
+    return out
+
+
+def scatter_rows(x: torch.Tensor, perm: torch.Tensor, rows: int) -> torch.Tensor:
+    """out[perm[p]] = x[p] for p < rows: the inverse of `permute_rows` (CSR order back to the input's edge order)."""
+    lib = _lib.load()
+    x = f32(x)
+    out = torch.empty((rows,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    width = int(x[0].numel()) if x.shape[0] else 1
+    check(lib.mdno_scatter_rows(ptr(x), ptr(perm), rows, width, ptr(out), stream_ptr(x.device)), "mdno_scatter_rows")
+    return out
+
+
+def nnconv_bwd(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root: Optional[torch.Tensor], g: torch.Tensor,
+               aggr: str, need=(True, True, True, True), generic: bool = False):
+    """Gradients of y = nnconv(x, graph, w_e, root, bias, aggr) (relu off) for g = dLoss/dy ->
+    (dx [R,Cin], d_we [E,Cin*Cout] in CSR order, d_root [Cin,Cout], d_bias [Cout]); an entry is None where `need` says
+    so.  64x64 add / mean run the model's tuned training kernels (mdno_nnconv_bwd_x / _we with gs = g / max(deg, 1))
+    unless `generic`; everything else goes through the per-edge message gradient (mdno_nnconv_msg_grad)."""
+    x, g = f32(x), f32(g)
+    R, cin = x.shape
+    cout = g.shape[1]
+    e = graph.edge_count()
+    need_x, need_w, need_root, need_bias = need
+    dx = d_we = d_root = d_bias = None
+    by_src = source_sorted(graph, R) if need_x else None
+    if not generic and cin == 64 and cout == 64 and aggr in ("add", "mean") and e > 0:
+        gs = scale_rows(g, inv_degree(graph, aggr)) if aggr == "mean" else g
+        if need_x:
+            dx = nnconv_bwd_x(g, gs, by_src, w_e, root)
+        if need_w:
+            d_we = nnconv_bwd_we(x.unsqueeze(0), gs.unsqueeze(0), graph)
+    elif need_x or need_w:
+        gm = nnconv_msg_grad(x, graph, w_e, g, aggr)
+        if need_x:
+            dx = nnconv_bwd_x_edges(gm, g, by_src, w_e, root, cin)
+        if need_w:
+            d_we = nnconv_bwd_we_edges(x, gm, graph)
+    if need_root and root is not None:
+        d_root = gemm_atb(x, g)
+    if need_bias:
+        d_bias = colsum(g)
+    return dx, d_we, d_root, d_bias

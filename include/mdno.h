@@ -332,6 +332,23 @@ int mdno_adam_step(int count, const mdno_adam_tensor* tensors, double lr, double
                    double weight_decay, int64_t step, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The gradient bucket of data-parallel training (the gradient reduce-add torch_geometric's DataParallel does before
+ * train()'s `optimizer.step()`, graph_kernel.py:467, :528): a list of fp32 tensors copied into (pack) or out of (unpack)
+ * ONE flat fp32 buffer in one launch (several only for lists longer than a kernel argument holds), so that the ranks
+ * reduce one buffer with one all-reduce.  `tensors`: HOST array of `count` entries (device pointer, element count,
+ * offset of the slot in elements of `flat`).  Pack zero-fills the slot of an entry whose data is NULL; unpack needs
+ * data for every non-empty entry.  A null `flat`, a negative numel or offset, or two slots that overlap return
+ * MDNO_EINVAL before any device work.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mdno_flat_tensor {
+    float* data;
+    int64_t numel;
+    int64_t offset;
+} mdno_flat_tensor;
+int mdno_pack_tensors(int count, const mdno_flat_tensor* tensors, float* flat, void* stream);
+int mdno_unpack_tensors(int count, const mdno_flat_tensor* tensors, const float* flat, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training ops (BASELINE configs[3]) — the backward of the kernel-integral block that autograd +
  * torch_geometric provide to train() (graph_kernel.py:445-474) for the path :299-302 / :194-209 /
  * :239-242.  All fp32; row/edge reductions use fixed-order partial sums (bitwise reproducible).

@@ -306,6 +306,49 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, lr: float, beta1: float, bet
                                      stream_ptr(params[0].device)), "mdno_adam_step")
 
 
+class FlatTensor(C.Structure):
+    """include/mdno.h mdno_flat_tensor"""
+    _fields_ = [("data", C.c_void_p), ("numel", C.c_int64), ("offset", C.c_int64)]
+
+
+def _flat_table(tensors, flat: Optional[torch.Tensor], offsets, what: str):
+    if len(tensors) != len(offsets):
+        raise MdnoError(f"{what}: {len(tensors)} tensors but {len(offsets)} offsets")
+    if flat is not None and flat.dtype != torch.float32:
+        raise MdnoError(f"{what}: the flat buffer must be fp32")
+    arr = (FlatTensor * max(len(tensors), 1))()
+    for i, (t, off) in enumerate(zip(tensors, offsets)):
+        if isinstance(t, int):                 # (pack only) a slot of this many elements without data: zero-filled
+            data, n = None, t
+        else:
+            if t.dtype != torch.float32:
+                raise MdnoError(f"{what}: fp32 tensors only (tensor {i} is {t.dtype})")
+            data, n = ptr(t), t.numel()
+        # the library cannot see the flat buffer's size: the slot must lie inside it
+        if flat is not None and int(off) >= 0 and n >= 0 and int(off) + n > flat.numel():
+            raise MdnoError(f"{what}: slot {i} [{int(off)}, {int(off) + n}) lies outside the flat buffer of {flat.numel()}")
+        arr[i] = FlatTensor(data, n, int(off))
+    return arr
+
+
+def pack_tensors(tensors, flat: torch.Tensor, offsets) -> torch.Tensor:
+    """flat[offsets[i] : offsets[i] + numel_i] = tensors[i] for every fp32 tensor of the list, in ONE launch
+    (include/mdno.h mdno_pack_tensors), on the current stream.  An entry given as an int n instead of a tensor
+    zero-fills a slot of n elements.  Returns flat."""
+    arr = _flat_table(tensors, flat, offsets, "pack_tensors")
+    check(_lib.load().mdno_pack_tensors(len(tensors), arr, ptr(flat), stream_ptr(flat.device if flat is not None else None)),
+          "mdno_pack_tensors")
+    return flat
+
+
+def unpack_tensors(flat: torch.Tensor, tensors, offsets) -> None:
+    """tensors[i] (in place) = flat[offsets[i] : offsets[i] + numel_i], in ONE launch (include/mdno.h
+    mdno_unpack_tensors), on the current stream."""
+    arr = _flat_table(tensors, flat, offsets, "unpack_tensors")
+    check(_lib.load().mdno_unpack_tensors(len(tensors), arr, ptr(flat), stream_ptr(flat.device if flat is not None else None)),
+          "mdno_unpack_tensors")
+
+
 # ------------------------------------------------------------------------------------------------
 # Training ops (include/mdno.h "Training ops"): thin wrappers, torch only allocates the outputs.
 def _ws(nbytes: int, dev) -> torch.Tensor:

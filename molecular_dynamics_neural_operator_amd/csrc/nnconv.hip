@@ -35,6 +35,10 @@ __device__ __forceinline__ float4 ld4_stream(const float* p) {
     return make_float4(t.x, t.y, t.z, t.w);
 }
 
+// max aggregation as torch has it (index_reduce_ / scatter_reduce "amax", torch_geometric's scatter max): a NaN message
+// wins and stays.  fmaxf (v_max_f32) returns the other operand, so a diverged edge would leave its row finite
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+
 __device__ __forceinline__ void fma4(float4& a, float s, const float4& w) {
     a.x = fmaf(s, w.x, a.x);
     a.y = fmaf(s, w.y, a.y);
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_row_kernel(
                 float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
                 edge_accumulate64<STREAM>(m, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
                 m = reduce_over_g(m);
-                acc = make_float4(fmaxf(acc.x, m.x), fmaxf(acc.y, m.y), fmaxf(acc.z, m.z), fmaxf(acc.w, m.w));
+                acc = make_float4(max_nan(acc.x, m.x), max_nan(acc.y, m.y), max_nan(acc.z, m.z), max_nan(acc.w, m.w));
             }
         }
         if (lane < 16) *reinterpret_cast<float4*>(&red[wave + u * WAVES][4 * lane]) = acc;
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_row_kernel(
         } else if (deg > 0) {
             s = red[0][tid];
 #pragma unroll
-            for (int c = 1; c < CHAINS; ++c) s = fmaxf(s, red[c][tid]);
+            for (int c = 1; c < CHAINS; ++c) s = max_nan(s, red[c][tid]);
         }
         if (aggr == MDNO_AGGR_MEAN) s = s / (float)(deg > 1 ? deg : 1);
         if (root != nullptr) s += rootred[tid];
@@ -270,7 +274,7 @@ __global__ __launch_bounds__(256) void nnconv_generic_kernel(
             const float* w = w_e + (size_t)p * Cin * Cout + o;
             float m = 0.f;
             for (int i = 0; i < Cin; ++i) m = fmaf(xj[i], w[(size_t)i * Cout], m);
-            s = aggr != MDNO_AGGR_MAX ? s + m : (p == beg ? m : fmaxf(s, m));
+            s = aggr != MDNO_AGGR_MAX ? s + m : (p == beg ? m : max_nan(s, m));
         }
         if (aggr == MDNO_AGGR_MEAN) s = s / (float)(deg > 1 ? deg : 1);
         if (root != nullptr) {

@@ -37,6 +37,7 @@ from ._lib import MdnoError, require_gpu
 from .dataset import ContactMapDataset, PairData  # noqa: F401  (re-exported like the reference)
 
 EPS = 1e-15
+EDGE_MLP_MAX_IN = 8         # input features of the fused edge-MLP kernels (csrc/edge_mlp.hip MAX_F)
 
 
 # --------------------------------------------------------------------------- init helpers
@@ -249,8 +250,10 @@ class DenseNet(nn.Module):
         if out_nonlinearity is not None:
             self.layers.append(out_nonlinearity())
         self._hip_ok = (self.n_layers == 3 and not normalize and out_nonlinearity is None
-                        and nonlinearity is nn.ReLU)
+                        and nonlinearity is nn.ReLU and layers[1] == layers[2])
         self._dims = list(layers)
+        # the fused edge-MLP kernels take at most EDGE_MLP_MAX_IN input features; a wider input runs layer by layer
+        self._fused = self._hip_ok and layers[0] <= EDGE_MLP_MAX_IN
 
     def hip_weights(self):
         if not self._hip_ok:
@@ -306,7 +309,7 @@ class DenseNet(nn.Module):
         if _wants_grad(self, x):
             return self._forward_grad(x)
         _no_training(self)
-        if not self._hip_ok:
+        if not self._fused or x.shape[0] == 0:      # (no rows: the fused kernels need an attribute pointer)
             with torch.no_grad():
                 return self._layerwise(ops.f32(x))
         w = self.hip_weights()
@@ -362,7 +365,7 @@ class NNConv_old(nn.Module):
             raise NotImplementedError(f"aggr={self.aggr!r}: the HIP path implements 'add', 'mean' and 'max'")
         with torch.no_grad():
             graph = ops.coo_to_csr(edge_index, x.shape[0])
-            if getattr(self.net, "_hip_ok", False):
+            if getattr(self.net, "_fused", False) and pseudo.shape[0] > 0:
                 dims = self.net._dims
                 w_e = ops.edge_mlp(self.net.hip_weights(), dims[0], dims[1], dims[3], graph, edge_attr=pseudo)
             else:       # any other edge network: evaluated in COO order, rows then put in the conv's edge order

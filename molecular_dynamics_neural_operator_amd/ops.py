@@ -123,6 +123,8 @@ def nnconv(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root: Optional[t
     y = out if out is not None else torch.empty((R, cout), dtype=torch.float32, device=x.device)
     root_c = f32(root) if root is not None else None
     bias_c = f32(bias) if bias is not None else None
+    if w_e.shape[0] == 0:       # no edges: every row is x.root + bias and W_e is never read, but must not be null
+        w_e = torch.empty((1, cin * cout), dtype=torch.float32, device=x.device)
     check(lib.mdno_nnconv_fwd(ptr(x), ptr(graph.row_ptr), ptr(graph.src), R, ptr(w_e), ptr(root_c), ptr(bias_c),
                               cin, cout, AGGR[aggr], int(relu), ptr(y), stream_ptr(x.device)), "mdno_nnconv_fwd")
     return y
@@ -366,6 +368,8 @@ def linear(a: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], relu: bo
     rows, k = a.shape
     n = w.shape[0]
     c = torch.empty((rows, n), dtype=torch.float32, device=a.device)
+    if rows == 0:               # (an edge network over a graph without edges)
+        return c
     bb = f32(b) if b is not None else None
     if gemm_mode == "split_f16" and k % 32 == 0 and n % 128 == 0 and rows > 0:
         ws = _ws(lib.mdno_linear_split_f16_workspace_bytes(rows, n, k), a.device)
@@ -391,6 +395,8 @@ def gemm_atb(a: torch.Tensor, b: torch.Tensor, gemm_mode: str = "f32") -> torch.
     rows, n1 = a.shape
     n2 = b.shape[1]
     c = torch.empty((n1, n2), dtype=torch.float32, device=a.device)
+    if rows == 0:               # an empty sum
+        return c.zero_()
     if gemm_mode == "split_f16" and lib.mdno_gemm_atb_split_f16_supported(rows, n1, n2):
         ws = _ws(lib.mdno_gemm_atb_split_f16_workspace_bytes(rows, n1, n2), a.device)
         check(lib.mdno_gemm_atb_split_f16(ptr(a), ptr(b), rows, n1, n2, ptr(c), 0, ptr(ws), ws.numel(), stream_ptr(a.device)),
@@ -408,6 +414,8 @@ def colsum(a: torch.Tensor) -> torch.Tensor:
     a = f32(a)
     rows, n = a.shape
     out = torch.empty(n, dtype=torch.float32, device=a.device)
+    if rows == 0:               # an empty sum
+        return out.zero_()
     ws = _ws(lib.mdno_reduce_workspace_bytes(n, 1), a.device)
     check(lib.mdno_colsum(ptr(a), rows, n, ptr(out), 0, ptr(ws), ws.numel(), stream_ptr(a.device)), "mdno_colsum")
     return out
@@ -915,8 +923,14 @@ def nnconv_bwd(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root: Option
     e = graph.edge_count()
     need_x, need_w, need_root, need_bias = need
     dx = d_we = d_root = d_bias = None
-    by_src = source_sorted(graph, R) if need_x else None
-    if not generic and cin == 64 and cout == 64 and aggr in ("add", "mean") and e > 0:
+    by_src = source_sorted(graph, R) if need_x and e > 0 else None
+    if e == 0:                  # no messages: dx = g . root^T, and W_e (no edge rows) gets a zero gradient
+        if need_x:
+            dx = linear(g, root, None) if root is not None else torch.zeros((R, cin), dtype=torch.float32,
+                                                                            device=x.device)
+        if need_w:
+            d_we = torch.zeros_like(w_e)
+    elif not generic and cin == 64 and cout == 64 and aggr in ("add", "mean"):
         gs = scale_rows(g, inv_degree(graph, aggr)) if aggr == "mean" else g
         if need_x:
             dx = nnconv_bwd_x(g, gs, by_src, w_e, root)

@@ -308,6 +308,16 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
     *reinterpret_cast<float4*>(out + id) = o;
 }
 
+// the same for a row length that is not a multiple of 4 (an edge-MLP of any ker_width): one element per thread
+__global__ __launch_bounds__(256) void relu_bwd_scalar_kernel(const float* __restrict__ g, const float* __restrict__ y,
+                                                              const float* __restrict__ row_scale, float* __restrict__ out,
+                                                              long long rows, int N) {
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= rows * N) return;
+    const float sc = row_scale ? row_scale[id / N] : 1.f;
+    out[id] = y[id] > 0.f ? g[id] * sc : 0.f;
+}
+
 // both at once: gz = g * (y > 0) and gs = gz * scale[row] — what the conv backward needs of one application
 // (d root, d bias read gz; the input and edge-weight gradients read gs = gz / max(deg,1)); same arithmetic as two calls
 __global__ __launch_bounds__(256) void relu_bwd2_kernel(const float* __restrict__ g, const float* __restrict__ y,
@@ -658,7 +668,13 @@ extern "C" int mdno_colsum(const float* a, int64_t rows, int n, float* out, int 
 
 extern "C" int mdno_relu_bwd(const float* g, const float* y, const float* row_scale, int64_t rows, int n, float* out,
                              void* stream) {
-    MDNO_REQUIRE(g && y && out && rows > 0 && n > 0 && n % 4 == 0, MDNO_EINVAL, "mdno_relu_bwd: bad arguments (n % 4)");
+    MDNO_REQUIRE(g && y && out && rows > 0 && n > 0, MDNO_EINVAL, "mdno_relu_bwd: bad arguments");
+    if (n % 4 || ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+        const long long count = rows * n;
+        hipLaunchKernelGGL(relu_bwd_scalar_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), g, y, row_scale, out, (long long)rows, n);
+        return check_launch("mdno_relu_bwd");
+    }
     const long long quads = rows * n / 4;
     hipLaunchKernelGGL(relu_bwd_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), g, y, row_scale, out, (long long)rows, n);

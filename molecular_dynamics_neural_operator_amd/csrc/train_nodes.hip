@@ -412,6 +412,7 @@ extern "C" int mdno_node_prologue_bwd(const mdno_kernelnn_params* p, const float
     else if (p->embedding_dim <= 8) hipLaunchKernelGGL(node_prologue_bwd_kernel<8>, dim3(blocks), dim3(ROWS), 0, s, a);
     else hipLaunchKernelGGL(node_prologue_bwd_kernel<MAX_EMB>, dim3(blocks), dim3(ROWS), 0, s, a);
     auto reduce = [&](int off, int count, float* out) {
+        if (count <= 0) return;      // (embedding_dim 0: no embedding gradient)
         hipLaunchKernelGGL(reduce_blocks_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float*)part + off,
                            blocks, tot, count, out);
     };

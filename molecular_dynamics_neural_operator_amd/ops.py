@@ -153,6 +153,7 @@ class ParamPack:
     def __init__(self, state_dict, depth: int, device, gemm_mode: str = "split_bf16",
                  conv_mode: str = "materialized"):
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        self._check_dims(sd)
         self.tensors = {}
         p = KernelNNParams()
         for field, key in self.KEYS.items():
@@ -165,6 +166,8 @@ class ParamPack:
                 raise MdnoError(f"state_dict lacks {key!r}")
             t = sd[key].detach().to(device=device, dtype=torch.float32).contiguous()
             self.tensors[field] = t
+            if t.numel() == 0:          # embedding_dim 0: an empty table has no storage; the kernels never read it
+                t = self.tensors.setdefault("_empty", torch.zeros(4, dtype=torch.float32, device=device))
             setattr(p, field, t.data_ptr())
         # the reference shares ONE edge-MLP between conv1 and conv2 (graph_kernel.py:271-273):
         # tied storage or equal values -> evaluate once
@@ -197,6 +200,21 @@ class ParamPack:
             raise MdnoError("edge-MLP output size != width**2")
         self.struct = p
         self.device = torch.device(device)
+
+    @staticmethod
+    def _check_dims(sd) -> None:
+        """The limits of the kernels (csrc/node_ops.hip, csrc/edge_mlp.hip), checked on the host before anything is
+        copied to the device."""
+        if "emb.weight" in sd and "fc1.weight" in sd:
+            emb = sd["emb.weight"].shape[1]
+            if emb > 16:
+                raise MdnoError(f"embedding_dim={emb} (0..16)")
+            if sd["fc1.weight"].shape[1] != emb + 3:
+                raise MdnoError(f"in_width={sd['fc1.weight'].shape[1]} must equal embedding_dim + 3 = {emb + 3} "
+                                "(graph_kernel.py:296)")
+        w0 = sd.get("conv1.net.layers.0.weight")
+        if w0 is not None and not 1 <= w0.shape[1] <= 8:
+            raise MdnoError(f"ker_in={w0.shape[1]} (1..8)")
 
     @property
     def ref(self):
@@ -686,10 +704,26 @@ def colsum_bf16(a: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _check_chain(what: str, x_layers: torch.Tensor, layers: int, w_e: torch.Tensor, *params) -> None:
+    """The chain entries are 64x64 only and read every operand at that size: refuse any other shape before a launch
+    (a [R,1] stack or a [E,1] W_e would otherwise be read as [R,64] / [E,4096])."""
+    if layers < 3:
+        raise MdnoError(f"{what}: depth must be >= 1 (x_layers needs 2*depth+1 >= 3 layers)")
+    if x_layers.dim() != 3 or x_layers.shape[0] != layers or x_layers.shape[2] != 64:
+        raise MdnoError(f"{what}: x_layers {tuple(x_layers.shape)}, expected [{layers}, R, 64]")
+    if w_e.dim() != 2 or w_e.shape[1] != 4096:
+        raise MdnoError(f"{what}: w_e {tuple(w_e.shape)}, expected [E, 4096] (64x64 channels only)")
+    for t in params:
+        want = (64, 64) if t.dim() == 2 else (64,)
+        if tuple(t.shape) != want:
+            raise MdnoError(f"{what}: root/bias {tuple(t.shape)}, expected {want}")
+
+
 def nnconv_chain_fwd(x_layers: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root1, bias1, root2, bias2,
                      depth: int) -> None:
     """x_layers f32 [2*depth+1, R, 64]: [0] given, [a] = relu(conv(x[a-1])) written in place — the 2*depth conv
     applications of the block in one call (w_e fp32 or bf16 [E,4096])."""
+    _check_chain("nnconv_chain_fwd", x_layers, 2 * depth + 1, w_e, root1, root2, bias1, bias2)
     lib = _lib.load()
     R = x_layers.shape[1]
     args = (ptr(x_layers), ptr(graph.row_ptr), ptr(graph.src), R, ptr(w_e), ptr(f32(root1)), ptr(f32(bias1)),
@@ -703,6 +737,9 @@ def nnconv_chain_fwd(x_layers: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor,
 def nnconv_chain_bwd(g_out: torch.Tensor, x_layers: torch.Tensor, inv_deg: torch.Tensor, by_src: CSRGraph,
                      w_e: torch.Tensor, root1, root2, depth: int):
     """Backward through the 2*depth applications -> (gz [L,R,64], gs [L,R,64], g_in [R,64])."""
+    _check_chain("nnconv_chain_bwd", x_layers, 2 * depth + 1, w_e, root1, root2)
+    if tuple(g_out.shape) != tuple(x_layers.shape[1:]):
+        raise MdnoError(f"nnconv_chain_bwd: g_out {tuple(g_out.shape)} != {tuple(x_layers.shape[1:])}")
     lib = _lib.load()
     L, R = 2 * depth, x_layers.shape[1]
     dev = x_layers.device
@@ -780,11 +817,12 @@ def node_prologue_bwd(pack: ParamPack, frames: torch.Tensor, x_aminoacid: torch.
     has_lstm = "lstm_w_ih" in pack.tensors
     d_lstm = torch.empty(108, dtype=torch.float32, device=dev) if has_lstm else None
     d_emb = torch.empty((p.num_embeddings, p.embedding_dim), dtype=torch.float32, device=dev)
+    emb_out = d_emb if d_emb.numel() else torch.empty(1, dtype=torch.float32, device=dev)     # (embedding_dim 0)
     d_w = torch.empty((p.width, p.in_width), dtype=torch.float32, device=dev)
     d_b = torch.empty(p.width, dtype=torch.float32, device=dev)
     ws = _ws(lib.mdno_node_prologue_bwd_workspace_bytes(pack.ref, M * N), dev)
     check(lib.mdno_node_prologue_bwd(pack.ref, ptr(frames), M, W, N, ptr(aa), int(aa.numel() == M * N and M > 1),
-                                     ptr(f32(x0)), ptr(f32(g0)), ptr(d_lstm), ptr(d_emb), ptr(d_w), ptr(d_b), ptr(ws),
+                                     ptr(f32(x0)), ptr(f32(g0)), ptr(d_lstm), ptr(emb_out), ptr(d_w), ptr(d_b), ptr(ws),
                                      ws.numel(), stream_ptr(dev)), "mdno_node_prologue_bwd")
     out = {"emb.weight": d_emb, "fc1.weight": d_w, "fc1.bias": d_b}
     if has_lstm:

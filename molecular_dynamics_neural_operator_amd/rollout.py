@@ -47,6 +47,10 @@ class RolloutEngine:
                  max_steps: int = 1000, edge_cap: Optional[int] = None, device=None, use_graph: bool = True):
         self.lib = _lib.load()
         self.device = require_gpu(device if device not in (None, "cuda") else None)
+        fc2 = getattr(model, "fc2", None)
+        out_width = fc2.out_features if fc2 is not None else getattr(getattr(model, "struct", None), "out_width", 3)
+        if out_width != 3:
+            raise MdnoError(f"rollout: out_width={out_width}, the model output must be a frame [N,3] (graph_kernel.py:407-410)")
         self.model = model
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
         self.threshold = float(threshold)

@@ -242,12 +242,48 @@ class DeviceTrajectory:
         return out
 
 
+# Longest window the prologue backward keeps per atom (csrc/train_nodes.hip MAX_W), largest embedding it handles
+MAX_TRAIN_WINDOW = 16
+MAX_EMBEDDING_DIM = 16
+
+
+def check_trainable(model, window: int) -> None:
+    """Refuse, before any device work, a model or window the training kernels do not implement: the conv chain and
+    its backward are 64x64 only (csrc/train.hip), the prologue backward keeps at most 16 frames and 16 embedding
+    channels per atom (csrc/train_nodes.hip), the edge-MLP's first layer reads at most 8 attributes
+    (csrc/edge_mlp.hip), and bf16 training tiles k by 128."""
+    conv2 = getattr(model, "conv2", None)
+    if conv2 is not None and model.conv1.net is not conv2.net:
+        raise NotImplementedError("training assumes the reference's single shared edge-MLP (graph_kernel.py:271-273)")
+    if conv2 is None and model.depth % 2:
+        raise NotImplementedError("notebook-era variant: training needs an even depth")
+    width = model.fc1.out_features
+    if width != 64:
+        raise NotImplementedError(f"training needs width 64 (got {width}): the conv chain and its backward are 64x64 only")
+    if not 1 <= window <= MAX_TRAIN_WINDOW:
+        raise NotImplementedError(f"training window {window}: the prologue backward takes 1..{MAX_TRAIN_WINDOW} frames")
+    emb = model.emb.embedding_dim
+    if emb > MAX_EMBEDDING_DIM:
+        raise NotImplementedError(f"embedding_dim={emb}: training takes 0..{MAX_EMBEDDING_DIM}")
+    if model.fc1.in_features != emb + 3:
+        raise MdnoError(f"in_width={model.fc1.in_features} must equal embedding_dim + 3 = {emb + 3} (graph_kernel.py:296)")
+    w0, _, w1, _, _, _ = model.conv1.net.hip_weights()
+    if w0.shape[1] > 8:
+        raise NotImplementedError(f"ker_in={w0.shape[1]}: the edge-MLP reads 1..8 edge attributes")
+    precision = getattr(model, "train_precision", "fp32")
+    if precision not in ("fp32", "bf16"):
+        raise MdnoError(f"train_precision={precision!r} (fp32, bf16)")
+    if precision == "bf16" and (w1.shape[0] % 128 or w1.shape[1] % 32):
+        raise NotImplementedError("bf16 training needs width 64 and ker_width a multiple of 128")
+
+
 def train_forward(model, data) -> torch.Tensor:
     """Differentiable forward of `KernelNN` for one sample, a list of samples, or an already collated batch
     (`collate`, `DeviceTrajectory.batch`) -> [B*N, out].  Nothing here waits for the device: index errors
     (amino-acid id or node id out of range — IndexError in the reference) are left in `model`'s training
     status word and raised by `check_train_status(model)`, which `train_epoch` calls once per epoch."""
     batch = collate(data) if not isinstance(data, PairData) else data
+    check_trainable(model, batch.x_position.shape[0] if batch.x_position.dim() == 3 else 1)
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise MdnoError("training needs the model on the GPU (model.to('cuda')); no CPU fallback")
@@ -256,8 +292,6 @@ def train_forward(model, data) -> torch.Tensor:
         xp = xp.unsqueeze(0)
     W, R, _ = xp.shape
     aa = batch.x_aminoacid.to(dev)
-    if getattr(model, "conv2", None) is not None and model.conv1.net is not model.conv2.net:
-        raise NotImplementedError("training assumes the reference's single shared edge-MLP (graph_kernel.py:271-273)")
     # per-atom prologue (graph_kernel.py:279-298 with B=1 semantics per sample): HIP forward + backward.
     # The ParamPack holds device pointers to the parameters' CURRENT storage (fp32 contiguous parameters
     # are viewed, not copied), the tensors themselves are passed so that autograd routes their gradients.
@@ -273,11 +307,15 @@ def train_forward(model, data) -> torch.Tensor:
     depth = model.depth if conv2 is not None else model.depth // 2
     # the feature stack of the kernel-integral block [2*depth+1, R, 64]: the prologue writes layer 0 in place and the
     # block returns its last layer as a view — no copy on either side
-    X = torch.empty((2 * depth + 1, R, model.fc1.out_features), dtype=torch.float32, device=dev) \
-        if model.fc1.out_features == 64 else None
-    pack.prologue_out = X[0] if X is not None else None
+    X = torch.empty((2 * depth + 1, R, 64), dtype=torch.float32, device=dev)
+    pack.prologue_out = X[0]
     x0 = NodePrologue.apply(pack, xp.unsqueeze(1).contiguous(), aa, *[sd[k] for k in names])
     pack.prologue_out = None
+    if depth == 0:
+        # no conv application (graph_kernel.py:299-302 loop zero times): fc2 reads x0, and the edge-MLP, root and
+        # bias parameters take no part in the loss — their .grad stays None, as under torch autograd; the edge list
+        # is not read, as in the reference
+        return FcOut.apply(x0, model.fc2.weight, model.fc2.bias)
     ei = batch.edge_index.to(dev)
     graph = ops.coo_to_csr(ei, R, validate=False, status=status)
     # the same edges grouped by source, for the input-gradient kernel: built now, next to the forward's sort
@@ -286,14 +324,8 @@ def train_forward(model, data) -> torch.Tensor:
     graph.x_stack = X
     net = model.conv1.net
     w0, b0, w1, b1, w2, b2 = net.hip_weights()
-    if conv2 is None and model.depth % 2:
-        raise NotImplementedError("notebook-era variant: training needs an even depth")
     c2 = conv2 if conv2 is not None else model.conv1
     precision = getattr(model, "train_precision", "fp32")
-    if precision not in ("fp32", "bf16"):
-        raise MdnoError(f"train_precision={precision!r} (fp32, bf16)")
-    if precision == "bf16" and (model.fc1.out_features != 64 or w1.shape[0] % 128 or w1.shape[1] % 32):
-        raise NotImplementedError("bf16 training needs width 64 and ker_width a multiple of 128")
     x = KernelIntegralBlock.apply(x0, batch.edge_attr.to(dev), graph, depth,
                                   "bf16" if precision == "bf16" else getattr(model, "gemm_mode", "f32"),
                                   w0, b0, w1, b1, w2, b2,

@@ -184,7 +184,7 @@ def train_step(sd: StateDict, samples: Sequence[dict], depth: int, dtype=torch.f
     (the only batch size at which the reference's forward is well defined), the loss is the
     sum over samples of ||out_b - y_b|| / ||y_b||.  conv1.net and conv2.net are ONE module in the reference
     (:271-273): `sd`'s conv2.net.* entries are ignored and both key sets receive the shared gradient.
-    Returns (loss, out [B*N, out_width], {name: grad})."""
+    Returns (loss, out [B*N, out_width], {name: grad or None})."""
     shared = {k: v for k, v in sd.items() if not k.startswith("conv2.net.")}
     params = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in shared.items()}
     outs, ys = [], []
@@ -196,7 +196,9 @@ def train_step(sd: StateDict, samples: Sequence[dict], depth: int, dtype=torch.f
     b = len(samples)
     loss = lp_loss_rel(out.view(b, -1), y.view(b, -1), size_average=False)
     names = list(params)
-    grads = torch.autograd.grad(loss, [params[n] for n in names])
+    # (depth 0: no conv application, so the edge-MLP, root and bias take no part in the loss and their gradient is
+    # None, as a parameter's .grad stays under torch autograd)
+    grads = torch.autograd.grad(loss, [params[n] for n in names], allow_unused=True)
     g = dict(zip(names, grads))
     for k in list(g):
         if k.startswith("conv1.net."):

@@ -598,6 +598,41 @@ int mdno_scale_rows(const float* a, const float* scale, int64_t rows, int n, flo
 int mdno_relu_mask_bwd(const float* g, const float* y, int64_t count, float* out, void* stream);
 int mdno_scatter_rows(const float* in, const int32_t* perm, int64_t rows, int width, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scoring a rollout against the true trajectory (csrc/forecast.hip) — what the reference does on the host after every
+ * epoch: the forecast's contact map beside the real one (make_propagation_movie / get_contact_map,
+ * graph_kernel.py:416-443), the per-step MSE of the notebook's propogate (bba_analysis.ipynb:351) and the structural
+ * distance its plots are coloured by (dataset.py:118).
+ *   frames  f32 [S, M, N, 3] (a rollout's produced frames, time-major)
+ *   truth   f32 [S, N, 3] shared by the members (truth_per_member = 0) or [S, M, N, 3] (truth_per_member != 0)
+ * per (step s, member m):
+ *   mse     f64 [S, M]     mean over the 3N coordinates of (frame - truth)^2, differences and sum in fp64
+ *   rmsd    f64 [S, M]     RMSD after the optimal rigid superposition (centroids removed, proper rotations only: a mirror
+ *                          image does not score 0), accumulated in fp64, rmsd^2 clamped at 0
+ *   counts  i64 [S, M, 3]  {contacts of the forecast, of the truth, of both}: ordered pairs (i, j), diagonal included,
+ *                          with sqrt(dx^2+dy^2+dz^2) < cutoff exactly as mdno_radius_graph_csr tests it — the
+ *                          non-zeros of the dense maps get_contact_map builds; a NaN / Inf coordinate is in no contact
+ *   first_nonfinite i32 [M]  the first step whose FORECAST frame holds a NaN or Inf, -1 for none; that (s, m) has
+ *                          mse = rmsd = NaN and no other entry is affected
+ * No atomics: results are bitwise reproducible and, up to 2,048 atoms (both frames of an (s, m) in the LDS of one
+ * workgroup), independent of the S and M of the call.  Larger frames (form AUTO) or form TILED split an (s, m) over
+ * several workgroups and add their partial results in a fixed order: the same counts, mse / rmsd to fp64 rounding.
+ * form LDS above 2,048 atoms: MDNO_EUNSUPPORTED.  S * M == 0 or N == 0: nothing is scored, first_nonfinite = -1.
+ * A negative size, a negative or non-finite cutoff or a null pointer to a non-empty array: MDNO_EINVAL before any
+ * device work.  Workspace: mdno_forecast_score_workspace_bytes(S, M, N, form).  Asynchronous on `stream`.
+ *
+ * mdno_contact_maps: maps u8 [F, N, N] (16-B aligned) of frames f32 [F, N, 3], maps[f][i][j] = 1 iff the pair is a
+ * contact — the matrix get_contact_map (graph_kernel.py:416-424) scatters construct_pairdata's edge list into.
+ * ---------------------------------------------------------------------------------------- */
+#define MDNO_FORECAST_AUTO  0
+#define MDNO_FORECAST_LDS   1
+#define MDNO_FORECAST_TILED 2
+size_t mdno_forecast_score_workspace_bytes(int S, int M, int N, int form);
+int mdno_forecast_score(const float* frames, const float* truth, int truth_per_member, int S, int M, int N,
+                        double cutoff, double* mse, double* rmsd, int64_t* counts, int32_t* first_nonfinite,
+                        int form, void* workspace, size_t workspace_bytes, void* stream);
+int mdno_contact_maps(const float* frames, int64_t F, int N, double cutoff, uint8_t* maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

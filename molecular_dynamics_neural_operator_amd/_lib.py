@@ -142,6 +142,9 @@ SIGNATURES = {
     "mdno_scale_rows": (_I, [_P, _P, _L, _I, _P, _P]),
     "mdno_relu_mask_bwd": (_I, [_P, _P, _L, _P, _P]),
     "mdno_scatter_rows": (_I, [_P, _P, _L, _I, _P, _P]),
+    "mdno_forecast_score_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "mdno_forecast_score": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "mdno_contact_maps": (_I, [_P, _L, _I, _D, _P, _P]),
 }
 
 _lib = None

@@ -41,6 +41,38 @@ __global__ __launch_bounds__(256) static void reduce_slices_q4_kernel(const floa
     }
 }
 
+// Sums over a wave (xor butterfly) and over a workgroup of WAVES waves (wave sums added in wave order): a fixed
+// association whatever the grid, and every thread receives the same bits.  T: double, int, long long.
+template <class T>
+__device__ __forceinline__ T wave_reduce_add(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// K values at once; `slots` is LDS for WAVES * K values of T.  The call starts and ends with a barrier, so one
+// slot array serves consecutive calls.
+template <int WAVES, int K, class T>
+__device__ __forceinline__ void block_reduce_add(T (&v)[K], T* slots) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_reduce_add(v[k]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) slots[wave * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        T s = slots[k];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) s += slots[w * K + k];
+        v[k] = s;
+    }
+    __syncthreads();
+}
+
 inline void launch_reduce_slices(const float* part, int slices, long long count, float* out, int accumulate, hipStream_t s) {
     hipLaunchKernelGGL(reduce_slices_q4_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, slices, count, out,
                        accumulate);

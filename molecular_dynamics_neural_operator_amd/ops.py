@@ -985,3 +985,72 @@ def nnconv_bwd(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root: Option
     if need_bias:
         d_bias = colsum(g)
     return dx, d_we, d_root, d_bias
+
+
+# ------------------------------------------------------------------------------------------------
+# Scoring a rollout (include/mdno.h "Scoring a rollout", csrc/forecast.hip)
+FORECAST_FORMS = {"auto": 0, "lds": 1, "tiled": 2}
+
+
+def _device_frames(t, what: str, ranks) -> torch.Tensor:
+    """`t` as a contiguous f32 device tensor [..., N, 3] of one of the given ranks, or MdnoError (no device work)."""
+    if not torch.is_tensor(t):
+        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise MdnoError(f"{what} is a CPU tensor: scoring runs on the GPU only (no CPU fallback exists)")
+    if t.dim() not in ranks or t.shape[-1] != 3:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected [{'..., ' if len(ranks) > 1 else 'S, M, '}N, 3] "
+                        f"of rank {' or '.join(str(r) for r in ranks)}")
+    return f32(t)
+
+
+def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.0, form: str = "auto"):
+    """frames f32 [S,M,N,3] against truth [S,N,3] (shared by the members) or [S,M,N,3] ->
+    (mse f64 [S,M], rmsd f64 [S,M], counts i64 [S,M,3], first_nonfinite i32 [M]); mdno_forecast_score.  Asynchronous on
+    the current stream, nothing is read back.  `form`: "auto" (one workgroup per (s, m) up to 2,048 atoms, tiled above),
+    "lds" or "tiled" to force one (same counts; a test hook)."""
+    frames = _device_frames(frames, "frames", (4,))
+    truth = _device_frames(truth, "truth", (3, 4))
+    if truth.device != frames.device:
+        raise MdnoError(f"truth is on {truth.device}, frames on {frames.device}")
+    S, M, N, _ = frames.shape
+    want = (S, M, N, 3) if truth.dim() == 4 else (S, N, 3)
+    if tuple(truth.shape) != want:
+        raise MdnoError(f"truth shape {tuple(truth.shape)} does not match frames {tuple(frames.shape)}: expected "
+                        f"{(S, N, 3)} or {(S, M, N, 3)}")
+    if form not in FORECAST_FORMS:
+        raise MdnoError(f"form {form!r}: expected one of {sorted(FORECAST_FORMS)}")
+    lib = _lib.load()
+    dev = frames.device
+    scored = S * M > 0 and N > 0
+    # (an (s, m) without atoms has no mean: NaN, and no contacts)
+    mse = torch.empty((S, M), dtype=torch.float64, device=dev) if scored else \
+        torch.full((S, M), float("nan"), dtype=torch.float64, device=dev)
+    rmsd = torch.empty_like(mse) if scored else mse.clone()
+    counts = torch.empty((S, M, 3), dtype=torch.int64, device=dev) if scored else \
+        torch.zeros((S, M, 3), dtype=torch.int64, device=dev)
+    first = torch.empty(M, dtype=torch.int32, device=dev)
+    nbytes = lib.mdno_forecast_score_workspace_bytes(S, M, N, FORECAST_FORMS[form])
+    ws = _ws(nbytes, dev) if scored else None
+    check(lib.mdno_forecast_score(ptr(frames) if scored else None, ptr(truth) if scored else None, int(truth.dim() == 4),
+                                  S, M, N, float(cutoff), ptr(mse) if scored else None, ptr(rmsd) if scored else None,
+                                  ptr(counts) if scored else None, ptr(first) if M else None, FORECAST_FORMS[form],
+                                  ptr(ws), ws.numel() if scored else 0, stream_ptr(dev)), "mdno_forecast_score")
+    return mse, rmsd, counts, first
+
+
+def contact_maps(frames: torch.Tensor, cutoff: float = 8.0) -> torch.Tensor:
+    """frames f32 [..., N, 3] -> u8 [..., N, N], 1 where the pair is within `cutoff` (the radius graph's own test, self
+    pairs included): the dense map get_contact_map (graph_kernel.py:416-424) builds.  mdno_contact_maps."""
+    frames = _device_frames(frames, "frames", tuple(range(2, 9)))
+    lib = _lib.load()
+    N = frames.shape[-2]
+    lead = tuple(frames.shape[:-2])
+    F = 1
+    for d in lead:
+        F *= d
+    maps = torch.empty(lead + (N, N), dtype=torch.uint8, device=frames.device)
+    empty = F == 0 or N == 0
+    check(lib.mdno_contact_maps(None if empty else ptr(frames), F, N, float(cutoff), None if empty else ptr(maps),
+                                stream_ptr(frames.device)), "mdno_contact_maps")
+    return maps

@@ -315,6 +315,26 @@ class RolloutEngine:
         """Frames of steps first_step .. first_step + steps - 1: f32 [steps, M, N, 3] (a view of the trajectory buffer)."""
         return self.traj[self.W + first_step:self.W + first_step + steps]
 
+    def _score_range(self, first_step: int, steps: Optional[int]) -> Tuple[int, int]:
+        first_step = int(first_step)
+        steps = self.steps_done - first_step if steps is None else int(steps)
+        if first_step < 0 or steps < 0 or first_step + steps > self.steps_done:
+            raise MdnoError(f"score: steps {first_step} .. {first_step + steps - 1} are not all among the "
+                            f"{self.steps_done} produced")
+        return first_step, steps
+
+    def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
+              threshold: Optional[float] = None):
+        """Score the produced frames of steps first_step .. first_step + steps - 1 (default: all) against
+        truth f32 [steps, N, 3] (every member against the same frames) or [steps, M, N, 3] -> `forecast.ForecastScore`.
+        The frames are read where they are (a view of the trajectory buffer, untouched); the scoring kernels run on
+        the current stream after the engine's enqueued steps, without waiting on the host.  `threshold`: the contact
+        cutoff, the engine's own by default."""
+        from .forecast import score_forecast
+        first_step, steps = self._score_range(first_step, steps)
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return score_forecast(self.produced(first_step, steps), truth, self.threshold if threshold is None else threshold)
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -438,6 +458,17 @@ class GroupedRolloutEngine:
         """Frames of steps first_step .. first_step + steps - 1 of every group, members in order: [steps, M, N, 3] (only
         these frames are copied — `traj` concatenates the groups' whole buffers)."""
         return torch.cat([e.produced(first_step, steps) for e in self.engines], dim=1)
+
+    def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
+              threshold: Optional[float] = None):
+        """`RolloutEngine.score` for every group on its own frames, members in order: the bits of
+        `score_forecast(self.frames(), truth)` without assembling the trajectory."""
+        from .forecast import ForecastScore
+        if torch.is_tensor(truth) and truth.dim() == 4 and truth.shape[1] != self.M:
+            raise MdnoError(f"truth shape {tuple(truth.shape)}: expected {self.M} members")
+        per_member = torch.is_tensor(truth) and truth.dim() == 4
+        return ForecastScore.cat([e.score(truth[:, lo:hi].contiguous() if per_member else truth, first_step, steps, threshold)
+                                  for e, (lo, hi) in zip(self.engines, self.bounds)])
 
     @property
     def edges_per_step(self) -> torch.Tensor:

@@ -217,6 +217,17 @@ class DeviceTrajectory:
     def __len__(self) -> int:
         return self.length
 
+    def truth_frames(self, start: int, steps: int) -> torch.Tensor:
+        """The `y` of samples start .. start + steps - 1 as ONE view [steps, N, 3] of the resident positions (no copy):
+        frame start + k + window + horizon - 1 for sample start + k.  At horizon 1 these are the frames a free run from
+        `dataset[start]` predicts step by step — what `graph_kernel.propogate` compares against — so they are the `truth`
+        of `RolloutEngine.score` / `forecast.score_forecast`."""
+        start, steps = int(start), int(steps)
+        if start < 0 or steps < 0 or start + steps > self.length:
+            raise IndexError(f"samples {start} .. {start + steps - 1} do not all lie in [0, {self.length})")
+        first = start + self.W + self.horizon - 1
+        return self.pos[first:first + steps]
+
     def batch(self, indices) -> PairData:
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.length:

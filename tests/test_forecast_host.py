@@ -1,0 +1,191 @@
+"""Host side of rollout scoring (forecast.py), no GPU: argument validation of the C entries and of the Python calls
+before any device work, the derived contact ratios, `DeviceTrajectory.truth_frames` indices, and `gather_scores`
+between two gloo ranks on CPU tensors."""
+import ctypes
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+from conftest import load_golden, write_golden_trajectory
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from molecular_dynamics_neural_operator_amd import _lib
+    if not _lib.LIB_PATH.exists():
+        import __graft_entry__ as g
+        g.build()
+    return _lib.load()
+
+
+def test_c_entries_refuse_bad_arguments_without_a_device(lib):
+    from molecular_dynamics_neural_operator_amd import _lib
+    buf = (ctypes.c_double * 64)()          # any non-null address: validation must return before touching it
+    p = ctypes.addressof(buf)
+
+    def score(frames=p, truth=p, S=2, M=2, N=4, cutoff=8.0, mse=p, rmsd=p, counts=p, first=p, form=0, ws=p):
+        return lib.mdno_forecast_score(frames, truth, 0, S, M, N, cutoff, mse, rmsd, counts, first, form, ws, 1 << 20, None)
+
+    for kw in (dict(frames=None), dict(truth=None), dict(mse=None), dict(rmsd=None), dict(counts=None), dict(first=None),
+               dict(ws=None)):
+        assert score(**kw) == _lib.EINVAL and b"null pointer" in lib.mdno_last_error(), kw
+    for kw in (dict(S=-1), dict(M=-1), dict(N=-1)):
+        assert score(**kw) == _lib.EINVAL and b"S=" in lib.mdno_last_error(), kw
+    for c in (-1.0, float("nan"), float("inf"), -float("inf")):
+        assert score(cutoff=c) == _lib.EINVAL and b"cutoff" in lib.mdno_last_error(), c
+        assert lib.mdno_contact_maps(p, 1, 4, c, p, None) == _lib.EINVAL and b"cutoff" in lib.mdno_last_error(), c
+    assert score(form=3) == _lib.EINVAL
+    assert score(N=4096, form=1) == _lib.EUNSUPPORTED                      # the LDS form holds 2,048 atoms
+    assert lib.mdno_contact_maps(None, 1, 4, 8.0, p, None) == _lib.EINVAL and b"null pointer" in lib.mdno_last_error()
+    assert lib.mdno_contact_maps(p, 1, 4, 8.0, None, None) == _lib.EINVAL
+    assert lib.mdno_contact_maps(p, -1, 4, 8.0, p, None) == _lib.EINVAL and lib.mdno_contact_maps(p, 1, -4, 8.0, p, None) == _lib.EINVAL
+    assert lib.mdno_contact_maps(p, 1, 4, 8.0, ((p + 15) & ~15) + 4, None) == _lib.EINVAL and b"aligned" in lib.mdno_last_error()
+    # nothing to do is a success without a device: no members, no maps
+    assert score(M=0, first=None, frames=None, truth=None, mse=None, rmsd=None, counts=None, ws=None) == _lib.OK
+    assert lib.mdno_contact_maps(None, 0, 4, 8.0, None, None) == _lib.OK and lib.mdno_contact_maps(None, 3, 0, 8.0, None, None) == _lib.OK
+    # workspace: one flag per (s, m) in the LDS form; the tiled form adds its partial sums and pair-tile counts
+    lds = lib.mdno_forecast_score_workspace_bytes(10, 3, 504, 0)
+    assert lds == 256 and lib.mdno_forecast_score_workspace_bytes(1000, 64, 504, 0) == 1000 * 64 * 4
+    T, T2, off = 9, 36, 0                                                    # 9,000 atoms: tiles of 1,024 and of 256
+    for nbytes in (2 * 4, 2 * T * 8 * 8, 2 * T * 10 * 8, 2 * T2 * T2 * 3 * 4):    # 256-B aligned carves, 2 = S * M
+        off = (off + 255) // 256 * 256 + nbytes
+    assert lib.mdno_forecast_score_workspace_bytes(1, 2, 9000, 0) == (off + 255) // 256 * 256
+    assert lib.mdno_forecast_score_workspace_bytes(1, 2, 9000, 0) == lib.mdno_forecast_score_workspace_bytes(1, 2, 9000, 2)
+    assert lib.mdno_forecast_score_workspace_bytes(10, 3, 504, 2) > lds
+    assert lib.mdno_forecast_score_workspace_bytes(0, 3, 504, 0) == 0 == lib.mdno_forecast_score_workspace_bytes(1, 1, 1, 7)
+
+
+def test_python_calls_refuse_cpu_tensors_and_bad_shapes():
+    from molecular_dynamics_neural_operator_amd import MdnoError
+    from molecular_dynamics_neural_operator_amd.forecast import contact_maps, score_forecast
+    f, t = torch.zeros(2, 3, 5, 3), torch.zeros(2, 5, 3)
+    with pytest.raises(MdnoError, match="CPU tensor"):
+        score_forecast(f, t)
+    with pytest.raises(MdnoError, match="CPU tensor"):
+        contact_maps(f)
+    with pytest.raises(MdnoError, match="torch tensor"):
+        score_forecast(f.numpy(), t)
+    meta = torch.device("meta")          # shape checks come before any device work: a meta tensor never reaches it
+
+    class OnDevice(torch.Tensor):         # a tensor that says it is on the GPU (there is none here)
+        is_cuda = True
+
+    def dev(*shape):
+        return torch.zeros(*shape, device=meta).as_subclass(OnDevice)
+
+    for fr, tr in ((dev(2, 3, 5), dev(2, 5, 3)), (dev(2, 3, 5, 4), dev(2, 5, 3)), (dev(2, 3, 5, 3), dev(5, 3)),
+                   (dev(2, 3, 5, 3), dev(3, 5, 3)), (dev(2, 3, 5, 3), dev(2, 6, 3)), (dev(2, 3, 5, 3), dev(2, 2, 5, 3)),
+                   (dev(2, 3, 5, 3), dev(2, 3, 5, 2))):
+        with pytest.raises(MdnoError, match="shape"):
+            score_forecast(fr, tr)
+    with pytest.raises(MdnoError, match="form"):
+        score_forecast(dev(2, 3, 5, 3), dev(2, 5, 3), form="fast")
+    with pytest.raises(MdnoError, match="shape"):
+        contact_maps(dev(5))
+    with pytest.raises(MdnoError, match="shape"):
+        contact_maps(dev(4, 5, 2))
+
+
+def test_contact_ratios_and_zero_denominators():
+    from molecular_dynamics_neural_operator_amd.forecast import ForecastScore
+    c = torch.tensor([[[10, 8, 6], [0, 5, 0]], [[7, 0, 0], [0, 0, 0]]], dtype=torch.int64)       # forecast, truth, both
+    s = ForecastScore(torch.zeros(2, 2, dtype=torch.float64), torch.zeros(2, 2, dtype=torch.float64), c,
+                      torch.tensor([-1, 1], dtype=torch.int32))
+    nan = float("nan")
+    for got, want in ((s.precision(), [[0.6, nan], [0.0, nan]]), (s.recall(), [[0.75, 0.0], [nan, nan]]),
+                      (s.native_fraction(), [[0.75, 0.0], [nan, nan]]), (s.jaccard(), [[0.5, 0.0], [0.0, nan]])):
+        assert got.dtype == torch.float64 and got.shape == (2, 2)
+        torch.testing.assert_close(got, torch.tensor(want, dtype=torch.float64), rtol=0, atol=0, equal_nan=True)
+    big = torch.tensor([[[2_500_000_000, 2_500_000_000, 2_499_999_999]]], dtype=torch.int64)     # N = 50,000: above 2^31
+    sb = ForecastScore(s.mse[:1, :1], s.rmsd[:1, :1], big, s.first_nonfinite[:1])
+    assert float(sb.precision()) == 2_499_999_999 / 2_500_000_000
+    two = ForecastScore.cat([s, sb.__class__(s.mse[:, :1], s.rmsd[:, :1], c[:, :1], s.first_nonfinite[:1])])
+    assert two.mse.shape == (2, 3) and two.contacts.shape == (2, 3, 3) and two.first_nonfinite.tolist() == [-1, 1, -1]
+    assert torch.equal(s.cpu().contacts, c)
+
+
+@pytest.mark.parametrize("window,horizon", [(1, 1), (3, 1), (2, 2)])
+def test_truth_frames_are_the_samples_targets(tmp_path, window, horizon):
+    from molecular_dynamics_neural_operator_amd.dataset import ContactMapDataset
+    from molecular_dynamics_neural_operator_amd.training import DeviceTrajectory
+    z = load_golden("rollout_20.npz")
+    path = tmp_path / "traj.npz"
+    write_golden_trajectory(path, z)
+    dset = ContactMapDataset(str(path), window_size=window, horizon=horizon)
+    traj = DeviceTrajectory.__new__(DeviceTrajectory)      # the index rule alone: the constructor needs a GPU to upload to
+    traj.W, traj.horizon, traj.length = window, horizon, len(dset)
+    traj.pos = torch.from_numpy(np.ascontiguousarray(dset.edge_attrs, dtype=np.float32))
+    for start, steps in ((0, len(dset)), (0, 1), (2, 5), (len(dset) - 1, 1), (len(dset), 0), (3, 0)):
+        got = traj.truth_frames(start, steps)
+        assert got.shape == (steps, traj.pos.shape[1], 3)
+        assert steps == 0 or got.data_ptr() == traj.pos[start + window + horizon - 1].data_ptr()      # a view, no copy
+        for k in range(steps):
+            assert torch.equal(got[k], dset[start + k].y)
+    for start, steps in ((-1, 2), (0, len(dset) + 1), (len(dset), 1), (2, -1)):
+        with pytest.raises(IndexError):
+            traj.truth_frames(start, steps)
+
+
+def test_gather_scores_without_a_process_group_returns_its_input():
+    from molecular_dynamics_neural_operator_amd.forecast import ForecastScore, gather_scores
+    s = ForecastScore(torch.zeros(2, 3, dtype=torch.float64), torch.zeros(2, 3, dtype=torch.float64),
+                      torch.zeros(2, 3, 3, dtype=torch.int64), torch.full((3,), -1, dtype=torch.int32))
+    assert gather_scores(s, 3) is s
+
+
+def _member_score(ids, S):
+    """The score of members `ids`, every value a function of (step, member) alone."""
+    from molecular_dynamics_neural_operator_amd.forecast import ForecastScore
+    m = torch.tensor(ids, dtype=torch.float64).view(1, -1)
+    s = torch.arange(S, dtype=torch.float64).view(-1, 1)
+    mse = 1e-3 * (s + 1) + m * 0.1 + 2.0 ** -40              # bits that an f32 round trip would lose
+    mse[:1] = float("nan")
+    rmsd = torch.sqrt(s + m + 0.5)
+    contacts = torch.stack([(s * 7 + m).long() + 2 ** 33, (s * 5 + m).long(), (s * 3 + m).long()], dim=-1)
+    first = torch.tensor([(-1 if i % 2 else i) for i in ids], dtype=torch.int32)
+    return ForecastScore(mse, rmsd, contacts, first)
+
+
+def _free_port():
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
+
+
+def _gather_worker(rank, world, port, total, S, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from molecular_dynamics_neural_operator_amd.forecast import gather_scores
+        from molecular_dynamics_neural_operator_amd.rollout import shard_members
+        full = gather_scores(_member_score(shard_members(total, rank, world), S), total)
+        want = _member_score(list(range(total)), S)
+        ok = all(a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int64) if a.is_floating_point() else a,
+                                                                           b.view(torch.int64) if b.is_floating_point() else b)
+                 for a, b in ((full.mse, want.mse), (full.rmsd, want.rmsd), (full.contacts, want.contacts),
+                              (full.first_nonfinite, want.first_nonfinite)))
+        q.put((rank, bool(ok)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("total,S", [(5, 4), (6, 3), (1, 2), (5, 0)])
+def test_gather_scores_over_two_gloo_ranks(total, S):
+    """Member m lives on rank m % 2 (shard_members); 5 members = 3 + 2 (uneven), 1 member = one empty rank.  Every
+    rank gets every member's values back bit for bit (NaNs, counts above 2^32 and the -1 markers included)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, total, S, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=120) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert res == [(0, True), (1, True)]

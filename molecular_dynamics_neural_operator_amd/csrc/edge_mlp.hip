@@ -95,12 +95,8 @@ struct GemmArgs {
     int tiled_out;        // 1: C written k-tiled [rows/128][N/32][128][32] (what csrc/moment.hip K1 streams)
 };
 
-// One K-tile of MFMA work for a wave: 2x2 tiles of 32x32 (mfma_f32.h)
+// One K-tile of MFMA work for a wave: 2x2 tiles of 32x32 (f32mma::mma_64x64, mfma_f32.h)
 static_assert(LDS_LD == f32mma::LD && BK == f32mma::BK, "tile helpers assume 36-float LDS rows");
-__device__ __forceinline__ void mma_tile(f32x16 (&acc)[2][2], const float* __restrict__ a_base,
-                                         const float* __restrict__ b_base) {
-    f32mma::mma_64x64(acc, a_base, b_base);
-}
 
 template <bool RELU>
 __global__ __launch_bounds__(256, 2) void gemm_tn_mfma_kernel(GemmArgs g) {
@@ -165,13 +161,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_mfma_kernel(GemmArgs g) {
     for (int kt = 0; kt < nk - 1; ++kt) {
         const int buf = kt & 1;
         MDNO_LOAD_TILE((size_t)(kt + 1) * BK)
-        mma_tile(acc, a_rd + buf * BM * LDS_LD, b_rd + buf * BN * LDS_LD);
+        f32mma::mma_64x64(acc, a_rd + buf * BM * LDS_LD, b_rd + buf * BN * LDS_LD);
         MDNO_STORE_TILE(buf ^ 1)
         __syncthreads();
     }
     {
         const int buf = (nk - 1) & 1;
-        mma_tile(acc, a_rd + buf * BM * LDS_LD, b_rd + buf * BN * LDS_LD);
+        f32mma::mma_64x64(acc, a_rd + buf * BM * LDS_LD, b_rd + buf * BN * LDS_LD);
     }
 #undef MDNO_LOAD_TILE
 #undef MDNO_STORE_TILE
@@ -233,6 +229,16 @@ __global__ __launch_bounds__(256) void gemm_tn_generic_kernel(GemmArgs g) {
     }
 }
 
+// what every product shares: operands, bias, N, K and the chunk's row window; the output (C, tiled_out) is set by name
+GemmArgs gemm_args(const float* A, const float* Bt, const float* bias, int N, int K, const int* num_edges,
+                   long long row_begin, int rows) {
+    GemmArgs g{};
+    g.A = A; g.Bt = Bt; g.bias = bias;
+    g.N = N; g.K = K;
+    g.num_edges = num_edges; g.row_begin = row_begin; g.rows = rows;
+    return g;
+}
+
 template <bool RELU>
 int launch_gemm(const GemmArgs& g, hipStream_t s) {
     TimedSection ts(RELU ? KID_GEMM_L1 : KID_GEMM_L2, s);
@@ -278,82 +284,54 @@ int* mdno::edge_mlp_activation_flags(void* workspace, int ker_width, int out_dim
     return edge_mlp_split_activation_flags(workspace, ker_width, out_dim, chunk_rows_for(edge_cap));
 }
 
-int mdno::edge_mlp(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                   const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                   long long edge_cap, int ker_in, int ker_width, int out_dim, int gemm_mode,
-                   const EdgeMlpWeights& w, float* w_e, void* workspace, size_t workspace_bytes, hipStream_t s,
-                   int phase) {
-    MDNO_REQUIRE(num_edges && w.w0 && w.b0 && w.w1 && w.b1 && w.w2 && w.b2 && w_e && workspace, MDNO_EINVAL,
-                 "edge_mlp: null pointer");
-    MDNO_REQUIRE((frames && src && dst) || edge_attr, MDNO_EINVAL, "edge_mlp: need (edge_pos, src, dst) or edge_attr");
-    MDNO_REQUIRE(edge_cap > 0 && ker_width > 0 && out_dim > 0, MDNO_EINVAL, "edge_mlp: bad sizes");
+int mdno::edge_mlp(const EdgeSource& es, int ker_in, int ker_width, int gemm_mode, const EdgeMlpWeights& w,
+                   const EdgeMlpOut& out, void* workspace, size_t workspace_bytes, hipStream_t s, int phase) {
+    const bool hidden = out.h_tiled != nullptr;
+    const int out_dim = hidden ? ker_width : out.out_dim;      // (the H target uses the workspace of a k x k last layer)
+    MDNO_REQUIRE(es.num_edges && w.w0 && w.b0 && w.w1 && w.b1 && workspace && (hidden ? !out.w_e : out.w_e && w.w2 && w.b2),
+                 MDNO_EINVAL, "edge_mlp: null pointer");
+    MDNO_REQUIRE((es.frames && es.src && es.dst) || es.edge_attr, MDNO_EINVAL,
+                 "edge_mlp: need (edge_pos, src, dst) or edge_attr");
+    MDNO_REQUIRE(es.edge_cap > 0 && ker_width > 0 && out_dim > 0, MDNO_EINVAL, "edge_mlp: bad sizes");
     MDNO_REQUIRE(ker_in > 0 && ker_in <= MAX_F, MDNO_EUNSUPPORTED, "edge_mlp: ker_in=%d (1..%d)", ker_in, MAX_F);
-    MDNO_REQUIRE(edge_attr || ker_in == 6, MDNO_EINVAL, "edge_mlp: position-derived attributes need ker_in == 6");
-    MDNO_REQUIRE(gemm_mode == MDNO_GEMM_SPLIT_BF16 || gemm_mode == MDNO_GEMM_F32 || gemm_mode == MDNO_GEMM_SPLIT_F16,
+    MDNO_REQUIRE(es.edge_attr || ker_in == 6, MDNO_EINVAL, "edge_mlp: position-derived attributes need ker_in == 6");
+    // W_e target only: on the H target an unknown mode has always run as split_bf16 (the factored conv does the same)
+    MDNO_REQUIRE(hidden || gemm_mode == MDNO_GEMM_SPLIT_BF16 || gemm_mode == MDNO_GEMM_F32 || gemm_mode == MDNO_GEMM_SPLIT_F16,
                  MDNO_EINVAL, "edge_mlp: gemm_mode=%d", gemm_mode);
-    const size_t need = mdno_edge_mlp_workspace_bytes(ker_width, out_dim, edge_cap, gemm_mode);
+    const size_t need = mdno_edge_mlp_workspace_bytes(ker_width, out_dim, es.edge_cap, gemm_mode);
     MDNO_REQUIRE(workspace_bytes >= need, MDNO_EWORKSPACE, "edge_mlp: workspace %zu < %zu", workspace_bytes, need);
-    const long long chunk = chunk_rows_for(edge_cap);
+    const long long chunk = chunk_rows_for(es.edge_cap);
     if (gemm_mode != MDNO_GEMM_F32 && edge_mlp_split_supported(ker_width, out_dim))
-        return edge_mlp_split(frames, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges, edge_cap,
-                              chunk, ker_in, ker_width, out_dim, w, w_e, workspace, s, phase,
-                              gemm_mode == MDNO_GEMM_SPLIT_F16 && ker_width % 32 == 0);
+        return edge_mlp_split(es, chunk, ker_in, ker_width, w, out, workspace, s, phase, gemm_mode == MDNO_GEMM_SPLIT_F16);
     if ((phase & WP_PHASE_MASK) == WP_PREPARE_ONLY) return MDNO_OK;   // the fp32 GEMMs read the weights as they are
+    // (only the MFMA kernel writes the k-tiled image)
+    MDNO_REQUIRE(!hidden || (ker_width % BN == 0 && (reinterpret_cast<uintptr_t>(w.w1) & 15) == 0), MDNO_EUNSUPPORTED,
+                 "edge_mlp: ker_width=%d must be a multiple of %d for the k-tiled H", ker_width, BN);
     Carver cv(workspace);
     float* h1 = cv.take<float>((size_t)chunk * ker_width);
     float* h2 = cv.take<float>((size_t)chunk * ker_width);
-    const float* pos_mode = edge_attr ? nullptr : frames;
-    for (long long e0 = 0; e0 < edge_cap; e0 += chunk) {
-        const int cnt = (int)((edge_cap - e0) < chunk ? (edge_cap - e0) : chunk);
+    for (long long e0 = 0; e0 < es.edge_cap; e0 += chunk) {
+        const int cnt = (int)((es.edge_cap - e0) < chunk ? (es.edge_cap - e0) : chunk);
         {
             TimedSection ts(KID_EDGE_L0, s);
-            hipLaunchKernelGGL(edge_l0_kernel, dim3((cnt + EB - 1) / EB), dim3(256), 0, s, pos_mode, frame, t_dev,
-                               rows_per_frame, src, dst, edge_attr, perm, num_edges, e0, cnt, ker_in, ker_width,
-                               w.w0, w.b0, h1);
+            hipLaunchKernelGGL(edge_l0_kernel, dim3((cnt + EB - 1) / EB), dim3(256), 0, s, es.positions(), es.frame, es.t_dev,
+                               es.rows_per_frame, es.src, es.dst, es.edge_attr, es.perm, es.num_edges, e0, cnt, ker_in,
+                               ker_width, w.w0, w.b0, h1);
         }
         MDNO_TRY(check_launch("edge_l0_kernel"));
-        GemmArgs g1{h1, w.w1, w.b1, h2, num_edges, e0, (int)chunk, ker_width, ker_width, 0};
+        GemmArgs g1 = gemm_args(h1, w.w1, w.b1, ker_width, ker_width, es.num_edges, e0, (int)chunk);
+        if (hidden) {      // chunk % 128 == 0: the k-tiled tile index continues across chunks
+            g1.C = out.h_tiled + (size_t)e0 * ker_width;
+            g1.tiled_out = 1;
+            MDNO_TRY(launch_gemm<true>(g1, s));
+            continue;
+        }
+        g1.C = h2;
         MDNO_TRY(launch_gemm<true>(g1, s));
         // the last layer writes straight into W_e; rows past *num_edges are masked by `valid`
-        GemmArgs g2{h2, w.w2, w.b2, w_e + (size_t)e0 * out_dim, num_edges, e0, (int)chunk, out_dim, ker_width, 0};
+        GemmArgs g2 = gemm_args(h2, w.w2, w.b2, out_dim, ker_width, es.num_edges, e0, (int)chunk);
+        g2.C = out.w_e + (size_t)e0 * out_dim;
         MDNO_TRY(launch_gemm<false>(g2, s));
-    }
-    return MDNO_OK;
-}
-
-int mdno::edge_mlp_hidden(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                          const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                          long long edge_cap, int ker_in, int ker_width, int gemm_mode, const EdgeMlpWeights& w,
-                          float* h_out, void* workspace, size_t workspace_bytes, hipStream_t s, int phase) {
-    MDNO_REQUIRE(num_edges && w.w0 && w.b0 && w.w1 && w.b1 && h_out && workspace, MDNO_EINVAL,
-                 "edge_mlp_hidden: null pointer");
-    MDNO_REQUIRE((frames && src && dst) || edge_attr, MDNO_EINVAL, "edge_mlp_hidden: need positions+CSR or edge_attr");
-    MDNO_REQUIRE(ker_in > 0 && ker_in <= MAX_F, MDNO_EUNSUPPORTED, "edge_mlp: ker_in=%d (1..%d)", ker_in, MAX_F);
-    MDNO_REQUIRE(edge_attr || ker_in == 6, MDNO_EINVAL, "edge_mlp: position-derived attributes need ker_in == 6");
-    const size_t need = mdno_edge_mlp_workspace_bytes(ker_width, ker_width, edge_cap, gemm_mode);
-    MDNO_REQUIRE(workspace_bytes >= need, MDNO_EWORKSPACE, "edge_mlp_hidden: workspace %zu < %zu", workspace_bytes, need);
-    const long long chunk = chunk_rows_for(edge_cap);
-    if (gemm_mode != MDNO_GEMM_F32 && edge_mlp_split_supported(ker_width, ker_width))
-        return edge_mlp_split_hidden(frames, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                     edge_cap, chunk, ker_in, ker_width, w, h_out, workspace, s, phase,
-                                     gemm_mode == MDNO_GEMM_SPLIT_F16);
-    if ((phase & WP_PHASE_MASK) == WP_PREPARE_ONLY) return MDNO_OK;
-    MDNO_REQUIRE(ker_width % BN == 0 && (reinterpret_cast<uintptr_t>(w.w1) & 15) == 0, MDNO_EUNSUPPORTED,
-                 "edge_mlp_hidden: ker_width=%d must be a multiple of %d", ker_width, BN);
-    Carver cv(workspace);
-    float* h1 = cv.take<float>((size_t)chunk * ker_width);
-    const float* pos_mode = edge_attr ? nullptr : frames;
-    for (long long e0 = 0; e0 < edge_cap; e0 += chunk) {
-        const int cnt = (int)((edge_cap - e0) < chunk ? (edge_cap - e0) : chunk);
-        {
-            TimedSection ts(KID_EDGE_L0, s);
-            hipLaunchKernelGGL(edge_l0_kernel, dim3((cnt + EB - 1) / EB), dim3(256), 0, s, pos_mode, frame, t_dev,
-                               rows_per_frame, src, dst, edge_attr, perm, num_edges, e0, cnt, ker_in, ker_width,
-                               w.w0, w.b0, h1);
-        }
-        MDNO_TRY(check_launch("edge_l0_kernel"));
-        GemmArgs g1{h1, w.w1, w.b1, h_out + (size_t)e0 * ker_width, num_edges, e0, (int)chunk, ker_width, ker_width, 1};
-        MDNO_TRY(launch_gemm<true>(g1, s));
     }
     return MDNO_OK;
 }
@@ -365,7 +343,7 @@ extern "C" int mdno_edge_mlp_fwd(const float* edge_pos, const int32_t* src, cons
                                  const float* w2, const float* b2, float* w_e, void* workspace,
                                  size_t workspace_bytes, void* stream) {
     EdgeMlpWeights w{w0, b0, w1, b1, w2, b2};
-    return mdno::edge_mlp(edge_pos, 0, nullptr, 0, src, dst, edge_attr, perm, num_edges, (long long)edge_cap, ker_in,
-                          ker_width, out_dim, gemm_mode, w, w_e, workspace, workspace_bytes,
+    const EdgeSource es{edge_pos, 0, nullptr, 0, src, dst, edge_attr, perm, num_edges, (long long)edge_cap};
+    return mdno::edge_mlp(es, ker_in, ker_width, gemm_mode, w, EdgeMlpOut::full(w_e, out_dim), workspace, workspace_bytes,
                           static_cast<hipStream_t>(stream));
 }

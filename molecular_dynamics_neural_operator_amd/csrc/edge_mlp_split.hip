@@ -58,22 +58,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-// flags[0]: a weight is not finite (set when the weight planes are built); flags[1]: an activation of the
-// current forward is out of fp16 range; flags[2], flags[3]: h1 / h2 of the current forward hold at least one
-// value >= F16_ACT_MIN (split_layout.h: below that the two-plane form has only an absolute error bound).
-// `need`: which of flags[2], flags[3] (bit 0, bit 1) the product's operands depend on.  Any failure sends
-// the chunk down the bf16 path.  flags[F16_FALLBACK_COUNT] counts the products (GEMM launches) that took it
-// (never reset by the library's forwards: a rollout plan zeroes it per run and reads it back, include/mdno.h).
-constexpr int F16_FALLBACK_COUNT = 8;
+// The flag words: F16FlagWord (kernels.h).  `need`: which of the "seen" words the product's operands depend on.
+// Any failure sends the chunk down the bf16 path.
+enum F16Need { F16_NEED_NONE = 0, F16_NEED_H1 = 1, F16_NEED_H2 = 2 };
 // grid of a bf16 FALLBACK launch (one that exits at once unless a flag is up): a launch that is not needed then costs a
 // kernel boundary, not the dispatch of a capacity-sized grid (thousands of workgroups); when it IS needed its workgroups
 // walk the tiles with this stride
 constexpr int kFallbackGemmGrid = 512, kFallbackL0RowTiles = 32;
 
 __device__ __forceinline__ bool f16_blocked(const int* __restrict__ flags, int need) {
-    bool b = (__builtin_nontemporal_load(flags) | __builtin_nontemporal_load(flags + 1)) != 0;
-    if (need & 1) b |= __builtin_nontemporal_load(flags + 2) == 0;
-    if (need & 2) b |= __builtin_nontemporal_load(flags + 3) == 0;
+    bool b = (__builtin_nontemporal_load(flags + F16_WEIGHT_RANGE) | __builtin_nontemporal_load(flags + F16_ACT_RANGE)) != 0;
+    if (need & F16_NEED_H1) b |= __builtin_nontemporal_load(flags + F16_H1_SEEN) == 0;
+    if (need & F16_NEED_H2) b |= __builtin_nontemporal_load(flags + F16_H2_SEEN) == 0;
     return b;
 }
 
@@ -179,7 +175,7 @@ __global__ __launch_bounds__(256) void split_planes_f16_kernel(const float* __re
 constexpr int MAX_F = 8;
 constexpr int L0_ROWS = 128, L0_UNITS = 128, L0_UNITS_SMALL = 32;
 
-// MODE 1: emit the two fp16 planes (and raise f16_flags[1] on a value out of fp16 range) instead of the
+// MODE 1: emit the two fp16 planes (and raise f16_flags[F16_ACT_RANGE] on a value out of fp16 range) instead of the
 // three bf16 planes; MODE 0 given f16_flags runs only when a flag is up (fallback); MODE 2: both images
 // (launches of a few rows, whose GEMMs pick their operand image themselves: gemm_split_f16_small_kernel).
 // (MODE 2 takes 32 hidden units per workgroup instead of 128: a launch of a few hundred rows is three row tiles, and
@@ -239,7 +235,7 @@ __global__ __launch_bounds__(256) void edge_l0_split_kernel(
     if (F16) {
 #pragma unroll
         for (int f = 0; f < MAX_F; ++f) operands_wild |= !(fabsf(attr[f]) < L0_OPERAND_BOUND);
-        if (operands_wild) atomicOr(f16_flags + 1, 1);
+        if (operands_wild) atomicOr(f16_flags + F16_ACT_RANGE, 1);
     }
     __syncthreads();
     if (!valid) return;
@@ -283,8 +279,8 @@ __global__ __launch_bounds__(256) void edge_l0_split_kernel(
                 *reinterpret_cast<uint4*>(hp + tiled_off(le, u0 + c, nkt, p)) = *reinterpret_cast<const uint4*>(o[p]);
         }
     }
-    if (F16 && bad) atomicOr(f16_flags + 1, 1);
-    if (F16 && seen) f16_flags[2] = 1;      // (the same value from whoever stores it: no atomic)
+    if (F16 && bad) atomicOr(f16_flags + F16_ACT_RANGE, 1);
+    if (F16 && seen) f16_flags[F16_H1_SEEN] = 1;      // (the same value from whoever stores it: no atomic)
 }
 
 // The bf16 image of a chunk for the FALLBACK of gemm_mode SPLIT_F16 (MODE 0's arithmetic): launched behind the fp16
@@ -349,30 +345,47 @@ __global__ __launch_bounds__(256) void edge_l0_split_fallback_kernel(
     }
 }
 
-// f16 = true: fp16 planes + range flag; f16 = false with flags: the bf16 fallback (runs if a flag is up)
-static int launch_edge_l0_split(const float* pos_mode, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                                const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                                long long e0, int cnt, int F, int k, const float* w0, const float* b0,
-                                unsigned char* hp, hipStream_t s, bool f16 = false, int* f16_flags = nullptr,
-                                int f16_need = 0, unsigned char* hp_f16 = nullptr) {
+// The edge-MLP workspace, one layout for both targets (carve_split): [h1 planes][h2 planes][W1 planes][W2 planes]
+// [W1 fp16 planes][flags][W2 fp16 planes][W1, W2 unscale][h1, h2 fp16 planes of a few-row launch]
+struct SplitWs {
+    unsigned char *h1p, *h2p, *w1p, *w2p, *w1h, *w2h;
+    unsigned char *h1h, *h2h;   // few rows (both_gemms_small): the fp16 images beside the bf16 ones in h1p, h2p
+    float *w1us, *w2us;      // per-row unscale factors of the fp16 weight images
+    int* f16_flags;
+    size_t total;
+};
+
+// Which image(s) of h1 a layer-0 launch writes, i.e. which kernel it is
+enum L0Image {
+    L0_BF16,            // three bf16 planes -> h1p
+    L0_F16,             // two fp16 planes -> h1p, raising the range / "seen" flags
+    L0_BOTH,            // few rows: bf16 planes -> h1p and fp16 planes -> h1h
+    L0_BF16_FALLBACK,   // behind the fp16 kernels: bf16 planes -> h1p, if a flag (or a missing `f16_need` word) says so
+};
+
+static int launch_edge_l0_split(L0Image image, const EdgeSource& es, long long e0, int cnt, int F, int k,
+                                const EdgeMlpWeights& w, const SplitWs& sw, hipStream_t s, int f16_need = F16_NEED_NONE) {
     const int row_tiles = (cnt + L0_ROWS - 1) / L0_ROWS;
-    if (!f16 && f16_flags != nullptr && hp_f16 == nullptr) {      // the fallback launch behind the fp16 kernels
+    if (image == L0_BF16_FALLBACK) {
         const dim3 fgrid(row_tiles < kFallbackL0RowTiles ? row_tiles : kFallbackL0RowTiles, k / L0_UNITS);
-        if (F == 6)
-            hipLaunchKernelGGL((edge_l0_split_fallback_kernel<6>), fgrid, dim3(256), 0, s, pos_mode, frame, t_dev, rows_per_frame,
-                               src, dst, edge_attr, perm, num_edges, e0, cnt, F, k, w0, b0, hp, (const int*)f16_flags, f16_need);
-        else
-            hipLaunchKernelGGL((edge_l0_split_fallback_kernel<0>), fgrid, dim3(256), 0, s, pos_mode, frame, t_dev, rows_per_frame,
-                               src, dst, edge_attr, perm, num_edges, e0, cnt, F, k, w0, b0, hp, (const int*)f16_flags, f16_need);
+#define MDNO_L0_FALLBACK(FT)                                                                                                \
+    hipLaunchKernelGGL((edge_l0_split_fallback_kernel<FT>), fgrid, dim3(256), 0, s, es.positions(), es.frame, es.t_dev,       \
+                       es.rows_per_frame, es.src, es.dst, es.edge_attr, es.perm, es.num_edges, e0, cnt, F, k, w.w0, w.b0,     \
+                       sw.h1p, (const int*)sw.f16_flags, f16_need)
+        if (F == 6) MDNO_L0_FALLBACK(6); else MDNO_L0_FALLBACK(0);
+#undef MDNO_L0_FALLBACK
         return check_launch("edge_l0_split_fallback_kernel");
     }
-    const dim3 grid(row_tiles, k / (hp_f16 ? L0_UNITS_SMALL : L0_UNITS));
-    // hp_f16 given: both images (bf16 planes -> hp, fp16 planes -> hp_f16)
-#define MDNO_L0(FT, MODE)                                                                                             \
-    hipLaunchKernelGGL((edge_l0_split_kernel<FT, MODE>), grid, dim3(256), 0, s, pos_mode, frame, t_dev, rows_per_frame, \
-                       src, dst, edge_attr, perm, num_edges, e0, cnt, F, k, w0, b0, hp, f16_flags, f16_need, hp_f16)
-    if (F == 6) { if (hp_f16) MDNO_L0(6, 2); else if (f16) MDNO_L0(6, 1); else MDNO_L0(6, 0); }
-    else        { if (hp_f16) MDNO_L0(0, 2); else if (f16) MDNO_L0(0, 1); else MDNO_L0(0, 0); }
+    TimedSection ts(KID_EDGE_L0, s);      // (the fallback launch above is part of the GEMM section it sits in)
+    const dim3 grid(row_tiles, k / (image == L0_BOTH ? L0_UNITS_SMALL : L0_UNITS));
+    int* const flags = image == L0_BF16 ? nullptr : sw.f16_flags;
+    unsigned char* const hp_f16 = image == L0_BOTH ? sw.h1h : nullptr;
+#define MDNO_L0(FT, MODE)                                                                                                   \
+    hipLaunchKernelGGL((edge_l0_split_kernel<FT, MODE>), grid, dim3(256), 0, s, es.positions(), es.frame, es.t_dev,           \
+                       es.rows_per_frame, es.src, es.dst, es.edge_attr, es.perm, es.num_edges, e0, cnt, F, k, w.w0, w.b0,     \
+                       sw.h1p, flags, f16_need, hp_f16)
+    if (F == 6) { if (image == L0_BOTH) MDNO_L0(6, 2); else if (image == L0_F16) MDNO_L0(6, 1); else MDNO_L0(6, 0); }
+    else        { if (image == L0_BOTH) MDNO_L0(0, 2); else if (image == L0_F16) MDNO_L0(0, 1); else MDNO_L0(0, 0); }
 #undef MDNO_L0
     return check_launch("edge_l0_split_kernel");
 }
@@ -382,19 +395,19 @@ struct SplitGemmArgs {
     const unsigned char* Ap;   // tiled planes of A  [rows/128][K/32][3][8 KiB]
     const unsigned char* Bp;   // tiled planes of Bt [N/128][K/32][3][8 KiB]
     const float* bias;         // [N]
-    float* C;                  // fp32 [rows][N] row-major            (OUT_PLANES = false)
-    unsigned char* Cp;         // tiled planes [rows/128][N/32][3][8 KiB], ReLU applied (OUT_PLANES = true)
+    float* C;                  // fp32 output (OUT_F32, OUT_F32_RELU: [rows][N] row-major; OUT_H_TILED: k-tiled)
+    unsigned char* Cp;         // tiled planes [rows/128][N/32][3][8 KiB], ReLU applied (OUT_PLANES, OUT_PLANES_F16)
     const int* num_edges;      // device count of valid rows (rows past it are neither computed nor stored) ...
     long long row_begin;       // ... relative to this first row; NULL: rows_valid below is used instead
     int rows, N, K;
-    int tiles_n, tiles_m;
+    int tiles_n, tiles_m;      // set by the launchers
     int rows_valid;
     int m_fastest;             // tile order: 0 = n fastest (neighbours share the A row-panel), 1 = m fastest (share B)
     const int* f16_flags = nullptr;   // SPLIT_F16: the fp16 kernel runs while no flag is up, the bf16 one (given
                                       // the flags) only when one is; NULL: unconditional
     int f16_need = 0;                 // which "seen" words the operands depend on (f16_blocked)
     const float* b_unscale = nullptr; // fp16 kernel: per-column factor undoing the weight rows' power-of-two scale
-    // gemm_split_f16_small_kernel only: the bf16 images of the same operands (and of the output, OUT 4).  Given
+    // gemm_split_f16_small_kernel only: the bf16 images of the same operands (and of the output, OUT_PLANES_F16).  Given
     // these the kernel multiplies them itself when a flag is up — no fallback launch behind it
     const unsigned char* Ap_b = nullptr;
     const unsigned char* Bp_b = nullptr;
@@ -403,6 +416,15 @@ struct SplitGemmArgs {
     // gradients of any magnitude, scaled row by row like the weights); [rows] floats, NULL = none
     const float* a_unscale = nullptr;
 };
+
+// What every product shares: operand images, bias, N, K and the row capacity.  The row window (num_edges + row_begin, or
+// rows_valid), the output (C / Cp) and the SPLIT_F16 fields are assigned by name; tiles_n, tiles_m belong to the launchers.
+static SplitGemmArgs split_gemm_args(const unsigned char* Ap, const unsigned char* Bp, const float* bias, int N, int K, int rows) {
+    SplitGemmArgs g{};
+    g.Ap = Ap; g.Bp = Bp; g.bias = bias;
+    g.rows = rows; g.N = N; g.K = K;
+    return g;
+}
 
 // One stage (k-step of 16) for a wave: (2x2 tiles) x 6 plane products = 24 MFMAs, 12 fragment reads.
 __device__ __forceinline__ void mma_split_stage(f32x16 (&acc)[2][2], const unsigned char* st, int a_rd, int b_rd) {
@@ -428,9 +450,14 @@ __device__ __forceinline__ void mma_split_stage(f32x16 (&acc)[2][2], const unsig
         }
 }
 
-// OUT: 0 = fp32 row-major (W_e), 1 = tiled bf16 planes after ReLU (next GEMM's operand),
-//      2 = fp32 k-tiled [rows/128][N/32][128][32] after ReLU (the hidden activation the factored conv streams)
-//      3 = fp32 row-major after ReLU (training: mdno_linear_split_fwd)
+// OUT (a SplitOut; the template parameters stay int): what the epilogue writes
+enum SplitOut {
+    OUT_F32 = 0,          // fp32 row-major (W_e)
+    OUT_PLANES = 1,       // tiled bf16 planes after ReLU (the next GEMM's operand)
+    OUT_H_TILED = 2,      // fp32 k-tiled [rows/128][N/32][128][32] after ReLU (the hidden activation the factored conv streams)
+    OUT_F32_RELU = 3,     // fp32 row-major after ReLU (training: mdno_linear_split_fwd)
+    OUT_PLANES_F16 = 4,   // two fp16 planes after ReLU (fp16 kernels: the next GEMM's operand; raises F16_ACT_RANGE on a value out of range)
+};
 // one TM x 128 tile of the product: tile `orig` of `nwg` in the XCD-aware order
 template <int TM, int OUT>
 __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, unsigned char* lds, long long valid, int nwg, int orig) {
@@ -535,9 +562,9 @@ __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, uns
                 const int m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (m < valid) {
                     const float v = acc[i][j][e] + bv;
-                    if (OUT == 2) {   // k-tiled fp32 image [m/128][n/32][128][32] (csrc/moment.hip K1)
+                    if (OUT == OUT_H_TILED) {   // k-tiled fp32 image [m/128][n/32][128][32] (csrc/moment.hip K1)
                         g.C[((size_t)(m >> 7) * (g.N >> 5) + (n >> 5)) * 4096 + (m & 127) * 32 + (n & 31)] = relu_f(v);
-                    } else if (OUT == 1) {
+                    } else if (OUT == OUT_PLANES) {
                         __bf16 ph, pm, pl;
                         split3(relu_f(v), ph, pm, pl);
                         const size_t o = tiled_off(m, n, g.N >> 4, 0);
@@ -545,7 +572,7 @@ __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, uns
                         *reinterpret_cast<__bf16*>(g.Cp + o + PLANE_BYTES) = pm;
                         *reinterpret_cast<__bf16*>(g.Cp + o + 2 * PLANE_BYTES) = pl;
                     } else {
-                        g.C[(size_t)m * g.N + n] = OUT == 3 ? relu_f(v) : v;
+                        g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
                     }
                 }
             }
@@ -645,8 +672,7 @@ constexpr int F16_TM = 256, F16_RING = 3;
 constexpr int F16_TILE_BYTES = 2 * 2 * PLANE_BYTES;       // one 128-row tile: two k-steps x two planes = 16 KiB
 constexpr int F16_STAGE_BYTES = 3 * F16_TILE_BYTES;       // A tile 0 | A tile 1 | B = 48 KiB
 
-// OUT: 2 = fp32 k-tiled after ReLU (the factored conv's H), 0 = fp32 row-major, 3 = fp32 row-major after ReLU,
-//      4 = two fp16 planes after ReLU (the next GEMM's operand; raises f16_flags[1] on a value out of range)
+// OUT: OUT_H_TILED, OUT_F32, OUT_F32_RELU or OUT_PLANES_F16
 // MI = 32-row tiles per wave: 2 -> 8 waves of 64x64 (162 VGPRs, two waves per SIMD).  The LDS pipe, not
 // the matrix pipe, is what this shape runs into (176 KiB of LDS traffic per 1,536 matrix-pipe cycles at
 // 128 B/clk); MI = 4 — 4 waves of 128x64, a third fewer fragment reads per MFMA, but 2 x 128 accumulator
@@ -805,9 +831,9 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
                     float v = (acc[i][j][e] + accx[i][j][e] * F16_LO_UNSCALE) * us;
                     if (ROW_SCALE) v *= ua[ROW_SCALE ? i : 0][e];
                     v += bv;
-                    if (OUT == 2) {
+                    if (OUT == OUT_H_TILED) {
                         g.C[((size_t)(m >> 7) * (g.N >> 5) + (n >> 5)) * 4096 + (m & 127) * 32 + (n & 31)] = relu_f(v);
-                    } else if (OUT == 4) {
+                    } else if (OUT == OUT_PLANES_F16) {
                         const float rv = relu_f(v);
                         bad |= !(rv < F16_MAX);
                         seen |= rv >= F16_ACT_MIN;
@@ -817,14 +843,14 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
                         *reinterpret_cast<_Float16*>(g.Cp + o) = ph;
                         *reinterpret_cast<_Float16*>(g.Cp + o + PLANE_BYTES) = pl;
                     } else {
-                        g.C[(size_t)m * g.N + n] = OUT == 3 ? relu_f(v) : v;
+                        g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
                     }
                 }
             }
         }
     }
-    if (OUT == 4 && bad) atomicOr(const_cast<int*>(g.f16_flags) + 1, 1);
-    if (OUT == 4 && seen) const_cast<int*>(g.f16_flags)[3] = 1;
+    if (OUT == OUT_PLANES_F16 && bad) atomicOr(const_cast<int*>(g.f16_flags) + F16_ACT_RANGE, 1);
+    if (OUT == OUT_PLANES_F16 && seen) const_cast<int*>(g.f16_flags)[F16_H2_SEEN] = 1;
 }
 
 // ---- the same product for a FEW rows (a 28-atom chain has 330 edges): (32 WM) x 64 tiles, WM x 2 waves of 32 x 32.
@@ -980,7 +1006,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
         ua[e] = (g.a_unscale && !blocked) ? g.a_unscale[bm + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h] : 1.f;
     bool bad = false, seen = false;
     const int n = bn + wn * 32 + l31;
-    if (OUT == 4) {
+    if (OUT == OUT_PLANES_F16) {
         // A lane holds ONE column of 16 rows: stored from the accumulators, the up to five plane images would take 80
         // two-byte stores per lane.  Instead the wave turns its 32 x 32 tile through a private LDS patch (the ring is
         // idle once everybody has left the K loop) and each lane converts and stores 8 adjacent columns of a row:
@@ -1018,8 +1044,8 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
                 }
             }
         }
-        if (bad) atomicOr(const_cast<int*>(g.f16_flags) + 1, 1);
-        if (seen) const_cast<int*>(g.f16_flags)[3] = 1;
+        if (bad) atomicOr(const_cast<int*>(g.f16_flags) + F16_ACT_RANGE, 1);
+        if (seen) const_cast<int*>(g.f16_flags)[F16_H2_SEEN] = 1;
         return;
     }
 #pragma unroll
@@ -1027,7 +1053,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
         const int m = bm + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
         if (m < valid) {
             const float v = (acc[e] + accx[e] * F16_LO_UNSCALE) * us * ua[e] + bv;
-            g.C[(size_t)m * g.N + n] = OUT == 3 ? relu_f(v) : v;
+            g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
         }
     }
 }
@@ -1061,7 +1087,7 @@ int launch_split_f16_gemm(SplitGemmArgs g, hipStream_t s) {
     MDNO_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&gemm_split_f16_kernel<OUT, MI>), lds_bytes, lds_raised));
     MDNO_REQUIRE(g.K % 32 == 0 && g.N % TN == 0 && g.rows % F16_TM == 0, MDNO_EUNSUPPORTED,
                  "split-f16 GEMM: rows=%d N=%d K=%d", g.rows, g.N, g.K);
-    if constexpr (OUT != 2) {      // (the factored conv's k-tiled H is written by the 256-row kernel only)
+    if constexpr (OUT != OUT_H_TILED) {      // (the factored conv's k-tiled H is written by the 256-row kernel only)
         if ((g.N / TN) * (g.rows / F16_TM) <= F16S_MAX_BIG_TILES) return launch_split_f16_gemm_small<OUT>(g, s);
     }
     g.tiles_n = g.N / TN;
@@ -1160,9 +1186,11 @@ int split_linear(const float* a, const float* w, const float* bias, long long ro
     unsigned char* wp = reinterpret_cast<unsigned char*>(cv.take<char>(split_planes_bytes(N, K)));
     MDNO_TRY(split_planes(a, (int)rows, K, ap, s));
     MDNO_TRY(split_planes(w, N, K, wp, s));
-    SplitGemmArgs g{ap, wp, bias, c, nullptr, nullptr, 0, (int)((rows + 255) / 256 * 256), N, K, 0, 0, (int)rows, 0};
-    if (relu) return N >= 2048 ? launch_split_gemm_tm<256, 3>(g, s) : launch_split_gemm_tm<128, 3>(g, s);
-    return N >= 2048 ? launch_split_gemm_tm<256, 0>(g, s) : launch_split_gemm_tm<128, 0>(g, s);
+    SplitGemmArgs g = split_gemm_args(ap, wp, bias, N, K, (int)((rows + 255) / 256 * 256));
+    g.C = c;
+    g.rows_valid = (int)rows;
+    if (relu) return N >= 2048 ? launch_split_gemm_tm<256, OUT_F32_RELU>(g, s) : launch_split_gemm_tm<128, OUT_F32_RELU>(g, s);
+    return N >= 2048 ? launch_split_gemm_tm<256, OUT_F32>(g, s) : launch_split_gemm_tm<128, OUT_F32>(g, s);
 }
 
 // The same product on two fp16 planes per operand (three plane products instead of six): every row of A and of W
@@ -1199,25 +1227,17 @@ int split_linear_f16(const float* a, const float* w, const float* bias, long lon
     // (the flag word collects "non-finite input": such rows give non-finite outputs, as an fp32 product would)
     MDNO_TRY(split_planes_f16(a, (int)rows, K, sw.ap, sw.aus, sw.flag, s));
     MDNO_TRY(split_planes_f16(w, N, K, sw.wp, sw.wus, sw.flag, s));
-    SplitGemmArgs g{sw.ap, sw.wp, bias, c, nullptr, nullptr, 0, (int)((rows + 255) / 256 * 256), N, K, 0, 0, (int)rows, 0};
+    SplitGemmArgs g = split_gemm_args(sw.ap, sw.wp, bias, N, K, (int)((rows + 255) / 256 * 256));
+    g.C = c;
+    g.rows_valid = (int)rows;
     g.b_unscale = sw.wus;
     g.a_unscale = sw.aus;
-    return relu ? launch_split_f16_gemm<3, 2>(g, s) : launch_split_f16_gemm<0, 2>(g, s);
+    return relu ? launch_split_f16_gemm<OUT_F32_RELU, 2>(g, s) : launch_split_f16_gemm<OUT_F32, 2>(g, s);
 }
 
 bool edge_mlp_split_supported(int ker_width, int out_dim) {
     return ker_width % 32 == 0 && ker_width % TN == 0 && out_dim % TN == 0;
 }
-
-// One layout for both entry points: [h1 planes][h2 planes][W1 planes][W2 planes][W1 fp16 planes][flags][W2 fp16 planes]
-// [W1, W2 unscale][h1, h2 fp16 planes of a few-row launch]
-struct SplitWs {
-    unsigned char *h1p, *h2p, *w1p, *w2p, *w1h, *w2h;
-    unsigned char *h1h, *h2h;   // few rows (both_gemms_small): the fp16 images beside the bf16 ones in h1p, h2p
-    float *w1us, *w2us;      // per-row unscale factors of the fp16 weight images
-    int* f16_flags;
-    size_t total;
-};
 
 // Both GEMMs of the full edge-MLP on the few-rows kernel: then every kernel of the chain carries both operand
 // images and picks one itself, and no fallback launch follows (at that size a launch costs more than a GEMM)
@@ -1249,163 +1269,138 @@ size_t edge_mlp_split_workspace_bytes(int ker_width, int out_dim, long long chun
     return carve_split(nullptr, ker_width, out_dim, chunk).total;
 }
 
-// (the word behind the flags that counts the products redone on bf16 planes: activation flags + 7)
 int* edge_mlp_split_activation_flags(void* workspace, int ker_width, int out_dim, long long chunk) {
-    return carve_split(workspace, ker_width, out_dim, chunk).f16_flags + 1;
+    return carve_split(workspace, ker_width, out_dim, chunk).f16_flags + F16_ACT_RANGE;
 }
 
-int edge_mlp_split(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                   const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                   long long edge_cap, long long chunk, int ker_in, int ker_width, int out_dim,
-                   const EdgeMlpWeights& w, float* w_e, void* workspace, hipStream_t s, int phase_in, bool f16) {
+int edge_mlp_split(const EdgeSource& es, long long chunk, int ker_in, int ker_width, const EdgeMlpWeights& w,
+                   const EdgeMlpOut& out, void* workspace, hipStream_t s, int phase_in, bool f16) {
     const int phase = phase_in & WP_PHASE_MASK;
     const bool flags_zeroed = (phase_in & WP_FLAGS_ZEROED) != 0;
+    const bool hidden = out.h_tiled != nullptr;       // stop after layer 1, whose epilogue writes H k-tiled
+    const int k = ker_width, out_dim = hidden ? k : out.out_dim;      // (H target: the layout of a k x k last layer)
     MDNO_REQUIRE(ker_in > 0 && ker_in <= MAX_F, MDNO_EUNSUPPORTED, "edge_mlp: ker_in=%d (1..%d)", ker_in, MAX_F);
-    MDNO_REQUIRE(((reinterpret_cast<uintptr_t>(w.w1) | reinterpret_cast<uintptr_t>(w.w2)) & 15) == 0, MDNO_EINVAL,
+    MDNO_REQUIRE(((reinterpret_cast<uintptr_t>(w.w1) | (hidden ? 0 : reinterpret_cast<uintptr_t>(w.w2))) & 15) == 0, MDNO_EINVAL,
                  "edge_mlp: weight pointers must be 16-byte aligned");
-    const int k = ker_width;
     const SplitWs sw = carve_split(workspace, k, out_dim, chunk);
-    unsigned char *h1p = sw.h1p, *h2p = sw.h2p, *w1p = sw.w1p, *w2p = sw.w2p;
-    if (phase != WP_RUN_ONLY) {
+    if (phase != WP_RUN_ONLY) {      // the weights' plane images; W2's only where the last layer runs here
         TimedSection ts(KID_EDGE_L0, s);
         const long long c1 = (long long)k * (k / 8), c2 = (long long)out_dim * (k / 8);
-        hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, s, w.w1, k, k, w1p);
-        hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((c2 + 255) / 256)), dim3(256), 0, s, w.w2, out_dim, k,
-                           w2p);
-        if (f16) {   // fp16 images of W1, W2 + their range flag (flags[0]); the bf16 images serve the fallback
-            MDNO_TRY(fill_ints(sw.f16_flags, 1, 0, s));
-            MDNO_TRY(split_planes_f16(w.w1, k, k, sw.w1h, sw.w1us, sw.f16_flags, s));
-            MDNO_TRY(split_planes_f16(w.w2, out_dim, k, sw.w2h, sw.w2us, sw.f16_flags, s));
+        hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, s, w.w1, k, k, sw.w1p);
+        if (!hidden)
+            hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((c2 + 255) / 256)), dim3(256), 0, s, w.w2, out_dim, k,
+                               sw.w2p);
+        if (f16) {   // fp16 images + their range flag (F16_WEIGHT_RANGE); the bf16 images serve the fallback
+            MDNO_TRY(fill_ints(sw.f16_flags + F16_WEIGHT_RANGE, 1, 0, s));
+            MDNO_TRY(split_planes_f16(w.w1, k, k, sw.w1h, sw.w1us, sw.f16_flags + F16_WEIGHT_RANGE, s));
+            if (!hidden) MDNO_TRY(split_planes_f16(w.w2, out_dim, k, sw.w2h, sw.w2us, sw.f16_flags + F16_WEIGHT_RANGE, s));
         }
     }
     MDNO_TRY(check_launch("split_planes_kernel"));
     if (phase == WP_PREPARE_ONLY) return MDNO_OK;
-    const float* pos_mode = edge_attr ? nullptr : frames;
     // activation flags of THIS forward (range, h1 seen, h2 seen)
-    if (f16 && !flags_zeroed) MDNO_TRY(fill_ints(sw.f16_flags + 1, kEdgeMlpActivationFlags, 0, s));
-    for (long long e0 = 0; e0 < edge_cap; e0 += chunk) {
-        const int cnt = (int)((edge_cap - e0) < chunk ? (edge_cap - e0) : chunk);
-        if (f16 && both_gemms_small(k, out_dim, chunk)) {
+    if (f16 && !flags_zeroed) MDNO_TRY(fill_ints(sw.f16_flags + F16_ACT_RANGE, kEdgeMlpActivationFlags, 0, s));
+    for (long long e0 = 0; e0 < es.edge_cap; e0 += chunk) {
+        const int cnt = (int)((es.edge_cap - e0) < chunk ? (es.edge_cap - e0) : chunk);
+        // this chunk's rows of the target (chunk % 128 == 0: the k-tiled tile index continues across chunks)
+        float* const c_out = hidden ? out.h_tiled + (size_t)e0 * k : out.w_e + (size_t)e0 * out_dim;
+        // a product over this chunk's rows: operand images, bias, N (K = k)
+        auto chunk_gemm = [&](const unsigned char* Ap, const unsigned char* Bp, const float* bias, int N) {
+            SplitGemmArgs g = split_gemm_args(Ap, Bp, bias, N, k, (int)chunk);
+            g.num_edges = es.num_edges; g.row_begin = e0;
+            return g;
+        };
+        // (W_e cases first, then H: a code object holds its kernels in the order their launchers are first named)
+        if (f16 && !hidden && both_gemms_small(k, out_dim, chunk)) {
             // a few hundred rows: three launches — every kernel writes / finds both operand images and the
             // GEMMs take the bf16 ones themselves when a flag is up (gemm_split_f16_small_kernel)
-            {
-                TimedSection ts(KID_EDGE_L0, s);
-                MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                              e0, cnt, ker_in, k, w.w0, w.b0, h1p, s, true, sw.f16_flags, 0, sw.h1h));
-            }
+            MDNO_TRY(launch_edge_l0_split(L0_BOTH, es, e0, cnt, ker_in, k, w, sw, s));
             {
                 TimedSection ts(KID_GEMM_L1, s);
-                SplitGemmArgs gh{sw.h1h, sw.w1h, w.b1, nullptr, sw.h2h, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0,
-                                 sw.f16_flags, 1, sw.w1us, h1p, w1p, h2p};
-                MDNO_TRY((launch_split_f16_gemm<4, 2>(gh, s)));
+                SplitGemmArgs gh = chunk_gemm(sw.h1h, sw.w1h, w.b1, k);
+                gh.Cp = sw.h2h;
+                gh.f16_flags = sw.f16_flags; gh.f16_need = F16_NEED_H1;
+                gh.b_unscale = sw.w1us;
+                gh.Ap_b = sw.h1p; gh.Bp_b = sw.w1p; gh.Cp_b = sw.h2p;      // the same three, on bf16 planes
+                MDNO_TRY((launch_split_f16_gemm<OUT_PLANES_F16, 2>(gh, s)));
             }
             {
                 TimedSection ts(KID_GEMM_L2, s);
-                SplitGemmArgs gh{sw.h2h, sw.w2h, w.b2, w_e + (size_t)e0 * out_dim, nullptr, num_edges, e0, (int)chunk, out_dim,
-                                 k, 0, 0, 0, 0, sw.f16_flags, 3, sw.w2us, h2p, w2p, nullptr};
-                MDNO_TRY((launch_split_f16_gemm<0, 2>(gh, s)));
+                SplitGemmArgs gh = chunk_gemm(sw.h2h, sw.w2h, w.b2, out_dim);
+                gh.C = c_out;
+                gh.f16_flags = sw.f16_flags; gh.f16_need = F16_NEED_H1 | F16_NEED_H2;
+                gh.b_unscale = sw.w2us;
+                gh.Ap_b = sw.h2p; gh.Bp_b = sw.w2p;
+                MDNO_TRY((launch_split_f16_gemm<OUT_F32, 2>(gh, s)));
             }
             continue;
         }
-        if (f16) {
+        if (f16 && !hidden) {
             // SPLIT_F16: layer 0 -> fp16 planes, hidden layer -> fp16 planes of h2 (its epilogue checks the
             // range), last layer -> W_e; then the same chunk on the bf16 kernels, which exit at their first
             // instruction unless a range flag is up
+            MDNO_TRY(launch_edge_l0_split(L0_F16, es, e0, cnt, ker_in, k, w, sw, s));
             {
-                TimedSection ts(KID_EDGE_L0, s);
-                MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                              e0, cnt, ker_in, k, w.w0, w.b0, h1p, s, true, sw.f16_flags));
+                TimedSection ts(KID_GEMM_L1, s);   // reads h1, writes h2 planes + their range / "seen" words
+                SplitGemmArgs gh = chunk_gemm(sw.h1p, sw.w1h, w.b1, k);
+                gh.Cp = sw.h2p;
+                gh.f16_flags = sw.f16_flags; gh.f16_need = F16_NEED_H1;
+                gh.b_unscale = sw.w1us;
+                MDNO_TRY((launch_split_f16_gemm<OUT_PLANES_F16, 2>(gh, s)));
             }
             {
-                TimedSection ts(KID_GEMM_L1, s);   // reads h1 (need 1), writes h2 planes + their range / "seen" words
-                SplitGemmArgs gh{h1p, sw.w1h, w.b1, nullptr, h2p, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0, sw.f16_flags,
-                                 1, sw.w1us};
-                MDNO_TRY((launch_split_f16_gemm<4, 2>(gh, s)));
-            }
-            {
-                TimedSection ts(KID_GEMM_L2, s);   // reads h2 (need 3: h1 and h2 both fit fp16)
-                SplitGemmArgs gh{h2p, sw.w2h, w.b2, w_e + (size_t)e0 * out_dim, nullptr, num_edges, e0, (int)chunk, out_dim,
-                                 k, 0, 0, 0, 0, sw.f16_flags, 3, sw.w2us};
-                MDNO_TRY((launch_split_f16_gemm<0, 2>(gh, s)));
-                // the bf16 trio runs iff the fp16 chain did not go all the way through (same test: need 3)
-                MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                              e0, cnt, ker_in, k, w.w0, w.b0, h1p, s, false, sw.f16_flags, 3));
-                SplitGemmArgs g1{h1p, w1p, w.b1, nullptr, h2p, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0, sw.f16_flags, 3};
-                MDNO_TRY((launch_split_gemm_tm<128, 1>(g1, s)));
-                SplitGemmArgs g2{h2p, w2p, w.b2, w_e + (size_t)e0 * out_dim, nullptr, num_edges, e0, (int)chunk, out_dim, k,
-                                 0, 0, 0, 0, sw.f16_flags, 3};
-                if (out_dim >= 2048) MDNO_TRY((launch_split_gemm_tm<256, 0>(g2, s)));
-                else MDNO_TRY((launch_split_gemm_tm<128, 0>(g2, s)));
+                TimedSection ts(KID_GEMM_L2, s);   // reads h2 (h1 and h2 both fit fp16)
+                const int need = F16_NEED_H1 | F16_NEED_H2;
+                SplitGemmArgs gh = chunk_gemm(sw.h2p, sw.w2h, w.b2, out_dim);
+                gh.C = c_out;
+                gh.f16_flags = sw.f16_flags; gh.f16_need = need;
+                gh.b_unscale = sw.w2us;
+                MDNO_TRY((launch_split_f16_gemm<OUT_F32, 2>(gh, s)));
+                // the bf16 trio runs iff the fp16 chain did not go all the way through (same test: `need`)
+                MDNO_TRY(launch_edge_l0_split(L0_BF16_FALLBACK, es, e0, cnt, ker_in, k, w, sw, s, need));
+                SplitGemmArgs g1 = chunk_gemm(sw.h1p, sw.w1p, w.b1, k);
+                g1.Cp = sw.h2p;
+                g1.f16_flags = sw.f16_flags; g1.f16_need = need;
+                MDNO_TRY((launch_split_gemm_tm<128, OUT_PLANES>(g1, s)));
+                SplitGemmArgs g2 = chunk_gemm(sw.h2p, sw.w2p, w.b2, out_dim);
+                g2.C = c_out;
+                g2.f16_flags = sw.f16_flags; g2.f16_need = need;
+                if (out_dim >= 2048) MDNO_TRY((launch_split_gemm_tm<256, OUT_F32>(g2, s)));
+                else MDNO_TRY((launch_split_gemm_tm<128, OUT_F32>(g2, s)));
             }
             continue;
         }
-        {
-            TimedSection ts(KID_EDGE_L0, s);
-            MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                          e0, cnt, ker_in, k, w.w0, w.b0, h1p, s));
+        if (!hidden) {
+            MDNO_TRY(launch_edge_l0_split(L0_BF16, es, e0, cnt, ker_in, k, w, sw, s));
+            SplitGemmArgs g1 = chunk_gemm(sw.h1p, sw.w1p, w.b1, k);
+            g1.Cp = sw.h2p;
+            MDNO_TRY(launch_split_gemm<OUT_PLANES>(g1, KID_GEMM_L1, s));
+            SplitGemmArgs g2 = chunk_gemm(sw.h2p, sw.w2p, w.b2, out_dim);
+            g2.C = c_out;
+            MDNO_TRY(launch_split_gemm<OUT_F32>(g2, KID_GEMM_L2, s));
+            continue;
         }
-        SplitGemmArgs g1{h1p, w1p, w.b1, nullptr, h2p, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0};
-        MDNO_TRY(launch_split_gemm<1>(g1, KID_GEMM_L1, s));
-        SplitGemmArgs g2{h2p, w2p, w.b2, w_e + (size_t)e0 * out_dim, nullptr, num_edges, e0, (int)chunk, out_dim, k,
-                         0, 0, 0, 0};
-        MDNO_TRY(launch_split_gemm<0>(g2, KID_GEMM_L2, s));
-    }
-    return MDNO_OK;
-}
-
-int edge_mlp_split_hidden(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                          const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                          long long edge_cap, long long chunk, int ker_in, int ker_width, const EdgeMlpWeights& w,
-                          float* h_out, void* workspace, hipStream_t s, int phase_in, bool f16) {
-    const int phase = phase_in & WP_PHASE_MASK;
-    const bool flags_zeroed = (phase_in & WP_FLAGS_ZEROED) != 0;
-    MDNO_REQUIRE(ker_in > 0 && ker_in <= MAX_F, MDNO_EUNSUPPORTED, "edge_mlp: ker_in=%d (1..%d)", ker_in, MAX_F);
-    MDNO_REQUIRE((reinterpret_cast<uintptr_t>(w.w1) & 15) == 0, MDNO_EINVAL,
-                 "edge_mlp: weight pointers must be 16-byte aligned");
-    const int k = ker_width;
-    const SplitWs sw = carve_split(workspace, k, k, chunk);      // (same layout as the full MLP with out_dim = k)
-    unsigned char *h1p = sw.h1p, *w1p = sw.w1p;
-    if (phase != WP_RUN_ONLY) {
-        TimedSection ts(KID_EDGE_L0, s);
-        const long long c1 = (long long)k * (k / 8);
-        hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((c1 + 255) / 256)), dim3(256), 0, s, w.w1, k, k, w1p);
-        if (f16) {   // fp16 image of W1 + its range flag (flags[0]); the bf16 image above serves the fallback
-            MDNO_TRY(fill_ints(sw.f16_flags, 1, 0, s));
-            MDNO_TRY(split_planes_f16(w.w1, k, k, sw.w1h, sw.w1us, sw.f16_flags, s));
-        }
-    }
-    MDNO_TRY(check_launch("split_planes_kernel"));
-    if (phase == WP_PREPARE_ONLY) return MDNO_OK;
-    const float* pos_mode = edge_attr ? nullptr : frames;
-    // activation flags of THIS forward (range, h1 seen, h2 seen)
-    if (f16 && !flags_zeroed) MDNO_TRY(fill_ints(sw.f16_flags + 1, kEdgeMlpActivationFlags, 0, s));
-    for (long long e0 = 0; e0 < edge_cap; e0 += chunk) {
-        const int cnt = (int)((edge_cap - e0) < chunk ? (edge_cap - e0) : chunk);
-        float* out = h_out + (size_t)e0 * k;      // chunk % 128 == 0: the k-tiled tile index continues across chunks
+        // ---- up to H: the same two run-time cases (fp16 chain + bf16 fallback pair, plain bf16) end at layer 1
         if (f16) {
-            {
-                TimedSection ts(KID_EDGE_L0, s);
-                MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                              e0, cnt, ker_in, k, w.w0, w.b0, h1p, s, true, sw.f16_flags));
-            }
+            MDNO_TRY(launch_edge_l0_split(L0_F16, es, e0, cnt, ker_in, k, w, sw, s));
             TimedSection ts(KID_GEMM_L1, s);
-            SplitGemmArgs gh{h1p, sw.w1h, w.b1, out, nullptr, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0, sw.f16_flags, 1,
-                             sw.w1us};
-            MDNO_TRY((launch_split_f16_gemm<2, 2>(gh, s)));
+            SplitGemmArgs gh = chunk_gemm(sw.h1p, sw.w1h, w.b1, k);
+            gh.C = c_out;
+            gh.f16_flags = sw.f16_flags; gh.f16_need = F16_NEED_H1;
+            gh.b_unscale = sw.w1us;
+            MDNO_TRY((launch_split_f16_gemm<OUT_H_TILED, 2>(gh, s)));
             // the same chunk on the bf16 kernels: both exit at their first instruction unless a range flag is up
-            MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                          e0, cnt, ker_in, k, w.w0, w.b0, h1p, s, false, sw.f16_flags, 1));
-            SplitGemmArgs g1{h1p, w1p, w.b1, out, nullptr, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0, sw.f16_flags, 1};
-            MDNO_TRY((launch_split_gemm_tm<128, 2>(g1, s)));
+            MDNO_TRY(launch_edge_l0_split(L0_BF16_FALLBACK, es, e0, cnt, ker_in, k, w, sw, s, F16_NEED_H1));
+            SplitGemmArgs g1 = chunk_gemm(sw.h1p, sw.w1p, w.b1, k);
+            g1.C = c_out;
+            g1.f16_flags = sw.f16_flags; g1.f16_need = F16_NEED_H1;
+            MDNO_TRY((launch_split_gemm_tm<128, OUT_H_TILED>(g1, s)));
             continue;
         }
-        {
-            TimedSection ts(KID_EDGE_L0, s);
-            MDNO_TRY(launch_edge_l0_split(pos_mode, frame, t_dev, rows_per_frame, src, dst, edge_attr, perm, num_edges,
-                                          e0, cnt, ker_in, k, w.w0, w.b0, h1p, s));
-        }
-        SplitGemmArgs g1{h1p, w1p, w.b1, out, nullptr, num_edges, e0, (int)chunk, k, k, 0, 0, 0, 0};
-        MDNO_TRY(launch_split_gemm<2>(g1, KID_GEMM_L1, s));
+        MDNO_TRY(launch_edge_l0_split(L0_BF16, es, e0, cnt, ker_in, k, w, sw, s));
+        SplitGemmArgs g1 = chunk_gemm(sw.h1p, sw.w1p, w.b1, k);
+        g1.C = c_out;
+        MDNO_TRY(launch_split_gemm<OUT_H_TILED>(g1, KID_GEMM_L1, s));
     }
     return MDNO_OK;
 }

@@ -134,7 +134,7 @@ void fwd_counter_words(const mdno_kernelnn_params* p, const FwdWs& fw, int M, in
     if (fw.factored) *conv = moment_carve(fw.fact, M * N, p->ker_width).counters;
     int* act = edge_mlp_activation_flags(fw.mlp, p->ker_width, fw.factored ? p->ker_width : p->width * p->width, edge_cap,
                                          p->gemm_mode);
-    if (act) *mlp = act + 7;      // (edge_mlp_split.hip: flags[F16_FALLBACK_COUNT = 8]; act = flags + 1)
+    if (act) *mlp = act + (F16_FALLBACK_COUNT - F16_ACT_RANGE);
 }
 
 int zero_counter_words(int* conv, int* mlp, hipStream_t s) {
@@ -159,6 +159,7 @@ int forward_impl(const mdno_kernelnn_params* p, const float* frames, int t0, con
                  const float* edge_attr, const int* perm, float* out_frames, int t_out, float* latent,
                  const FwdWs& ws, int* status, hipStream_t s, int phase = WP_BOTH, const StepTail* tail = nullptr) {
     const int R = M * N, C = p->width;
+    const EdgeSource es{edge_frames, edge_frame, t_dev, R, src, dst, edge_attr, perm, num_edges, edge_cap};
     // WP_PREPARE_ONLY: just the weight-derived operands of the (single, shared) edge-MLP
     const bool prep_only = (phase & WP_PHASE_MASK) == WP_PREPARE_ONLY;
     if (!prep_only && !(phase & WP_PROLOGUE_DONE))
@@ -182,9 +183,8 @@ int forward_impl(const mdno_kernelnn_params* p, const float* frames, int t0, con
             if (block == 0 || own) {
                 EdgeMlpWeights w = own ? EdgeMlpWeights{p->k2_w0, p->k2_b0, p->k2_w1, p->k2_b1, p->k2_w2, p->k2_b2}
                                        : EdgeMlpWeights{p->k_w0, p->k_b0, p->k_w1, p->k_b1, p->k_w2, p->k_b2};
-                MDNO_TRY(edge_mlp_hidden(edge_frames, edge_frame, t_dev, R, src, dst, edge_attr, perm, num_edges, edge_cap,
-                                         p->ker_in, p->ker_width, p->gemm_mode, w, ws.h2, ws.mlp, ws.mlp_bytes, s,
-                                         block == 0 ? phase : (phase & ~WP_FLAGS_ZEROED)));
+                MDNO_TRY(edge_mlp(es, p->ker_in, p->ker_width, p->gemm_mode, w, EdgeMlpOut::hidden(ws.h2), ws.mlp, ws.mlp_bytes, s,
+                                  block == 0 ? phase : (phase & ~WP_FLAGS_ZEROED)));
                 if ((phase & WP_PHASE_MASK) != WP_RUN_ONLY) MDNO_TRY(moment_prepare_weights(w.w2, w.b2, p->ker_width, mw, s, p->gemm_mode));
             }
             if (prep_only) return MDNO_OK;
@@ -205,9 +205,8 @@ int forward_impl(const mdno_kernelnn_params* p, const float* frames, int t0, con
                 EdgeMlpWeights w = (block == 0)
                                        ? EdgeMlpWeights{p->k_w0, p->k_b0, p->k_w1, p->k_b1, p->k_w2, p->k_b2}
                                        : EdgeMlpWeights{p->k2_w0, p->k2_b0, p->k2_w1, p->k2_b1, p->k2_w2, p->k2_b2};
-                MDNO_TRY(edge_mlp(edge_frames, edge_frame, t_dev, R, src, dst, edge_attr, perm, num_edges, edge_cap,
-                                  p->ker_in, p->ker_width, C * C, p->gemm_mode, w, ws.w_e, ws.mlp, ws.mlp_bytes, s,
-                                  block == 0 ? phase : (phase & ~WP_FLAGS_ZEROED)));   // (the caller zeroed the flags once)
+                MDNO_TRY(edge_mlp(es, p->ker_in, p->ker_width, p->gemm_mode, w, EdgeMlpOut::full(ws.w_e, C * C), ws.mlp, ws.mlp_bytes,
+                                  s, block == 0 ? phase : (phase & ~WP_FLAGS_ZEROED)));   // (the caller zeroed the flags once)
             }
             if (prep_only) return MDNO_OK;
             const float* root = block == 0 ? p->conv1_root : p->conv2_root;

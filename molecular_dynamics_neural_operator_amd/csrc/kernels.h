@@ -1,8 +1,7 @@
 // Internal launch functions behind the C ABI.  They take one extra pair of arguments the public
 // entry points do not expose: a frame index plus an optional DEVICE-side step counter, so that a
-// captured rollout step (hipGraph) can be replayed unchanged while the window advances.
-//   frames : f32 [T, R, 3] time-major, R = M*N rows per frame; frame f starts at frames + f*R*3
-//   frame  : host index; effective frame = frame + (t_dev ? *t_dev : 0)
+// captured rollout step (hipGraph) can be replayed unchanged while the window advances
+// (frames / frame / t_dev: see EdgeSource).
 #pragma once
 #include "common.h"
 
@@ -43,36 +42,57 @@ struct EdgeMlpWeights {
 // WP_PROLOGUE_DONE (OR-ed in, engine only): the node features of this forward are already in place.
 enum WeightPhase { WP_BOTH = 0, WP_PREPARE_ONLY = 1, WP_RUN_ONLY = 2, WP_PHASE_MASK = 3, WP_FLAGS_ZEROED = 4,
                    WP_PROLOGUE_DONE = 8 };
-constexpr int kEdgeMlpActivationFlags = 3;
-// the three per-forward flag words of the SPLIT_F16 edge-MLP inside `workspace` (NULL in the other modes);
-// out_dim = ker_width for edge_mlp_hidden
+// Words of the SPLIT_F16 flag block (64 ints in the edge-MLP workspace).  Any of the first four sends a product down
+// the bf16 path (f16_blocked, edge_mlp_split.hip); the count is never reset by the library's forwards: a rollout plan
+// zeroes it per run and reads it back (include/mdno.h).
+enum F16FlagWord {
+    F16_WEIGHT_RANGE = 0,     // a weight is not finite (set when the weight planes are built)
+    F16_ACT_RANGE = 1,        // an activation of the current forward is out of fp16 range
+    F16_H1_SEEN = 2,          // h1 / h2 of the current forward hold at least one value >= F16_ACT_MIN (split_layout.h:
+    F16_H2_SEEN = 3,          //   below that the two-plane form has only an absolute error bound)
+    F16_FALLBACK_COUNT = 8,   // products (GEMM launches) that took the bf16 path
+};
+constexpr int kEdgeMlpActivationFlags = 3;      // the per-forward words: F16_ACT_RANGE .. F16_H2_SEEN
+// the per-forward flag words of the SPLIT_F16 edge-MLP inside `workspace`, from F16_ACT_RANGE on (NULL in the other
+// modes); out_dim = ker_width for the H target
 int* edge_mlp_activation_flags(void* workspace, int ker_width, int out_dim, long long edge_cap, int gemm_mode);
 int* edge_mlp_split_activation_flags(void* workspace, int ker_width, int out_dim, long long chunk);
 
-// gemm_mode: MDNO_GEMM_SPLIT_BF16 (default; falls back to exact fp32 when the shape is not tileable)
-// or MDNO_GEMM_F32.
-int edge_mlp(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src, const int* dst,
-             const float* edge_attr, const int* perm, const int* num_edges, long long edge_cap, int ker_in,
-             int ker_width, int out_dim, int gemm_mode, const EdgeMlpWeights& w, float* w_e, void* workspace,
-             size_t workspace_bytes, hipStream_t s, int phase = WP_BOTH);
+// Where the edge attributes of an edge-MLP call come from: positions gathered through the graph (attr =
+// [pos[src], pos[dst]], ker_in == 6), or the caller's own edge_attr, which wins when both are given.
+struct EdgeSource {
+    const float* frames;      // f32 [T, R, 3] time-major, R = rows_per_frame = M*N; frame f starts at frames + f*R*3
+    int frame;                // host index; effective frame = frame + (t_dev ? *t_dev : 0)
+    const int* t_dev;         // optional device-side step counter
+    int rows_per_frame;
+    const int *src, *dst;     // [edge_cap] endpoints, CSR edge order
+    const float* edge_attr;   // [*, ker_in] explicit attributes, or NULL
+    const int* perm;          // edge e reads edge_attr row perm[e] (NULL: row e)
+    const int* num_edges;     // device count of valid edges
+    long long edge_cap;
+    const float* positions() const { return edge_attr ? nullptr : frames; }   // what the layer-0 kernels take as `frames`
+};
+
+// What an edge-MLP call produces — exactly one of the two:
+//   w_e      the full MLP, fp32 [edge_cap, out_dim] row-major in CSR edge order (what the materialised conv streams)
+//   h_tiled  the MLP up to its last hidden activation H = relu(L1(relu(L0(attr)))), fp32 k-tiled
+//            [edge_cap/128][ker_width/32][128][32] (what the factored conv streams: moment.hip K1)
+struct EdgeMlpOut {
+    float* w_e;
+    int out_dim;
+    float* h_tiled;
+    static EdgeMlpOut full(float* w_e, int out_dim) { return {w_e, out_dim, nullptr}; }
+    static EdgeMlpOut hidden(float* h_tiled) { return {nullptr, 0, h_tiled}; }
+};
+
+// gemm_mode: MDNO_GEMM_SPLIT_BF16 (default; falls back to exact fp32 when the shape is not tileable),
+// MDNO_GEMM_SPLIT_F16 or MDNO_GEMM_F32.
+int edge_mlp(const EdgeSource& es, int ker_in, int ker_width, int gemm_mode, const EdgeMlpWeights& w,
+             const EdgeMlpOut& out, void* workspace, size_t workspace_bytes, hipStream_t s, int phase = WP_BOTH);
 bool edge_mlp_split_supported(int ker_width, int out_dim);
 size_t edge_mlp_split_workspace_bytes(int ker_width, int out_dim, long long chunk);
-int edge_mlp_split(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                   const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                   long long edge_cap, long long chunk, int ker_in, int ker_width, int out_dim,
-                   const EdgeMlpWeights& w, float* w_e, void* workspace, hipStream_t s, int phase = WP_BOTH,
-                   bool f16 = false);
-
-// Edge-MLP up to its last hidden activation: H = relu(L1(relu(L0(attr)))) as fp32 [edge_cap, ker_width]
-// row-major (what the factored conv consumes); same attr modes and gemm_mode as edge_mlp.
-int edge_mlp_hidden(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                    const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                    long long edge_cap, int ker_in, int ker_width, int gemm_mode, const EdgeMlpWeights& w,
-                    float* h_out, void* workspace, size_t workspace_bytes, hipStream_t s, int phase = WP_BOTH);
-int edge_mlp_split_hidden(const float* frames, int frame, const int* t_dev, int rows_per_frame, const int* src,
-                          const int* dst, const float* edge_attr, const int* perm, const int* num_edges,
-                          long long edge_cap, long long chunk, int ker_in, int ker_width, const EdgeMlpWeights& w,
-                          float* h_out, void* workspace, hipStream_t s, int phase = WP_BOTH, bool f16 = false);
+int edge_mlp_split(const EdgeSource& es, long long chunk, int ker_in, int ker_width, const EdgeMlpWeights& w,
+                   const EdgeMlpOut& out, void* workspace, hipStream_t s, int phase, bool f16);
 
 // Pieces of the split-bf16 GEMM usable on their own (edge_mlp_split.hip): fp32 [rows,K] -> tiled bf16
 // planes (buffer of split_planes_bytes), and C[rows,N] = A . Bt^T (fp32 row-major) from two such images.

@@ -419,7 +419,7 @@ int mdno_nnconv_bwd_we(const float* x, const float* gs, const int32_t* src, cons
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Training ops, bf16 (BASELINE configs[3] names bf16; csrc/train_bf16.hip).  The block's large tensors —
+ * Training ops, bf16 (BASELINE configs[3] names bf16; csrc/train_bf16.hip, csrc/train_conv.hip).  The block's large tensors —
  * h1, h2 [E,k], W_e and dW_e [E,64*64] — are bf16, row-major (pointers typed void*), every GEMM is one
  * bf16 x bf16 MFMA product with fp32 accumulation; parameters (cast per call from the fp32 masters), node
  * features, conv outputs and all reductions are fp32.  Same formulas as the fp32 ops above, width 64.

@@ -6,7 +6,7 @@
 # sha256 over the bytes of csrc/*.{hip,h,sh} and include/mdno.h in C-locale name order (the Python side,
 # _lib.source_build_id(), computes the same thing).  It is compiled into the library (mdno_build_id()) and kept in
 # build/BUILD_ID; if the sources' id, the flags or the library differ from what build/ holds, EVERYTHING is rebuilt
-# from scratch (all 13 files in parallel: ~10 s) — there is no per-file incrementality to go stale.
+# from scratch (every file in parallel: ~10 s) — there is no per-file incrementality to go stale.
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../libmdno.so"

@@ -22,70 +22,15 @@
 // 178 us = 6.04 TB/s incl. ~7 us of ramp): 993 MB in 187 us at N=504 (92 % of that), 6.1 TB/s at 8
 // members.  Splitting rows into 16-edge segments balanced over waves (two-pass, partial sums) was
 // built and measured: no gain (192 us) — the kernel is bandwidth-, not balance-limited.
+#include "conv64.h"      // the lane mapping, the 16 chains and the per-edge accumulation
 #include "kernels.h"
 
 namespace mdno {
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// W_e is read exactly once per application: stream it past the caches (global_load ... nt)
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4_stream(const float* p) {
-    const f32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-
 // max aggregation as torch has it (index_reduce_ / scatter_reduce "amax", torch_geometric's scatter max): a NaN message
 // wins and stays.  fmaxf (v_max_f32) returns the other operand, so a diverged edge would leave its row finite
 __device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ void fma4(float4& a, float s, const float4& w) {
-    a.x = fmaf(s, w.x, a.x);
-    a.y = fmaf(s, w.y, a.y);
-    a.z = fmaf(s, w.z, a.z);
-    a.w = fmaf(s, w.w, a.w);
-}
-
-// acc += x[16g..16g+15] . Wblk[16g..16g+15][4q..4q+3].  STREAM: W is read once per application and is far larger
-// than the caches (nt loads leave them to x); !STREAM: all of W_e fits the L2s (a short chain: 330 edges = 5.4 MB
-// over 8 x 4 MB), the 2 x depth applications of a forward re-read it, and a row's 12 x 16 KiB reach its ONE CU at
-// the L2's 66-73 GB/s per CU instead of the Infinity Cache's 33 (MI355X_MICROARCH.md, gather rates): the
-// application is bound by exactly that
-template <bool STREAM = true>
-__device__ __forceinline__ void edge_accumulate64(float4& acc, const float* __restrict__ xrow,
-                                                  const float* __restrict__ wmat, int g, int q) {
-    // the 16 KiB of W first: their address does not wait for src[p], which the x row's does
-    const float* wp = wmat + (16 * g) * 64 + 4 * q;
-    float4 w[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) w[r] = STREAM ? ld4_stream(wp + r * 64) : ld4(wp + r * 64);
-    const float* xp = xrow + 16 * g;
-    const float4 x0 = ld4(xp), x1 = ld4(xp + 4), x2 = ld4(xp + 8), x3 = ld4(xp + 12);
-    // all twenty loads in flight before the first FMA waits for one (left alone, the scheduler waits for the
-    // x row after nine of them and issues the rest behind that round trip)
-    __builtin_amdgcn_sched_barrier(0);
-    fma4(acc, x0.x, w[0]);  fma4(acc, x0.y, w[1]);  fma4(acc, x0.z, w[2]);  fma4(acc, x0.w, w[3]);
-    fma4(acc, x1.x, w[4]);  fma4(acc, x1.y, w[5]);  fma4(acc, x1.z, w[6]);  fma4(acc, x1.w, w[7]);
-    fma4(acc, x2.x, w[8]);  fma4(acc, x2.y, w[9]);  fma4(acc, x2.z, w[10]); fma4(acc, x2.w, w[11]);
-    fma4(acc, x3.x, w[12]); fma4(acc, x3.y, w[13]); fma4(acc, x3.z, w[14]); fma4(acc, x3.w, w[15]);
-}
-
-__device__ __forceinline__ float4 reduce_over_g(float4 a) {
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        a.x += __shfl_xor(a.x, o);
-        a.y += __shfl_xor(a.y, o);
-        a.z += __shfl_xor(a.z, o);
-        a.w += __shfl_xor(a.w, o);
-    }
-    return a;
-}
-
-// A row's edges are dealt to CHAINS = 16 summation chains (edge i of the row -> chain i % 16) whatever
-// the launch shape: with 16 waves a wave owns one chain, with 4 waves it owns chains w, w+4, w+8, w+12
-// (one accumulator each).  The chains are then added in chain order, so the 4- and the 16-wave launch
-// give the same bits and a row's result does not depend on how many rows it is batched with.
-constexpr int CHAINS = 16;
 
 template <int WAVES, bool STREAM = true>
 __global__ __launch_bounds__(WAVES * 64) void nnconv64_row_kernel(
@@ -110,13 +55,13 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_row_kernel(
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         if (aggr != MDNO_AGGR_MAX) {
             for (int p = beg + wave + u * WAVES; p < end; p += CHAINS)
-                edge_accumulate64<STREAM>(acc, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
+                edge_accumulate64<float, STREAM>(acc, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
             acc = reduce_over_g(acc);
         } else {      // every message in full, then the running maximum of the chain (-inf: a chain without edges)
             acc = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
             for (int p = beg + wave + u * WAVES; p < end; p += CHAINS) {
                 float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
-                edge_accumulate64<STREAM>(m, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
+                edge_accumulate64<float, STREAM>(m, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
                 m = reduce_over_g(m);
                 acc = make_float4(max_nan(acc.x, m.x), max_nan(acc.y, m.y), max_nan(acc.z, m.z), max_nan(acc.w, m.w));
             }
@@ -127,7 +72,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_row_kernel(
     // got the fewest edges
     const bool root_wave = root != nullptr && wave == (deg % WAVES);
     float4 racc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (root_wave) edge_accumulate64<false>(racc, x + (size_t)row * 64, root, g, q);      // (every row reads root: cached)
+    if (root_wave) edge_accumulate64<float, false>(racc, x + (size_t)row * 64, root, g, q);      // (every row reads root: cached)
 
     racc = reduce_over_g(racc);
     if (root_wave && lane < 16) *reinterpret_cast<float4*>(&rootred[4 * lane]) = racc;
@@ -206,13 +151,13 @@ __global__ __launch_bounds__(1024 / SPLIT) void nnconv64_colsplit_kernel(
     };
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int p = beg + chain; p < end; p += CHAINS)
-        edge_accumulate64<STREAM>(acc, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
+        edge_accumulate64<float, STREAM>(acc, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
     acc = reduce_g(acc);
     if (g == 0) *reinterpret_cast<float4*>(&red[chain][4 * (l % QN)]) = acc;
     // the root term: the chain that got the fewest edges takes it (as the wave deg % 16 does in the row kernel)
     const bool root_chain = root != nullptr && chain == (deg % CHAINS);
     float4 racc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (root_chain) edge_accumulate64<false>(racc, x + (size_t)row * 64, root, g, q);
+    if (root_chain) edge_accumulate64<float, false>(racc, x + (size_t)row * 64, root, g, q);
     racc = reduce_g(racc);
     if (root_chain && g == 0) *reinterpret_cast<float4*>(&rootred[4 * (l % QN)]) = racc;
     __syncthreads();

@@ -1,15 +1,8 @@
-// Training (BASELINE.json configs[3]): backward of the kernel-integral block — 2*depth conv
-// applications sharing one edge-MLP — as individually callable ops.  Replaces what autograd +
-// torch_geometric do for graph_kernel.py:445-474 (train) on the path :299-302 / :194-209 / :239-242.
-//
-// Forward (materialised) per application a = 1..L:  z_a = mean_{e->t} x_{a-1}[src e] . W_e + x_{a-1}.root + bias,
-// x_a = relu(z_a), W_e = reshape(L2(relu(L1(relu(L0 attr_e))))).  Given g_a = dLoss/dx_a:
-//     gz_a      = g_a * (x_a > 0)                          gs_a[t] = gz_a[t] / max(deg_t, 1)
-//     g_{a-1}   = gz_a . root^T + sum_{e: src e = r} W_e . gs_a[dst e]                 (nnconv_bwd_x)
-//     d root    = sum_a x_{a-1}^T . gz_a,   d bias = sum_a colsum(gz_a)               (nnconv_bwd_root)
-//     d W_e     = sum_a x_{a-1}[src e] (x) gs_a[dst e]                                (nnconv_bwd_we)
-// and through the edge-MLP with  C = A . Bt^T  (linear_fwd),  C = A^T . B over rows (gemm_atb), column sums
-// and ReLU masks.  Everything is fp32; reductions over rows/edges use fixed-order partial sums
+// Training (BASELINE.json configs[3]): the Linear-layer ops of the fp32 training path — the shared edge-MLP of the
+// kernel-integral block, forward and backward, as individually callable ops: C = act(A . Bt^T + bias) (linear_fwd),
+// C = A^T . B over rows (gemm_atb), column sums, ReLU masks and a transpose.  The conv applications and their
+// gradients are train_conv.hip.  Replaces what autograd does for graph_kernel.py:445-474 (train) on the path
+// :299-302 / :239-242.  Everything is fp32; reductions over rows/edges use fixed-order partial sums
 // (no float atomics), so gradients are bitwise reproducible.
 #include "kernels.h"
 #include "mfma_f32.h"
@@ -348,188 +341,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
         if (bx + i < Cc && by + tx < R) At[(size_t)(bx + i) * R + by + tx] = tile[tx][i];
 }
 
-__global__ __launch_bounds__(256) void inv_degree_kernel(const int* __restrict__ row_ptr, int rows, int mean,
-                                                         float* __restrict__ inv) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int d = row_ptr[r + 1] - row_ptr[r];
-    inv[r] = mean ? 1.0f / (float)(d > 1 ? d : 1) : 1.0f;
-}
-
-// ---------------------------------------------------------------- conv backward: input gradient
-// g_prev[r] = gz[r] . root^T + sum_{p in out-edges of r} W_e[eid[p]] . gs[dst[p]]   (64x64 only)
-// One workgroup (4 waves) per source row r; its out-edges (positions in the dst-sorted edge array)
-// come from the src-sorted CSR (row_ptr_s, eid_s, dst_s).  Lane (g, q) owns rows 16g..16g+15 x
-// columns 4q..4q+3 of W_e as in the forward kernel; per-lane partial dot products are summed over
-// ALL the row's edges first and reduced across the 16 q-lanes once per row.
-// STREAM: the matrix is an edge's W_e — read once per application, far larger than the caches: non-temporal loads
-template <bool STREAM>
-__device__ __forceinline__ void wg_accumulate(float (&acc)[16], const float* __restrict__ wmat,
-                                              const float* __restrict__ gvec, int g, int q) {
-    typedef float f32x4_t __attribute__((ext_vector_type(4)));
-    const float4 gq = *reinterpret_cast<const float4*>(gvec + 4 * q);
-    const float* wp = wmat + (16 * g) * 64 + 4 * q;
-    float4 w[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        if (STREAM) {
-            const f32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(wp + r * 64));
-            w[r] = make_float4(t.x, t.y, t.z, t.w);
-        } else {
-            w[r] = *reinterpret_cast<const float4*>(wp + r * 64);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        acc[r] = fmaf(w[r].x, gq.x, fmaf(w[r].y, gq.y, fmaf(w[r].z, gq.z, fmaf(w[r].w, gq.w, acc[r]))));
-}
-
-// y_below != NULL: gz_below / gs_below of the application below are written instead of g_prev (mdno_relu_bwd2 fused)
-__global__ __launch_bounds__(256) void nnconv_bwd_x_kernel(const float* __restrict__ gz, const float* __restrict__ gs,
-                                                           const int* __restrict__ row_ptr_s,
-                                                           const int* __restrict__ eid_s, const int* __restrict__ dst_s,
-                                                           const float* __restrict__ w_e, const float* __restrict__ root,
-                                                           float* __restrict__ g_prev, int num_rows,
-                                                           const float* __restrict__ y_below = nullptr,
-                                                           const float* __restrict__ inv_deg = nullptr,
-                                                           float* __restrict__ gz_below = nullptr,
-                                                           float* __restrict__ gs_below = nullptr) {
-    __shared__ float red[4][64];
-    const int row = blockIdx.x;
-    if (row >= num_rows) return;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, q = lane & 15;
-    const int beg = row_ptr_s[row], end = row_ptr_s[row + 1];
-    float acc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int p = beg + wave; p < end; p += 4)
-        wg_accumulate<true>(acc, w_e + (size_t)eid_s[p] * 4096, gs + (size_t)dst_s[p] * 64, g, q);
-    if (root != nullptr && wave == ((end - beg) & 3)) wg_accumulate<false>(acc, root, gz + (size_t)row * 64, g, q);
-    // reduce over the 16 q-lanes of each group: xor 1,2,4,8
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = acc[r];
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        acc[r] = v;
-    }
-    if (q == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave][16 * g + r] = acc[r];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        const size_t at = (size_t)row * 64 + tid;
-        if (y_below != nullptr) {
-            const bool on = y_below[at] > 0.f;
-            gz_below[at] = on ? v : 0.f;
-            gs_below[at] = on ? v * inv_deg[row] : 0.f;
-        } else {
-            g_prev[at] = v;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- conv backward: d root, d bias
-// d root[i][o] (+)= sum_{l, r} x_l[r][i] * gz_l[r][o];  d bias[o] (+)= sum_{l, r} gz_l[r][o]
-// x, gz: [L, R, 64] stacked layers.  Block b takes a slice of the L*R rows -> partials, then reduce.
-__device__ __forceinline__ void bwd_root_slice(const float* __restrict__ x, const float* __restrict__ gz, long long r0, long long r1,
-                                               int slot, float* __restrict__ part_root, float* __restrict__ part_bias) {
-    __shared__ float xs[64][65], gsx[64][65];
-    const int tid = threadIdx.x;
-    const int i0 = (tid >> 4) * 4, o0 = (tid & 15) * 4;    // 4x4 outputs per thread
-    float acc[4][4] = {};
-    float bsum = 0.f;
-    for (long long rb = r0; rb < r1; rb += 64) {
-        __syncthreads();
-        for (int t = tid; t < 64 * 64; t += 256) {
-            const int rr = t >> 6, c = t & 63;
-            const bool ok = rb + rr < r1;
-            xs[rr][c] = ok ? x[(rb + rr) * 64 + c] : 0.f;
-            gsx[rr][c] = ok ? gz[(rb + rr) * 64 + c] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int rr = 0; rr < 64; ++rr) {
-            float xv[4], gv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) { xv[a] = xs[rr][i0 + a]; gv[a] = gsx[rr][o0 + a]; }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = fmaf(xv[a], gv[b], acc[a][b]);
-        }
-        if (tid < 64)
-            for (int rr = 0; rr < 64; ++rr) bsum += gsx[rr][tid];
-    }
-    float* pr = part_root + (size_t)slot * 4096;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) pr[(i0 + a) * 64 + o0 + b] = acc[a][b];
-    if (tid < 64) part_bias[(size_t)slot * 64 + tid] = bsum;
-}
-
-__global__ __launch_bounds__(256) void nnconv_bwd_root_kernel(const float* __restrict__ x, const float* __restrict__ gz,
-                                                              long long rows, long long slice_rows,
-                                                              float* __restrict__ part_root,
-                                                              float* __restrict__ part_bias) {
-    const long long r0 = (long long)blockIdx.x * slice_rows;
-    long long r1 = r0 + slice_rows;
-    if (r1 > rows) r1 = rows;
-    bwd_root_slice(x, gz, r0, r1, blockIdx.x, part_root, part_bias);
-}
-
-__global__ __launch_bounds__(256) void nnconv_bwd_root_pair_kernel(const float* __restrict__ x, const float* __restrict__ gz,
-                                                                   long long rows_each, long long slice_rows, int per_half,
-                                                                   float* __restrict__ part_root, float* __restrict__ part_bias) {
-    const int half = (int)blockIdx.x / per_half, b = (int)blockIdx.x - half * per_half;
-    const long long base = (long long)half * rows_each;
-    const long long r0 = base + (long long)b * slice_rows;
-    long long r1 = r0 + slice_rows;
-    if (r1 > base + rows_each) r1 = base + rows_each;
-    bwd_root_slice(x, gz, r0, r1, blockIdx.x, part_root, part_bias);
-}
-
-// ---------------------------------------------------------------- conv backward: d W_e
-// dW_e[p][i][o] (+)= sum_l x_l[src[p]][i] * gs_l[dst[p]][o];  x, gs: [L, R, 64].  One wave per edge,
-// lane (g, q) owns rows 16g..16g+15 x columns 4q..4q+3 and writes them as 16 coalesced 16-B stores.
-__global__ __launch_bounds__(256) void nnconv_bwd_we_kernel(const float* __restrict__ x, const float* __restrict__ gs,
-                                                            const int* __restrict__ src, const int* __restrict__ dst,
-                                                            long long E, int L, long long layer_stride,
-                                                            float* __restrict__ dwe, int accumulate) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, q = lane & 15;
-    const long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= E) return;
-    const float* xs = x + (size_t)src[p] * 64 + 16 * g;
-    const float* gq = gs + (size_t)dst[p] * 64 + 4 * q;
-    float4 acc[16];
-    float* out = dwe + (size_t)p * 4096 + (16 * g) * 64 + 4 * q;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        acc[r] = accumulate ? *reinterpret_cast<const float4*>(out + r * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int l = 0; l < L; ++l) {
-        const float4 gv = *reinterpret_cast<const float4*>(gq + (size_t)l * layer_stride);
-        const float* xl = xs + (size_t)l * layer_stride;
-        const float4 x0 = *reinterpret_cast<const float4*>(xl), x1 = *reinterpret_cast<const float4*>(xl + 4);
-        const float4 x2 = *reinterpret_cast<const float4*>(xl + 8), x3 = *reinterpret_cast<const float4*>(xl + 12);
-        const float xv[16] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w,
-                              x2.x, x2.y, x2.z, x2.w, x3.x, x3.y, x3.z, x3.w};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            acc[r].x = fmaf(xv[r], gv.x, acc[r].x);
-            acc[r].y = fmaf(xv[r], gv.y, acc[r].y);
-            acc[r].z = fmaf(xv[r], gv.z, acc[r].z);
-            acc[r].w = fmaf(xv[r], gv.w, acc[r].w);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) *reinterpret_cast<float4*>(out + r * 64) = acc[r];
-}
-
 constexpr int kSlices = 16;      // fixed K-split of the A^T.B reductions (partials added in slice order)
 constexpr int kColSlices = 128;  // column sums: many more slices (the reduction is a pure stream)
 
@@ -696,128 +507,4 @@ extern "C" int mdno_transpose(const float* a, int rows, int cols, float* at, voi
     hipLaunchKernelGGL(transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a, at, rows, cols);
     return check_launch("mdno_transpose");
-}
-
-extern "C" int mdno_inv_degree(const int32_t* row_ptr, int rows, int aggr, float* inv, void* stream) {
-    MDNO_REQUIRE(row_ptr && inv && rows > 0, MDNO_EINVAL, "mdno_inv_degree: bad arguments");
-    hipLaunchKernelGGL(inv_degree_kernel, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       row_ptr, rows, aggr == MDNO_AGGR_MEAN ? 1 : 0, inv);
-    return check_launch("mdno_inv_degree");
-}
-
-extern "C" int mdno_nnconv_bwd_x(const float* gz, const float* gs, const int32_t* row_ptr_s, const int32_t* eid_s,
-                                 const int32_t* dst_s, int num_rows, const float* w_e, const float* root,
-                                 int Cin, int Cout, float* g_prev, void* stream) {
-    MDNO_REQUIRE(gz && gs && row_ptr_s && eid_s && dst_s && w_e && g_prev && num_rows > 0, MDNO_EINVAL,
-                 "mdno_nnconv_bwd_x: bad arguments");
-    MDNO_REQUIRE(Cin == 64 && Cout == 64, MDNO_EUNSUPPORTED, "mdno_nnconv_bwd_x: only 64x64 channels");
-    hipLaunchKernelGGL(nnconv_bwd_x_kernel, dim3(num_rows), dim3(256), 0, static_cast<hipStream_t>(stream), gz, gs,
-                       row_ptr_s, eid_s, dst_s, w_e, root, g_prev, num_rows);
-    return check_launch("mdno_nnconv_bwd_x");
-}
-
-// rows per workgroup of nnconv_bwd_root_kernel: 256 (four 64-row passes) — 1,024 left cfg4's 21,504 stacked
-// rows to 21 workgroups on 256 CUs (174 us per call); 128 moved the time into the serial slice sums
-constexpr long long kRootSliceRows = 256;
-
-extern "C" size_t mdno_nnconv_bwd_root_workspace_bytes(int64_t rows) {
-    const long long blocks = (rows + kRootSliceRows - 1) / kRootSliceRows;
-    return align_up((size_t)blocks * (4096 + 64) * sizeof(float), 256);
-}
-
-extern "C" int mdno_nnconv_bwd_root(const float* x, const float* gz, int64_t rows, int Cin, int Cout, float* d_root,
-                                    float* d_bias, int accumulate, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-    MDNO_REQUIRE(x && gz && rows > 0 && workspace, MDNO_EINVAL, "mdno_nnconv_bwd_root: bad arguments");
-    MDNO_REQUIRE(Cin == 64 && Cout == 64, MDNO_EUNSUPPORTED, "mdno_nnconv_bwd_root: only 64x64 channels");
-    MDNO_REQUIRE(workspace_bytes >= mdno_nnconv_bwd_root_workspace_bytes(rows), MDNO_EWORKSPACE,
-                 "mdno_nnconv_bwd_root: workspace");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long slice_rows = kRootSliceRows;
-    const int blocks = (int)((rows + slice_rows - 1) / slice_rows);
-    float* part_root = static_cast<float*>(workspace);
-    float* part_bias = part_root + (size_t)blocks * 4096;
-    hipLaunchKernelGGL(nnconv_bwd_root_kernel, dim3(blocks), dim3(256), 0, s, x, gz, (long long)rows, slice_rows,
-                       part_root, part_bias);
-    if (d_root)
-        launch_reduce_slices((const float*)part_root, blocks, 4096ll, d_root, accumulate, s);
-    if (d_bias)
-        launch_reduce_slices((const float*)part_bias, blocks, 64ll, d_bias, accumulate, s);
-    return check_launch("mdno_nnconv_bwd_root");
-}
-
-// conv1's and conv2's root / bias gradients in ONE launch: x, gz [2 * rows_each, 64], the first rows_each rows conv1's
-// stacked layers, the rest conv2's (they are adjacent in the training step's layer stack).  The slices of a half never
-// cross into the other, and each half's partial sums are the ones mdno_nnconv_bwd_root forms for it alone (same slice
-// boundaries, same order): bitwise the two single calls, one 36 us launch less per batch.
-extern "C" size_t mdno_nnconv_bwd_root_pair_workspace_bytes(int64_t rows_each) {
-    const long long blocks = 2 * ((rows_each + kRootSliceRows - 1) / kRootSliceRows);
-    return align_up((size_t)blocks * (4096 + 64) * sizeof(float), 256);
-}
-
-extern "C" int mdno_nnconv_bwd_root_pair(const float* x, const float* gz, int64_t rows_each, float* d_root1, float* d_bias1,
-                                         float* d_root2, float* d_bias2, void* workspace, size_t workspace_bytes, void* stream) {
-    MDNO_REQUIRE(x && gz && rows_each > 0 && workspace && d_root1 && d_bias1 && d_root2 && d_bias2, MDNO_EINVAL,
-                 "mdno_nnconv_bwd_root_pair: bad arguments");
-    MDNO_REQUIRE(workspace_bytes >= mdno_nnconv_bwd_root_pair_workspace_bytes(rows_each), MDNO_EWORKSPACE,
-                 "mdno_nnconv_bwd_root_pair: workspace");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int per_half = (int)((rows_each + kRootSliceRows - 1) / kRootSliceRows);
-    float* part_root = static_cast<float*>(workspace);
-    float* part_bias = part_root + (size_t)2 * per_half * 4096;
-    hipLaunchKernelGGL(nnconv_bwd_root_pair_kernel, dim3(2 * per_half), dim3(256), 0, s, x, gz, (long long)rows_each,
-                       (long long)kRootSliceRows, per_half, part_root, part_bias);
-    launch_reduce_slices((const float*)part_root, per_half, 4096ll, d_root1, 0, s);
-    launch_reduce_slices((const float*)part_root + (size_t)per_half * 4096, per_half, 4096ll, d_root2, 0, s);
-    launch_reduce_slices((const float*)part_bias, per_half, 64ll, d_bias1, 0, s);
-    launch_reduce_slices((const float*)part_bias + (size_t)per_half * 64, per_half, 64ll, d_bias2, 0, s);
-    return check_launch("mdno_nnconv_bwd_root_pair");
-}
-
-extern "C" int mdno_nnconv_bwd_we(const float* x, const float* gs, const int32_t* src, const int32_t* dst, int64_t E,
-                                  int layers, int64_t layer_stride, int Cin, int Cout, float* d_we, int accumulate,
-                                  void* stream) {
-    MDNO_REQUIRE(x && gs && src && dst && d_we && E > 0 && layers > 0, MDNO_EINVAL, "mdno_nnconv_bwd_we: bad arguments");
-    MDNO_REQUIRE(Cin == 64 && Cout == 64, MDNO_EUNSUPPORTED, "mdno_nnconv_bwd_we: only 64x64 channels");
-    hipLaunchKernelGGL(nnconv_bwd_we_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, gs, src, dst, (long long)E, layers, (long long)layer_stride,
-                       d_we, accumulate);
-    return check_launch("mdno_nnconv_bwd_we");
-}
-
-// ---------------------------------------------------------------- the conv applications of a training step as ONE call
-extern "C" int mdno_nnconv_chain_fwd(float* x_layers, const int32_t* row_ptr, const int32_t* src, int num_rows,
-                                     const float* w_e, const float* root1, const float* bias1, const float* root2,
-                                     const float* bias2, int depth, void* stream) {
-    MDNO_REQUIRE(x_layers && row_ptr && src && w_e && num_rows > 0 && depth > 0, MDNO_EINVAL,
-                 "mdno_nnconv_chain_fwd: bad arguments");
-    const size_t stride = (size_t)num_rows * 64;
-    for (int a = 1; a <= 2 * depth; ++a)
-        MDNO_TRY(mdno_nnconv_fwd(x_layers + (a - 1) * stride, row_ptr, src, num_rows, w_e, a <= depth ? root1 : root2,
-                                 a <= depth ? bias1 : bias2, 64, 64, MDNO_AGGR_MEAN, 1, x_layers + a * stride, stream));
-    return MDNO_OK;
-}
-
-extern "C" int mdno_nnconv_chain_bwd(const float* g_out, const float* x_layers, const float* inv_deg,
-                                     const int32_t* row_ptr_s, const int32_t* eid_s, const int32_t* dst_s, int num_rows,
-                                     const float* w_e, const float* root1, const float* root2, int depth, float* gz,
-                                     float* gs, float* g_in, void* stream) {
-    MDNO_REQUIRE(g_out && x_layers && inv_deg && row_ptr_s && eid_s && dst_s && w_e && gz && gs && g_in && num_rows > 0 &&
-                     depth > 0, MDNO_EINVAL, "mdno_nnconv_chain_bwd: bad arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int L = 2 * depth;
-    const size_t stride = (size_t)num_rows * 64;
-    MDNO_TRY(mdno_relu_bwd2(g_out, x_layers + L * stride, inv_deg, num_rows, 64, gz + (L - 1) * stride, gs + (L - 1) * stride,
-                            stream));
-    for (int a = L; a >= 1; --a) {
-        const float* root = a <= depth ? root1 : root2;
-        if (a > 1)
-            hipLaunchKernelGGL(nnconv_bwd_x_kernel, dim3(num_rows), dim3(256), 0, s, gz + (a - 1) * stride, gs + (a - 1) * stride,
-                               row_ptr_s, eid_s, dst_s, w_e, root, (float*)nullptr, num_rows, x_layers + (a - 1) * stride,
-                               inv_deg, gz + (a - 2) * stride, gs + (a - 2) * stride);
-        else
-            hipLaunchKernelGGL(nnconv_bwd_x_kernel, dim3(num_rows), dim3(256), 0, s, gz, gs, row_ptr_s, eid_s, dst_s, w_e, root,
-                               g_in, num_rows, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
-    }
-    return check_launch("mdno_nnconv_chain_bwd");
 }

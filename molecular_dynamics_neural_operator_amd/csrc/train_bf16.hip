@@ -5,15 +5,15 @@
 // block is a single bf16 x bf16 MFMA product with fp32 accumulation; the parameters stay fp32 (master
 // weights, cast per call), as do the node features, the conv outputs and every reduction.  That halves
 // the two E x 16 KiB tensors of the fp32 path (train.hip), takes the weight-gradient products A^T.B
-// off the fp32 MFMA (1/16 of the bf16 rate) and halves what the conv kernels stream.
+// off the fp32 MFMA (1/16 of the bf16 rate) and halves what the conv kernels stream.  This file holds the
+// Linear-layer ops on bf16 operands; the conv kernels reading bf16 W_e / writing bf16 dW_e are train_conv.hip.
 //
 //   cast_bf16            fp32 -> bf16 (RNE), row-major
 //   gemm_nt_bf16         C = act(A . W^T + b)      A bf16 [rows,K], W bf16 [N,K]      -> bf16 or fp32
 //   gemm_tn_bf16         C = A^T . B over rows     A bf16 [rows,n1], B bf16 [rows,n2] -> fp32 [n1,n2]
-//   nnconv64_bf16w_*     the conv forward / input-gradient kernels of nnconv.hip / train.hip reading bf16 W_e
-//   nnconv_bwd_we_bf16   dW_e written as bf16
 //   relu_bwd_bf16, colsum_bf16   the elementwise / reduction ops on bf16 operands
 // Reductions keep fixed-order partial sums (no float atomics): gradients are bitwise reproducible.
+#include "bf16.h"
 #include "kernels.h"
 #include "reduce.h"
 
@@ -22,18 +22,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
-__device__ __forceinline__ float4 ld4_bf16(const __bf16* p) {      // 4 consecutive bf16 -> float4 (8-B load)
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                       __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
-}
-__device__ __forceinline__ uint2 pack4_bf16(float a, float b, float c, float d) {
-    const bf16x4 v = {(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
-    return __builtin_bit_cast(uint2, v);
-}
 
 // ---------------------------------------------------------------- cast
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ in, long long n4,
@@ -329,156 +317,6 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const __bf16* __restr
     }
 }
 
-// ---------------------------------------------------------------- conv forward, bf16 W_e
-// nnconv64_row_kernel (nnconv.hip) with 8-B loads of four bf16: same lane map (lane (g,q) owns input rows
-// 16g..16g+15 x output columns 4q..4q+3), same 16 summation chains, fp32 accumulation.
-__device__ __forceinline__ void fma4(float4& a, float s, const float4& w) {
-    a.x = fmaf(s, w.x, a.x); a.y = fmaf(s, w.y, a.y); a.z = fmaf(s, w.z, a.z); a.w = fmaf(s, w.w, a.w);
-}
-__device__ __forceinline__ float4 reduce_over_g(float4 a) {
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        a.x += __shfl_xor(a.x, o); a.y += __shfl_xor(a.y, o); a.z += __shfl_xor(a.z, o); a.w += __shfl_xor(a.w, o);
-    }
-    return a;
-}
-template <class WT>
-__device__ __forceinline__ float4 ldw4(const WT* p);
-template <>
-__device__ __forceinline__ float4 ldw4<float>(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// (W_e is read once per conv application and is far larger than the caches: streamed past them)
-template <>
-__device__ __forceinline__ float4 ldw4<__bf16>(const __bf16* p) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2 u = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
-    return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                       __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
-}
-
-// (W first: its address does not wait for src[p], which the x row's does; all twenty loads in flight before the
-// first FMA waits — a batch row has ~12 edges, one per wave, so a workgroup's life is its chain of round trips)
-template <class WT>
-__device__ __forceinline__ void edge_acc64(float4& acc, const float* __restrict__ xrow, const WT* __restrict__ wmat,
-                                           int g, int q) {
-    const WT* wp = wmat + (16 * g) * 64 + 4 * q;
-    float4 w[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) w[r] = ldw4<WT>(wp + r * 64);
-    const float* xp = xrow + 16 * g;
-    const float4 x0 = *reinterpret_cast<const float4*>(xp), x1 = *reinterpret_cast<const float4*>(xp + 4);
-    const float4 x2 = *reinterpret_cast<const float4*>(xp + 8), x3 = *reinterpret_cast<const float4*>(xp + 12);
-    __builtin_amdgcn_sched_barrier(0);
-    fma4(acc, x0.x, w[0]);  fma4(acc, x0.y, w[1]);  fma4(acc, x0.z, w[2]);  fma4(acc, x0.w, w[3]);
-    fma4(acc, x1.x, w[4]);  fma4(acc, x1.y, w[5]);  fma4(acc, x1.z, w[6]);  fma4(acc, x1.w, w[7]);
-    fma4(acc, x2.x, w[8]);  fma4(acc, x2.y, w[9]);  fma4(acc, x2.z, w[10]); fma4(acc, x2.w, w[11]);
-    fma4(acc, x3.x, w[12]); fma4(acc, x3.y, w[13]); fma4(acc, x3.z, w[14]); fma4(acc, x3.w, w[15]);
-}
-
-// WAVES = 16: a wave per summation chain; WAVES = 4: a wave owns chains w, w+4, w+8, w+12, one after the other (same
-// chains, same order of additions: same bits) — four times as many workgroups resident per CU
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void nnconv64_bf16w_kernel(const float* __restrict__ x, const int* __restrict__ row_ptr,
-                                                              const int* __restrict__ src,
-                                                              const __bf16* __restrict__ w_e,
-                                                              const float* __restrict__ root,
-                                                              const float* __restrict__ bias, float* __restrict__ y,
-                                                              int num_rows, int aggr, int relu) {
-    __shared__ float red[16][64];
-    __shared__ float rootred[64];
-    const int row = blockIdx.x;
-    if (row >= num_rows) return;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, q = lane & 15;
-    const int beg = row_ptr[row], end = row_ptr[row + 1], deg = end - beg;
-#pragma unroll
-    for (int u = 0; u < 16 / WAVES; ++u) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int p = beg + wave + u * WAVES; p < end; p += 16)
-            edge_acc64<__bf16>(acc, x + (size_t)src[p] * 64, w_e + (size_t)p * 4096, g, q);
-        acc = reduce_over_g(acc);
-        if (lane < 16) *reinterpret_cast<float4*>(&red[wave + u * WAVES][4 * lane]) = acc;
-    }
-    const bool root_wave = root != nullptr && wave == (deg % WAVES);
-    float4 racc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (root_wave) edge_acc64<float>(racc, x + (size_t)row * 64, root, g, q);
-    racc = reduce_over_g(racc);
-    if (root_wave && lane < 16) *reinterpret_cast<float4*>(&rootred[4 * lane]) = racc;
-    __syncthreads();
-    if (tid < 64) {
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) s += red[c][tid];
-        if (aggr == MDNO_AGGR_MEAN) s = s / (float)(deg > 1 ? deg : 1);
-        if (root != nullptr) s += rootred[tid];
-        if (bias != nullptr) s += bias[tid];
-        if (relu) s = relu_f(s);
-        y[(size_t)row * 64 + tid] = s;
-    }
-}
-
-// ---------------------------------------------------------------- conv backward wrt the input, bf16 W_e
-// nnconv_bwd_x_kernel (train.hip): g_prev[r] = gz[r] . root^T + sum_{e: src e = r} W_e . gs[dst e]
-template <class WT>
-__device__ __forceinline__ void wg_acc(float (&acc)[16], const WT* __restrict__ wmat, const float* __restrict__ gvec,
-                                       int g, int q) {
-    const float4 gq = *reinterpret_cast<const float4*>(gvec + 4 * q);
-    const WT* wp = wmat + (16 * g) * 64 + 4 * q;
-    float4 w[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) w[r] = ldw4<WT>(wp + r * 64);
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        acc[r] = fmaf(w[r].x, gq.x, fmaf(w[r].y, gq.y, fmaf(w[r].z, gq.z, fmaf(w[r].w, gq.w, acc[r]))));
-}
-
-// y_below != NULL: the gradient leaves through the ReLU of the application below (whose output is y_below) —
-// gz_below = g_prev * (y_below > 0), gs_below = gz_below * inv_deg[row] are written instead of g_prev: what
-// mdno_relu_bwd2 would make of g_prev in a launch of its own, same arithmetic
-__global__ __launch_bounds__(256) void nnconv_bwd_x_bf16w_kernel(const float* __restrict__ gz, const float* __restrict__ gs,
-                                                                 const int* __restrict__ row_ptr_s,
-                                                                 const int* __restrict__ eid_s,
-                                                                 const int* __restrict__ dst_s,
-                                                                 const __bf16* __restrict__ w_e,
-                                                                 const float* __restrict__ root,
-                                                                 float* __restrict__ g_prev, int num_rows,
-                                                                 const float* __restrict__ y_below = nullptr,
-                                                                 const float* __restrict__ inv_deg = nullptr,
-                                                                 float* __restrict__ gz_below = nullptr,
-                                                                 float* __restrict__ gs_below = nullptr) {
-    __shared__ float red[4][64];
-    const int row = blockIdx.x;
-    if (row >= num_rows) return;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, q = lane & 15;
-    const int beg = row_ptr_s[row], end = row_ptr_s[row + 1];
-    float acc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int p = beg + wave; p < end; p += 4)
-        wg_acc<__bf16>(acc, w_e + (size_t)eid_s[p] * 4096, gs + (size_t)dst_s[p] * 64, g, q);
-    if (root != nullptr && wave == ((end - beg) & 3)) wg_acc<float>(acc, root, gz + (size_t)row * 64, g, q);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = acc[r];
-        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-        acc[r] = v;
-    }
-    if (q == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave][16 * g + r] = acc[r];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        const size_t at = (size_t)row * 64 + tid;
-        if (y_below != nullptr) {
-            const bool on = y_below[at] > 0.f;
-            gz_below[at] = on ? v : 0.f;
-            gs_below[at] = on ? v * inv_deg[row] : 0.f;
-        } else {
-            g_prev[at] = v;
-        }
-    }
-}
-
 // ---------------------------------------------------------------- column sums + A^T.B for a few fp32 columns
 // colsum[n] = sum_r a[r][n] and atb[n][j] = sum_r a[r][n] * b[r][j] (j < KB <= 8) in ONE pass over a bf16 [rows,n]:
 // the bias and weight gradient of the edge-MLP's FIRST layer (b = the fp32 edge attributes, 6 columns), which were a
@@ -552,181 +390,6 @@ __global__ __launch_bounds__(256) void colsum_atb_finish_kernel(const float* __r
     colsum[c] = red[c];
 #pragma unroll
     for (int m = 0; m < KB; ++m) atb[(size_t)c * KB + m] = red[(size_t)(m + 1) * n + c];
-}
-
-// ---------------------------------------------------------------- d W_e as bf16
-// nnconv_bwd_we_kernel (train.hip) with the result rounded once, at the end, and written as 8-B stores
-__global__ __launch_bounds__(256) void nnconv_bwd_we_bf16_kernel(const float* __restrict__ x, const float* __restrict__ gs,
-                                                                 const int* __restrict__ src, const int* __restrict__ dst,
-                                                                 long long E, int L, long long layer_stride,
-                                                                 __bf16* __restrict__ dwe) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, q = lane & 15;
-    const long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= E) return;
-    const float* xs = x + (size_t)src[p] * 64 + 16 * g;
-    const float* gq = gs + (size_t)dst[p] * 64 + 4 * q;
-    float4 acc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int l = 0; l < L; ++l) {
-        const float4 gv = *reinterpret_cast<const float4*>(gq + (size_t)l * layer_stride);
-        const float* xl = xs + (size_t)l * layer_stride;
-        const float4 x0 = *reinterpret_cast<const float4*>(xl), x1 = *reinterpret_cast<const float4*>(xl + 4);
-        const float4 x2 = *reinterpret_cast<const float4*>(xl + 8), x3 = *reinterpret_cast<const float4*>(xl + 12);
-        const float xv[16] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w,
-                              x2.x, x2.y, x2.z, x2.w, x3.x, x3.y, x3.z, x3.w};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            acc[r].x = fmaf(xv[r], gv.x, acc[r].x); acc[r].y = fmaf(xv[r], gv.y, acc[r].y);
-            acc[r].z = fmaf(xv[r], gv.z, acc[r].z); acc[r].w = fmaf(xv[r], gv.w, acc[r].w);
-        }
-    }
-    __bf16* out = dwe + (size_t)p * 4096 + (16 * g) * 64 + 4 * q;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) *reinterpret_cast<uint2*>(out + r * 64) = pack4_bf16(acc[r].x, acc[r].y, acc[r].z, acc[r].w);
-}
-
-// ---------------------------------------------------------------- d W_e as bf16 + its column sums, on the matrix pipe
-// dW_e[p] = sum_l gs_l[dst p] (x) x_l[src p] is a [64 x L] . [L x 64] product per edge: with L <= 16 ONE k-step of
-// v_mfma_f32_32x32x16_bf16 per 32 x 32 quadrant.  The kernel above spends 768 FMAs per lane and edge on it (115 us at
-// cfg4, twice what writing the 358 MB takes); here both fp32 operands are split exactly into three bf16 planes in
-// registers and the six leading plane products accumulated in fp32 (fp32 accuracy, as everywhere in this library):
-// 24 MFMAs per edge.  One wave per edge at a time, edges p = wave, wave + W, ..: the next edge's 32 operand words are
-// fetched before this edge's MFMAs.
-//   A = G (rows o): lane (l31, h) holds gs_l[dst][32 ob + l31], l = 8 h .. 8 h + 7;  B = X (columns i): x_l[src][32 ib + l31]
-//   acc[ob][ib][e] = dW_e[i = 32 ib + l31][o = 32 ob + (e & 3) + 8 (e >> 2) + 4 h]: four consecutive o -> one 8-B LDS write
-// and the rounded tile goes out through LDS row by row: 16 B per lane, 1 KiB contiguous per store instruction.
-// The column sums (the last layer's bias gradient: sum over edges of the ROUNDED dW_e, what mdno_colsum_bf16 computes
-// from the stored tensor in a second pass over its 358 MB) are taken on the way: every lane owns 64 fixed (i, o)
-// positions of the tile, adds each edge's rounded values in edge order, the four waves of a workgroup are added in wave
-// order through LDS and the workgroups by reduce_slices: fixed association, no atomics.
-// BF16 = false: the fp32 training path's dW_e (train.hip's nnconv_bwd_we_kernel: 180 us + a 96 us column-sum pass over
-// 716 MB at cfg4) through the same loop, the tile staged as fp32 and its column sums taken from the stored values.
-constexpr int WE_WGS = 512;                              // workgroups of the launch (whatever E: the association of the sums is fixed)
-template <bool BF16> struct WeTile {
-    static constexpr int ROW = BF16 ? 136 : 272;         // LDS bytes per row of 64 outputs (+8 / +16: the 32 rows a write touches spread over the banks)
-    static constexpr int BYTES = 64 * ROW;               // 8,704 / 17,408 B per wave
-};
-
-template <bool BF16>
-__global__ __launch_bounds__(256, 2) void nnconv_bwd_we_mfma_kernel(const float* __restrict__ x, const float* __restrict__ gs,
-                                                                   const int* __restrict__ src, const int* __restrict__ dst,
-                                                                   long long E, int L, long long layer_stride,
-                                                                   void* __restrict__ dwe_, float* __restrict__ part) {
-    constexpr int ROW = WeTile<BF16>::ROW, TILE = WeTile<BF16>::BYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * TILE > 4096 * 4 ? 4 * TILE : 4096 * 4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    // read-back role: 16 B per lane; bf16: 8 rows x 128 B per pass (8 passes), fp32: 4 rows x 256 B (16 passes)
-    constexpr int PASSES = BF16 ? 8 : 16, RPP = 64 / PASSES, PER = BF16 ? 8 : 4;
-    const int rr = BF16 ? lane >> 3 : lane >> 4, rc = BF16 ? lane & 7 : lane & 15;
-    unsigned char* tile = lds + wave * TILE;
-    const long long W = (long long)gridDim.x * 4;
-    float cs[64];
-#pragma unroll
-    for (int j = 0; j < 64; ++j) cs[j] = 0.f;
-    float ga[2][8], xb[2][8];                            // this edge's operand words; next edge's while the MFMAs run
-    // (every load unconditional — a layer past L re-reads layer 0 and is zeroed by a select — so that the loop body is
-    // straight-line code: with `on ? load : 0` the compiler built a branch around each of the 32 loads)
-    auto fetch = [&](long long p, float (&g_)[2][8], float (&x_)[2][8]) {
-        const float* gq = gs + (size_t)dst[p] * 64 + l31;
-        const float* xq = x + (size_t)src[p] * 64 + l31;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int l = 8 * h + j;
-            const size_t off = (size_t)(l < L ? l : 0) * layer_stride;
-            g_[0][j] = gq[off];
-            g_[1][j] = gq[off + 32];
-            x_[0][j] = xq[off];
-            x_[1][j] = xq[off + 32];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (8 * h + j >= L) { g_[0][j] = 0.f; g_[1][j] = 0.f; x_[0][j] = 0.f; x_[1][j] = 0.f; }
-    };
-    auto split3 = [](const float (&v)[8], bf16x8 (&pl)[3]) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const __bf16 hi = (__bf16)v[j];
-            const float r1 = v[j] - (float)hi;
-            const __bf16 mid = (__bf16)r1;
-            const __bf16 lo = (__bf16)(r1 - (float)mid);
-            pl[0][j] = hi; pl[1][j] = mid; pl[2][j] = lo;
-        }
-    };
-    long long p = (long long)blockIdx.x * 4 + wave;
-    if (p < E) fetch(p, ga, xb);
-    for (; p < E; p += W) {
-        bf16x8 a[2][3], b[2][3];
-        split3(ga[0], a[0]); split3(ga[1], a[1]);
-        split3(xb[0], b[0]); split3(xb[1], b[1]);
-        if (p + W < E) fetch(p + W, ga, xb);
-        __builtin_amdgcn_sched_barrier(0);
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib) {
-                const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][1], b[ib][1], zero, 0, 0, 0);      // (C = inline 0)
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][2], b[ib][0], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][2], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][1], b[ib][0], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][1], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][0], acc[ob][ib], 0, 0, 0);
-            }
-        // tile -> LDS [i][o] (a wave's own tile: no workgroup barrier); four consecutive o per write
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x16& c = acc[ob][ib];
-                    unsigned char* wp = tile + (32 * ib + l31) * ROW + (32 * ob + 8 * g + 4 * h) * (BF16 ? 2 : 4);
-                    if (BF16) *reinterpret_cast<uint2*>(wp) = pack4_bf16(c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]);
-                    else *reinterpret_cast<float4*>(wp) = make_float4(c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]);
-                }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int ps = 0; ps < PASSES; ++ps) {
-            const unsigned char* rp = tile + (RPP * ps + rr) * ROW + rc * 16;
-            const size_t at = (size_t)p * 4096 + (RPP * ps + rr) * 64 + PER * rc;
-            if (BF16) {
-                const uint2 u0 = *reinterpret_cast<const uint2*>(rp), u1 = *reinterpret_cast<const uint2*>(rp + 8);
-                *reinterpret_cast<uint4*>(static_cast<__bf16*>(dwe_) + at) = make_uint4(u0.x, u0.y, u1.x, u1.y);
-                const unsigned w4[4] = {u0.x, u0.y, u1.x, u1.y};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    cs[8 * ps + 2 * j] += __builtin_bit_cast(float, w4[j] << 16);
-                    cs[8 * ps + 2 * j + 1] += __builtin_bit_cast(float, w4[j] & 0xffff0000u);
-                }
-            } else {
-                const float4 v = *reinterpret_cast<const float4*>(rp);
-                *reinterpret_cast<float4*>(static_cast<float*>(dwe_) + at) = v;
-                cs[4 * ps] += v.x; cs[4 * ps + 1] += v.y; cs[4 * ps + 2] += v.z; cs[4 * ps + 3] += v.w;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();      // the tile is rewritten by the next edge
-    }
-    // column sums: the four waves in wave order through LDS -> part[workgroup][4096]
-    float* red = reinterpret_cast<float*>(lds);
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int ps = 0; ps < PASSES; ++ps)
-#pragma unroll
-                for (int j = 0; j < PER; ++j) {
-                    const int idx = (RPP * ps + rr) * 64 + PER * rc + j;
-                    red[idx] = w == 0 ? cs[PER * ps + j] : red[idx] + cs[PER * ps + j];
-                }
-        }
-        __syncthreads();
-    }
-    float* po = part + (size_t)blockIdx.x * 4096;
-    for (int i = threadIdx.x; i < 1024; i += 256)
-        reinterpret_cast<float4*>(po)[i] = reinterpret_cast<const float4*>(red)[i];
 }
 
 // ---------------------------------------------------------------- elementwise / reductions on bf16
@@ -891,72 +554,6 @@ extern "C" int mdno_gemm_atb_bf16(const void* a, const void* b, int64_t rows, in
     return check_launch("gemm_tn_bf16_kernel");
 }
 
-extern "C" int mdno_nnconv_bf16w_fwd(const float* x, const int32_t* row_ptr, const int32_t* src, int num_rows,
-                                     const void* w_e, const float* root, const float* bias, int aggr, int relu,
-                                     float* y, void* stream) {
-    MDNO_REQUIRE(x && row_ptr && src && w_e && y && num_rows > 0, MDNO_EINVAL, "mdno_nnconv_bf16w_fwd: bad arguments");
-    MDNO_REQUIRE(aggr == MDNO_AGGR_ADD || aggr == MDNO_AGGR_MEAN, MDNO_EUNSUPPORTED, "mdno_nnconv_bf16w_fwd: aggr %d", aggr);
-    // many short rows (a training batch: 3,584 rows of ~12 edges): four waves per row keep four times as many rows
-    // resident per CU — 30.4k instead of 29.5k samples/s on cfg4; few rows: a wave per chain
-    if (num_rows >= 2048)
-        hipLaunchKernelGGL(nnconv64_bf16w_kernel<4>, dim3(num_rows), dim3(256), 0, static_cast<hipStream_t>(stream), x, row_ptr,
-                           src, static_cast<const __bf16*>(w_e), root, bias, y, num_rows, aggr, relu);
-    else
-        hipLaunchKernelGGL(nnconv64_bf16w_kernel<16>, dim3(num_rows), dim3(1024), 0, static_cast<hipStream_t>(stream), x,
-                           row_ptr, src, static_cast<const __bf16*>(w_e), root, bias, y, num_rows, aggr, relu);
-    return check_launch("nnconv64_bf16w_kernel");
-}
-
-extern "C" int mdno_nnconv_bwd_x_bf16w(const float* gz, const float* gs, const int32_t* row_ptr_s, const int32_t* eid_s,
-                                       const int32_t* dst_s, int num_rows, const void* w_e, const float* root,
-                                       float* g_prev, void* stream) {
-    MDNO_REQUIRE(gz && gs && row_ptr_s && eid_s && dst_s && w_e && g_prev && num_rows > 0, MDNO_EINVAL,
-                 "mdno_nnconv_bwd_x_bf16w: bad arguments");
-    hipLaunchKernelGGL(nnconv_bwd_x_bf16w_kernel, dim3(num_rows), dim3(256), 0, static_cast<hipStream_t>(stream), gz, gs,
-                       row_ptr_s, eid_s, dst_s, static_cast<const __bf16*>(w_e), root, g_prev, num_rows);
-    return check_launch("nnconv_bwd_x_bf16w_kernel");
-}
-
-extern "C" int mdno_nnconv_bwd_we_bf16(const float* x, const float* gs, const int32_t* src, const int32_t* dst, int64_t E,
-                                       int L, int64_t layer_stride, void* d_we, void* stream) {
-    MDNO_REQUIRE(x && gs && src && dst && d_we && E >= 0 && L > 0, MDNO_EINVAL, "mdno_nnconv_bwd_we_bf16: bad arguments");
-    if (E == 0) return MDNO_OK;
-    hipLaunchKernelGGL(nnconv_bwd_we_bf16_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, gs, src, dst, (long long)E, L, (long long)layer_stride,
-                       static_cast<__bf16*>(d_we));
-    return check_launch("nnconv_bwd_we_bf16_kernel");
-}
-
-extern "C" size_t mdno_nnconv_bwd_we_colsum_workspace_bytes(void) { return align_up((size_t)WE_WGS * 4096 * sizeof(float), 256); }
-extern "C" size_t mdno_nnconv_bwd_we_bf16_colsum_workspace_bytes(void) { return mdno_nnconv_bwd_we_colsum_workspace_bytes(); }
-
-template <bool BF16>
-static int bwd_we_colsum(const char* what, const float* x, const float* gs, const int32_t* src, const int32_t* dst, int64_t E, int L,
-                         int64_t layer_stride, void* d_we, float* colsum, void* workspace, size_t workspace_bytes, void* stream) {
-    MDNO_REQUIRE(x && gs && src && dst && d_we && colsum && workspace && E >= 0 && L > 0, MDNO_EINVAL, "%s: bad arguments", what);
-    MDNO_REQUIRE(L <= 16, MDNO_EUNSUPPORTED, "%s: %d conv applications (one MFMA k-step holds 16)", what, L);
-    MDNO_REQUIRE(workspace_bytes >= mdno_nnconv_bwd_we_colsum_workspace_bytes(), MDNO_EWORKSPACE, "%s: workspace too small", what);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(nnconv_bwd_we_mfma_kernel<BF16>, dim3(WE_WGS), dim3(256), 0, s, x, gs, src, dst, (long long)E, L,
-                       (long long)layer_stride, d_we, static_cast<float*>(workspace));
-    launch_reduce_slices(static_cast<const float*>(workspace), WE_WGS, 4096, colsum, 0, s);
-    return check_launch(what);
-}
-
-extern "C" int mdno_nnconv_bwd_we_bf16_colsum(const float* x, const float* gs, const int32_t* src, const int32_t* dst, int64_t E,
-                                              int L, int64_t layer_stride, void* d_we, float* colsum, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-    return bwd_we_colsum<true>("mdno_nnconv_bwd_we_bf16_colsum", x, gs, src, dst, E, L, layer_stride, d_we, colsum, workspace,
-                               workspace_bytes, stream);
-}
-
-extern "C" int mdno_nnconv_bwd_we_colsum(const float* x, const float* gs, const int32_t* src, const int32_t* dst, int64_t E, int L,
-                                         int64_t layer_stride, float* d_we, float* colsum, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
-    return bwd_we_colsum<false>("mdno_nnconv_bwd_we_colsum", x, gs, src, dst, E, L, layer_stride, d_we, colsum, workspace,
-                                workspace_bytes, stream);
-}
-
 extern "C" int mdno_relu_bwd_bf16(const float* g, const void* y, int64_t rows, int n, int out_bf16, void* out,
                                   void* stream) {
     MDNO_REQUIRE(g && y && out && rows >= 0 && n % 4 == 0, MDNO_EINVAL, "mdno_relu_bwd_bf16: bad arguments");
@@ -986,46 +583,6 @@ extern "C" int mdno_colsum_bf16(const void* a, int64_t rows, int n, float* out, 
                        static_cast<float*>(workspace), (long long)rows, n, slice_rows);
     launch_reduce_slices(static_cast<const float*>(workspace), kColSlicesB, (long long)n, out, 0, s);
     return check_launch("colsum_bf16_kernel");
-}
-
-// ---------------------------------------------------------------- the conv applications of a training step as ONE call
-extern "C" int mdno_nnconv_chain_bf16w_fwd(float* x_layers, const int32_t* row_ptr, const int32_t* src, int num_rows,
-                                           const void* w_e, const float* root1, const float* bias1, const float* root2,
-                                           const float* bias2, int depth, void* stream) {
-    MDNO_REQUIRE(x_layers && row_ptr && src && w_e && num_rows > 0 && depth > 0, MDNO_EINVAL,
-                 "mdno_nnconv_chain_bf16w_fwd: bad arguments");
-    const size_t stride = (size_t)num_rows * 64;
-    for (int a = 1; a <= 2 * depth; ++a)
-        MDNO_TRY(mdno_nnconv_bf16w_fwd(x_layers + (a - 1) * stride, row_ptr, src, num_rows, w_e, a <= depth ? root1 : root2,
-                                       a <= depth ? bias1 : bias2, MDNO_AGGR_MEAN, 1, x_layers + a * stride, stream));
-    return MDNO_OK;
-}
-
-extern "C" int mdno_nnconv_chain_bf16w_bwd(const float* g_out, const float* x_layers, const float* inv_deg,
-                                           const int32_t* row_ptr_s, const int32_t* eid_s, const int32_t* dst_s,
-                                           int num_rows, const void* w_e, const float* root1, const float* root2, int depth,
-                                           float* gz, float* gs, float* g_in, void* stream) {
-    MDNO_REQUIRE(g_out && x_layers && inv_deg && row_ptr_s && eid_s && dst_s && w_e && gz && gs && g_in && num_rows > 0 &&
-                     depth > 0, MDNO_EINVAL, "mdno_nnconv_chain_bf16w_bwd: bad arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int L = 2 * depth;
-    const size_t stride = (size_t)num_rows * 64;
-    // the gradient enters through the ReLU of application L; every later ReLU is the epilogue of the kernel above it
-    MDNO_TRY(mdno_relu_bwd2(g_out, x_layers + L * stride, inv_deg, num_rows, 64, gz + (L - 1) * stride, gs + (L - 1) * stride,
-                            stream));
-    for (int a = L; a >= 1; --a) {
-        const float* root = a <= depth ? root1 : root2;
-        if (a > 1)
-            hipLaunchKernelGGL(nnconv_bwd_x_bf16w_kernel, dim3(num_rows), dim3(256), 0, s, gz + (a - 1) * stride,
-                               gs + (a - 1) * stride, row_ptr_s, eid_s, dst_s, static_cast<const __bf16*>(w_e), root,
-                               (float*)nullptr, num_rows, x_layers + (a - 1) * stride, inv_deg, gz + (a - 2) * stride,
-                               gs + (a - 2) * stride);
-        else
-            hipLaunchKernelGGL(nnconv_bwd_x_bf16w_kernel, dim3(num_rows), dim3(256), 0, s, gz, gs, row_ptr_s, eid_s, dst_s,
-                               static_cast<const __bf16*>(w_e), root, g_in, num_rows, (const float*)nullptr,
-                               (const float*)nullptr, (float*)nullptr, (float*)nullptr);
-    }
-    return check_launch("mdno_nnconv_chain_bf16w_bwd");
 }
 
 extern "C" size_t mdno_colsum_atb_bf16_workspace_bytes(int n, int kb) {

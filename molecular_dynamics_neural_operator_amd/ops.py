@@ -505,15 +505,20 @@ def permute_rows(x: torch.Tensor, perm: torch.Tensor, rows: int) -> torch.Tensor
     return out
 
 
+def _nnconv_bwd_x(gz: torch.Tensor, gs: torch.Tensor, by_src: CSRGraph, w_e: torch.Tensor, root, bf16w: bool) -> torch.Tensor:
+    """g_prev [R,64] of one conv application; `bf16w`: w_e is stored in bf16 (the entry takes no channel counts)."""
+    lib = _lib.load()
+    name = "mdno_nnconv_bwd_x_bf16w" if bf16w else "mdno_nnconv_bwd_x"
+    g_prev = torch.empty_like(gz)
+    check(getattr(lib, name)(ptr(gz), ptr(gs), ptr(by_src.row_ptr), ptr(by_src.perm), ptr(by_src.src), gz.shape[0],
+                             ptr(_bf16(w_e) if bf16w else w_e), ptr(f32(root)) if root is not None else None,
+                             *(() if bf16w else (64, 64)), ptr(g_prev), stream_ptr(gz.device)), name)
+    return g_prev
+
+
 def nnconv_bwd_x(gz: torch.Tensor, gs: torch.Tensor, by_src: CSRGraph, w_e: torch.Tensor,
                  root: Optional[torch.Tensor]) -> torch.Tensor:
-    lib = _lib.load()
-    rows = gz.shape[0]
-    g_prev = torch.empty_like(gz)
-    check(lib.mdno_nnconv_bwd_x(ptr(gz), ptr(gs), ptr(by_src.row_ptr), ptr(by_src.perm), ptr(by_src.src), rows,
-                                ptr(w_e), ptr(f32(root)) if root is not None else None, 64, 64, ptr(g_prev),
-                                stream_ptr(gz.device)), "mdno_nnconv_bwd_x")
-    return g_prev
+    return _nnconv_bwd_x(gz, gs, by_src, w_e, root, bf16w=False)
 
 
 def nnconv_bwd_root(x: torch.Tensor, gz: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -545,23 +550,33 @@ def nnconv_bwd_root_pair(x_layers: torch.Tensor, gz_layers: torch.Tensor):
     return tuple(outs)
 
 
-def nnconv_bwd_we(x_layers: torch.Tensor, gs_layers: torch.Tensor, graph: CSRGraph, with_colsum: bool = False):
-    """x_layers, gs_layers [L,R,64] -> d_we [E,4096]; `with_colsum`: also its column sums from the same pass (up to 16
-    conv applications: the matrix-pipe kernel; beyond, the FMA kernel and `ops.colsum`)."""
+def _nnconv_bwd_we(x_layers: torch.Tensor, gs_layers: torch.Tensor, graph: CSRGraph, with_colsum: bool, bf16: bool):
+    """x_layers, gs_layers [L,R,64] -> d_we [E,4096], fp32 or (`bf16`) rounded once to bf16; `with_colsum`: also its
+    column sums (fp32 [4096], of the stored values) from the same pass — up to 16 conv applications (depth <= 8): the
+    matrix-pipe kernel; beyond, the FMA kernel and a column-sum pass."""
     lib = _lib.load()
     L, R, _ = x_layers.shape
     e = graph.edge_count()
-    d_we = torch.empty((e, 4096), dtype=torch.float32, device=x_layers.device)
+    dev = x_layers.device
+    d_we = torch.empty((e, 4096), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
+    operands = (ptr(x_layers), ptr(gs_layers), ptr(graph.src), ptr(graph.dst), e, L, R * 64)
     if with_colsum and L <= 16 and e > 0:
-        cs = torch.empty(4096, dtype=torch.float32, device=x_layers.device)
-        nb = lib.mdno_nnconv_bwd_we_colsum_workspace_bytes()
-        ws = _ws(nb, x_layers.device)
-        check(lib.mdno_nnconv_bwd_we_colsum(ptr(x_layers), ptr(gs_layers), ptr(graph.src), ptr(graph.dst), e, L, R * 64,
-                                            ptr(d_we), ptr(cs), ptr(ws), nb, stream_ptr(d_we.device)), "mdno_nnconv_bwd_we_colsum")
+        name = "mdno_nnconv_bwd_we_bf16_colsum" if bf16 else "mdno_nnconv_bwd_we_colsum"
+        cs = torch.empty(4096, dtype=torch.float32, device=dev)
+        nb = getattr(lib, name + "_workspace_bytes")()
+        ws = _ws(nb, dev)
+        check(getattr(lib, name)(*operands, ptr(d_we), ptr(cs), ptr(ws), nb, stream_ptr(dev)), name)
         return d_we, cs
-    check(lib.mdno_nnconv_bwd_we(ptr(x_layers), ptr(gs_layers), ptr(graph.src), ptr(graph.dst), e, L, R * 64, 64, 64,
-                                 ptr(d_we), 0, stream_ptr(d_we.device)), "mdno_nnconv_bwd_we")
-    return (d_we, colsum(d_we)) if with_colsum else d_we
+    if bf16:
+        check(lib.mdno_nnconv_bwd_we_bf16(*operands, ptr(d_we), stream_ptr(dev)), "mdno_nnconv_bwd_we_bf16")
+    else:
+        check(lib.mdno_nnconv_bwd_we(*operands, 64, 64, ptr(d_we), 0, stream_ptr(dev)), "mdno_nnconv_bwd_we")
+    return (d_we, colsum_bf16(d_we) if bf16 else colsum(d_we)) if with_colsum else d_we
+
+
+def nnconv_bwd_we(x_layers: torch.Tensor, gs_layers: torch.Tensor, graph: CSRGraph, with_colsum: bool = False):
+    """d_we fp32 [E,4096] (and its column sums): see `_nnconv_bwd_we`."""
+    return _nnconv_bwd_we(x_layers, gs_layers, graph, with_colsum, bf16=False)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -656,32 +671,12 @@ def nnconv_bf16w(x: torch.Tensor, graph: CSRGraph, w_e: torch.Tensor, root, bias
 
 
 def nnconv_bwd_x_bf16w(gz: torch.Tensor, gs: torch.Tensor, by_src: CSRGraph, w_e: torch.Tensor, root) -> torch.Tensor:
-    lib = _lib.load()
-    g_prev = torch.empty_like(gz)
-    check(lib.mdno_nnconv_bwd_x_bf16w(ptr(gz), ptr(gs), ptr(by_src.row_ptr), ptr(by_src.perm), ptr(by_src.src),
-                                      gz.shape[0], ptr(_bf16(w_e)), ptr(f32(root)) if root is not None else None,
-                                      ptr(g_prev), stream_ptr(gz.device)), "mdno_nnconv_bwd_x_bf16w")
-    return g_prev
+    return _nnconv_bwd_x(gz, gs, by_src, w_e, root, bf16w=True)
 
 
 def nnconv_bwd_we_bf16(x_layers: torch.Tensor, gs_layers: torch.Tensor, graph: CSRGraph, with_colsum: bool = False):
-    """d_we bf16 [E,4096]; `with_colsum`: also its column sums (fp32 [4096], the sums of the rounded values) from the
-    same pass — up to 16 conv applications (depth <= 8); beyond that the plain kernel and `colsum_bf16`."""
-    lib = _lib.load()
-    L, R, _ = x_layers.shape
-    e = graph.edge_count()
-    d_we = torch.empty((e, 4096), dtype=torch.bfloat16, device=x_layers.device)
-    if with_colsum and L <= 16 and e > 0:
-        cs = torch.empty(4096, dtype=torch.float32, device=x_layers.device)
-        nb = lib.mdno_nnconv_bwd_we_bf16_colsum_workspace_bytes()
-        ws = _ws(nb, x_layers.device)
-        check(lib.mdno_nnconv_bwd_we_bf16_colsum(ptr(x_layers), ptr(gs_layers), ptr(graph.src), ptr(graph.dst), e, L, R * 64,
-                                                 ptr(d_we), ptr(cs), ptr(ws), nb, stream_ptr(d_we.device)),
-              "mdno_nnconv_bwd_we_bf16_colsum")
-        return d_we, cs
-    check(lib.mdno_nnconv_bwd_we_bf16(ptr(x_layers), ptr(gs_layers), ptr(graph.src), ptr(graph.dst), e, L, R * 64,
-                                      ptr(d_we), stream_ptr(d_we.device)), "mdno_nnconv_bwd_we_bf16")
-    return (d_we, colsum_bf16(d_we)) if with_colsum else d_we
+    """d_we bf16 [E,4096] (and the fp32 column sums of the rounded values): see `_nnconv_bwd_we`."""
+    return _nnconv_bwd_we(x_layers, gs_layers, graph, with_colsum, bf16=True)
 
 
 def relu_bwd_bf16(g: torch.Tensor, y: torch.Tensor, out_bf16: bool = True) -> torch.Tensor:

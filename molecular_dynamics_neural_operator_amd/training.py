@@ -13,7 +13,7 @@ Two precisions (`model.train_precision`):
                     fp32-level accuracy, or fp32 MFMA); gradients match an fp64 replica to ~1e-6.
   "bf16"            BASELINE.json configs[3] ("bf16"): the block's large tensors (h1, h2, W_e, dW_e) are
                     stored in bf16 and every GEMM is one bf16 MFMA product with fp32 accumulation
-                    (csrc/train_bf16.hip); parameters stay fp32 masters, reductions stay fp32.  Half the
+                    (csrc/train_bf16.hip, csrc/train_conv.hip); parameters stay fp32 masters, reductions stay fp32.  Half the
                     memory of the two E x 16 KiB tensors, gradients match the fp64 replica to ~1e-2.
 """
 from __future__ import annotations
@@ -51,70 +51,50 @@ class KernelIntegralBlock(torch.autograd.Function):
             X[0].copy_(x0)
         ctx.bf16 = gemm_mode == "bf16"
         if ctx.bf16:
-            return KernelIntegralBlock._forward_bf16(ctx, X, ea, graph, depth, w0, b0, w1, b1, w2, b2, root1, bias1,
-                                                     root2, bias2)
-        h1 = ops.linear(ea, w0, b0, relu=True)
-        h2 = ops.linear(h1, w1, b1, relu=True, gemm_mode=gemm_mode)
-        w_e = ops.linear(h2, w2, b2, relu=False, gemm_mode=gemm_mode)
+            h1 = ops.linear_smallk_bf16(ea, w0, b0, relu=True)               # K = 6: fp32 fmaf chains, stored bf16
+            h2 = ops.linear_bf16(h1, w1, b1, relu=True, out_bf16=True)
+            w_e = ops.linear_bf16(h2, w2, b2, relu=False, out_bf16=True)     # [E, 4096] bf16: 8 KiB per edge
+        else:
+            h1 = ops.linear(ea, w0, b0, relu=True)
+            h2 = ops.linear(h1, w1, b1, relu=True, gemm_mode=gemm_mode)
+            w_e = ops.linear(h2, w2, b2, relu=False, gemm_mode=gemm_mode)
         ops.nnconv_chain_fwd(X, graph, w_e, root1, bias1, root2, bias2, depth)        # the 2*depth applications, one call
         ctx.graph, ctx.depth, ctx.gemm_mode = graph, depth, gemm_mode
         ctx.save_for_backward(ea, h1, h2, w_e, X, w0, w1, w2, root1, root2)
         return X[L]
 
     @staticmethod
-    def _forward_bf16(ctx, X, ea, graph, depth, w0, b0, w1, b1, w2, b2, root1, bias1, root2, bias2):
-        h1 = ops.linear_smallk_bf16(ea, w0, b0, relu=True)               # K = 6: fp32 fmaf chains, stored bf16
-        h2 = ops.linear_bf16(h1, w1, b1, relu=True, out_bf16=True)
-        w_e = ops.linear_bf16(h2, w2, b2, relu=False, out_bf16=True)     # [E, 4096] bf16: 8 KiB per edge
-        L = 2 * depth
-        ops.nnconv_chain_fwd(X, graph, w_e, root1, bias1, root2, bias2, depth)
-        ctx.graph, ctx.depth, ctx.gemm_mode = graph, depth, "bf16"
-        ctx.save_for_backward(ea, h1, h2, w_e, X, w0, w1, w2, root1, root2)
-        return X[L]
-
-    @staticmethod
-    def _backward_bf16(ctx, g_out):
-        ea, h1, h2, w_e, X, w0, w1, w2, root1, root2 = ctx.saved_tensors
-        graph, depth = ctx.graph, ctx.depth
-        L, R = 2 * depth, X.shape[1]
-        by_src = getattr(graph, "by_src", None) or ops.source_sorted(graph, R)
-        inv = ops.inv_degree(graph, "mean")
-        GZ, GS, g = ops.nnconv_chain_bwd(g_out, X, inv, by_src, w_e, root1, root2, depth)
-        d_root1, d_bias1, d_root2, d_bias2 = ops.nnconv_bwd_root_pair(X[0:L], GZ[0:L])       # both convs, one launch
-        d_we, d_b2 = ops.nnconv_bwd_we_bf16(X[0:L], GS, graph, with_colsum=True)      # bf16 [E, 4096] and its column sums, one pass
-        del GZ, GS
-        d_w2 = ops.gemm_atb_bf16(d_we, h2)
-        gz2 = ops.linear_bf16_relu_bwd(d_we, ops.transpose(w2), h2)        # bf16((h2 > 0) * (dW_e . W2))
-        del d_we
-        d_b1 = ops.colsum_bf16(gz2)
-        d_w1 = ops.gemm_atb_bf16(gz2, h1)
-        gz1 = ops.linear_bf16_relu_bwd(gz2, ops.transpose(w1), h1)
-        # first layer: bias and weight gradient in ONE pass over gz1 (d_w0 = gz1^T . ea with the fp32 attributes)
-        d_b0, d_w0 = ops.colsum_atb_bf16(gz1, ea)
-        return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
-
-    @staticmethod
     def backward(ctx, g_out):
-        if ctx.bf16:
-            return KernelIntegralBlock._backward_bf16(ctx, g_out)
         ea, h1, h2, w_e, X, w0, w1, w2, root1, root2 = ctx.saved_tensors
         graph, depth, gemm_mode = ctx.graph, ctx.depth, ctx.gemm_mode
         L, R = 2 * depth, X.shape[1]
+        # the conv applications: the same five steps in either precision (the ops pick the kernel by W_e's dtype)
         by_src = getattr(graph, "by_src", None) or ops.source_sorted(graph, R)
         inv = ops.inv_degree(graph, "mean")
         GZ, GS, g = ops.nnconv_chain_bwd(g_out, X, inv, by_src, w_e, root1, root2, depth)
         d_root1, d_bias1, d_root2, d_bias2 = ops.nnconv_bwd_root_pair(X[0:L], GZ[0:L])       # both convs, one launch
-        d_we, d_b2 = ops.nnconv_bwd_we(X[0:L], GS, graph, with_colsum=True)        # and its column sums, one pass
+        bwd_we = ops.nnconv_bwd_we_bf16 if ctx.bf16 else ops.nnconv_bwd_we
+        d_we, d_b2 = bwd_we(X[0:L], GS, graph, with_colsum=True)        # [E, 4096] and its column sums, one pass
         del GZ, GS
         # edge-MLP backward
-        d_w2 = ops.gemm_atb(d_we, h2, gemm_mode=gemm_mode)
-        gz2 = ops.relu_bwd(ops.linear(d_we, ops.transpose(w2), None, gemm_mode=gemm_mode), h2)
-        del d_we
-        d_b1 = ops.colsum(gz2)
-        d_w1 = ops.gemm_atb(gz2, h1, gemm_mode=gemm_mode)
-        gz1 = ops.relu_bwd(ops.linear(gz2, ops.transpose(w1), None, gemm_mode=gemm_mode), h1)
-        d_b0 = ops.colsum(gz1)
-        d_w0 = ops.gemm_atb(gz1, ea)
+        if ctx.bf16:
+            d_w2 = ops.gemm_atb_bf16(d_we, h2)
+            gz2 = ops.linear_bf16_relu_bwd(d_we, ops.transpose(w2), h2)        # bf16((h2 > 0) * (dW_e . W2))
+            del d_we
+            d_b1 = ops.colsum_bf16(gz2)
+            d_w1 = ops.gemm_atb_bf16(gz2, h1)
+            gz1 = ops.linear_bf16_relu_bwd(gz2, ops.transpose(w1), h1)
+            # first layer: bias and weight gradient in ONE pass over gz1 (d_w0 = gz1^T . ea with the fp32 attributes)
+            d_b0, d_w0 = ops.colsum_atb_bf16(gz1, ea)
+        else:
+            d_w2 = ops.gemm_atb(d_we, h2, gemm_mode=gemm_mode)
+            gz2 = ops.relu_bwd(ops.linear(d_we, ops.transpose(w2), None, gemm_mode=gemm_mode), h2)
+            del d_we
+            d_b1 = ops.colsum(gz2)
+            d_w1 = ops.gemm_atb(gz2, h1, gemm_mode=gemm_mode)
+            gz1 = ops.relu_bwd(ops.linear(gz2, ops.transpose(w1), None, gemm_mode=gemm_mode), h1)
+            d_b0 = ops.colsum(gz1)
+            d_w0 = ops.gemm_atb(gz1, ea)
         return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
 
 
@@ -260,7 +240,7 @@ MAX_EMBEDDING_DIM = 16
 
 def check_trainable(model, window: int) -> None:
     """Refuse, before any device work, a model or window the training kernels do not implement: the conv chain and
-    its backward are 64x64 only (csrc/train.hip), the prologue backward keeps at most 16 frames and 16 embedding
+    its backward are 64x64 only (csrc/train_conv.hip), the prologue backward keeps at most 16 frames and 16 embedding
     channels per atom (csrc/train_nodes.hip), the edge-MLP's first layer reads at most 8 attributes
     (csrc/edge_mlp.hip), and bf16 training tiles k by 128."""
     conv2 = getattr(model, "conv2", None)

@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # Per-kernel register / LDS / scratch usage of one HIP source, compiled device-only for gfx950 (no GPU needed).
 # Usage: scripts/kernel_resources.sh csrc-file.hip [name-filter-regex]
+#   e.g. scripts/kernel_resources.sh train_conv.hip nnconv_bwd_x      (both instances of the input-gradient kernel)
 set -euo pipefail
 root="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 src="$root/molecular_dynamics_neural_operator_amd/csrc/$1"

@@ -1,5 +1,5 @@
 """fp64 replica of `train_precision="bf16"` (molecular_dynamics_neural_operator_amd/training.py
-`_forward_bf16` / `_backward_bf16`, csrc/train_bf16.hip) — TEST INFRASTRUCTURE.
+the bf16 branches of `KernelIntegralBlock`, csrc/train_bf16.hip, csrc/train_conv.hip) — TEST INFRASTRUCTURE.
 
 The oracle's train step (oracle/graph_kernel_oracle.py `train_step`: the reference's forward, loss and
 backward in fp64) with the bf16 path's STORAGE roundings put where the HIP path has them, so that what is

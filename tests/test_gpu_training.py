@@ -357,7 +357,7 @@ def test_training_reduces_loss(dev, tmp_path):
 
 # ------------------------------------------------------------------------------- bf16 training (cfg4)
 def test_bf16_ops_against_fp64_of_the_rounded_operands(dev, O):
-    """csrc/train_bf16.hip op by op.  GEMMs are exact products of the bf16-rounded operands with fp32
+    """csrc/train_bf16.hip and the bf16 kernels of csrc/train_conv.hip op by op.  GEMMs are exact products of the bf16-rounded operands with fp32
     accumulation, so against fp64 of the SAME rounded operands they are as accurate as an fp32 GEMM; the
     conv kernels with bf16 W_e equal the fp32 kernels fed the rounded weights (same chains, same FMAs)."""
     from molecular_dynamics_neural_operator_amd import ops

@@ -147,21 +147,36 @@ SIGNATURES = {
     "mdno_contact_maps": (_I, [_P, _L, _I, _D, _P, _P]),
 }
 
+# include/mdno_train.h (training on dense graphs, its own version number): name -> (restype, argtypes), kept in step
+# with that header (tests/test_train_cabi.py checks both ways)
+TRAIN_ABI_VERSION = 1
+TRAIN_SIGNATURES = {
+    "mdno_train_abi_version": (_I, []),
+    "mdno_train_moment_h_floats": (_SZ, [_L, _I]),
+    "mdno_train_moment_fwd_workspace_bytes": (_SZ, [_I, _I, _L, _I]),
+    "mdno_train_moment_fwd": (_I, [_P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I,
+                                   _P, _P, _P, _SZ, _P]),
+    "mdno_train_moment_bwd_workspace_bytes": (_SZ, [_I, _I, _L]),
+    "mdno_train_moment_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _SZ, _P]),
+}
+
 _lib = None
 
 
 def source_build_id() -> str | None:
-    """The id csrc/build.sh compiles into the library, recomputed from the tree: sha256 over csrc/*.{hip,h,sh} and
-    include/mdno.h (bytes, C-locale name order), first 16 hex digits.  None where the sources are not beside the
+    """The id csrc/build.sh compiles into the library, recomputed from the tree: sha256 over csrc/*.{hip,h,sh},
+    include/mdno.h and include/mdno_train.h (bytes, C-locale name order), first 16 hex digits.  None where the sources are not beside the
     package (a binary-only install)."""
     import hashlib
     csrc = _HERE / "csrc"
     header = _HERE.parent / "include" / "mdno.h"
-    if not csrc.is_dir() or not header.exists():
+    train_header = header.with_name("mdno_train.h")
+    if not csrc.is_dir() or not header.exists() or not train_header.exists():
         return None
     files = sorted([f for f in csrc.iterdir() if f.suffix in (".hip", ".h", ".sh")], key=lambda f: str(f).encode())
     h = hashlib.sha256()
-    for f in files + [header]:
+    for f in files + [header, train_header]:
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
 
@@ -176,13 +191,15 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP library is not built. Run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
     ver = lib.mdno_abi_version()
     if ver != ABI_VERSION:
         raise MdnoError(f"libmdno ABI {ver} != binding {ABI_VERSION}; rebuild the library")
+    if lib.mdno_train_abi_version() != TRAIN_ABI_VERSION:
+        raise MdnoError(f"libmdno training ABI {lib.mdno_train_abi_version()} != binding {TRAIN_ABI_VERSION}; rebuild the library")
     want, have = source_build_id(), lib.mdno_build_id().decode()
     # (an experimental build — scripts/micro/build_exp.sh, loaded through MDNO_LIB — says so in its build id; MDNO_LIB
     # pointing at any other library, the in-tree one included, does not switch the check off)

@@ -143,6 +143,9 @@ int moment_prepare_graph(const int* row_ptr, int num_rows, const MomentWs& f, hi
 int moment_conv(const float* x, const float* h2, const int* row_ptr, const int* src, int num_rows, int ker_width,
                 const float* root, const float* bias, int aggr, int relu, float* y, const MomentWs& f, hipStream_t s,
                 int gemm_mode, int application);
+// K1 alone (training backward): S (+ s0) of destinations r0 .. r0 + cnt - 1 into f.s, unscaled
+int moment_s_chunk(const float* x, const float* h2, const int* row_ptr, const int* src, int ker_width, int r0, int cnt,
+                   const MomentWs& f, hipStream_t s, bool exact_f32);
 // SPLIT_F16, before a forward's application 0: every row's largest |x| (the later applications get it from the one before)
 int moment_row_absmax(const float* x, int num_rows, const MomentWs& f, hipStream_t s);
 

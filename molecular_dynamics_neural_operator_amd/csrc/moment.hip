@@ -41,6 +41,7 @@
 
 #include "kernels.h"
 #include "mfma_f32.h"
+#include "moment_layout.h"
 #include "split_layout.h"
 
 namespace mdno {
@@ -211,15 +212,14 @@ __global__ __launch_bounds__(CH) void degree_order_kernel(const int* __restrict_
 }
 
 // ---------------------------------------------------------------- K1: S_t = X_N(t)^T . H_t
-// k-tiles (32 kappa) of a destination's row of the S image: 64 k / 32 for S_t itself + 2 for s0_t (kappa = 64 k + i)
-__host__ __device__ constexpr size_t moment_nkt(int K) { return (size_t)64 * K / 32 + 2; }
+// (moment_nkt, the k-tiles of a destination's row of the S image: moment_layout.h)
 constexpr int MO_EDGES = 16;                 // edges per stage = one MFMA k-step
 // The first bytes of H are loaded with the default cache policy, the rest non-temporally: the 2 x depth applications of
 // a forward stream the same H, and what of it stays in the 256 MiB Infinity Cache between two of them is read faster
 // (scripts/micro/mall_partial_residency.hip: 248 MB at 5.5 TB/s all non-temporal, 6.3 TB/s with 64 MiB kept — and no
 // further gain from more, while S (written by K1, read back by K2 out of the same cache) and W3R need their share).
 constexpr size_t kMomentCachedBytes = (size_t)64 << 20;
-constexpr int MO_CQ = 256;                   // hidden units per workgroup
+// (MO_CQ = 256 hidden units per workgroup: moment_layout.h)
 constexpr int MO_HROW = MO_CQ * 2 + 64;      // LDS bytes per edge row of an H plane (64 B of padding: the four rows of a
                                              // transposing read's block fall into four different 64-B bank quarters)
 constexpr int MO_XROW = 64 * 2 + 64;         // the same for the 64 feature columns
@@ -1012,12 +1012,7 @@ __global__ __launch_bounds__(256) void row_absmax_kernel(const float* __restrict
 }  // namespace
 
 // ---------------------------------------------------------------- host side
-constexpr int kMomentChunkRows = 512;      // destinations per S chunk: 512 x 64 k x 4 B = 128 MiB at k = 1024, written by K1
-                                           // and read back by K2 while still in the 256 MiB Infinity Cache
-static int moment_chunk_rows(int num_rows) {
-    const int padded = (num_rows + 127) / 128 * 128;
-    return padded < kMomentChunkRows ? padded : kMomentChunkRows;
-}
+// (kMomentChunkRows = 512 destinations per S chunk, moment_chunk_rows: moment_layout.h)
 
 // k % 128: what the hidden GEMM that writes H tiles by, and what makes a K2 slice an even number of k-tiles
 // (64 k / 32 = 2 k k-tiles over 128 slices = k / 64 each; K2's loop takes them two at a time)
@@ -1078,6 +1073,21 @@ int moment_prepare_graph(const int* row_ptr, int num_rows, const MomentWs& f, hi
 int moment_row_absmax(const float* x, int num_rows, const MomentWs& f, hipStream_t s) {
     hipLaunchKernelGGL(row_absmax_kernel, dim3((num_rows + 15) / 16), dim3(256), 0, s, x, num_rows, f.xm[0]);
     return check_launch("row_absmax_kernel");
+}
+
+// K1 alone for the destinations r0 .. r0 + cnt - 1: their S (+ s0) into f.s in S's own units — on three bf16 planes, or
+// (`exact_f32`) on the fp32 MFMA.  What the training backward recomputes per chunk (train_moment.hip).
+int moment_s_chunk(const float* x, const float* h2, const int* row_ptr, const int* src, int ker_width, int r0, int cnt,
+                   const MomentWs& f, hipStream_t s, bool exact_f32) {
+    const dim3 grid((unsigned)(((cnt + 7) / 8) * 8 * moment_nq(ker_width)));
+    const int cache_e = (int)(kMomentCachedBytes / ((size_t)ker_width * sizeof(float))) & ~127;
+    if (exact_f32)
+        hipLaunchKernelGGL(moment_f32_kernel, grid, dim3(256), 0, s, h2, row_ptr, src, (const int*)f.order, f.s, ker_width, r0,
+                           cnt, x);
+    else
+        hipLaunchKernelGGL(moment_kernel<false>, grid, dim3(256), 0, s, h2, row_ptr, src, (const int*)f.order, f.s, ker_width,
+                           r0, cnt, x, cache_e, (float*)nullptr, (const float*)nullptr, (int*)nullptr);
+    return check_launch("moment_s_chunk");
 }
 
 int moment_conv(const float* x, const float* h2, const int* row_ptr, const int* src, int num_rows, int ker_width,

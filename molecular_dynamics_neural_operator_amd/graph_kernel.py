@@ -427,6 +427,9 @@ class KernelNN(nn.Module):
         # training (training.py): "fp32" or "bf16" (bf16 storage of h1, h2, W_e, dW_e + single-product bf16
         # GEMMs with fp32 accumulation; fp32 master parameters)
         self.train_precision = "fp32"
+        # training.py: "materialized" (W_e and dW_e [E, 4096] are formed), "factored" (per destination, neither exists:
+        # dense graphs; width 64, ker_width % 128 == 0, fp32 storage) or "auto" (the counted-graph rule per batch)
+        self.train_conv_mode = "materialized"
         # how conv applications run inside the on-device rollout / position-graph forward
         # (include/mdno.h MDNO_CONV_*): "factored" = the reference's sums reassociated per destination
         # node, W_e never formed (csrc/moment.hip; needs width 64 and ker_width % 128 == 0, otherwise the

@@ -750,6 +750,65 @@ def nnconv_chain_bwd(g_out: torch.Tensor, x_layers: torch.Tensor, inv_deg: torch
     return gz, gs, g_in
 
 
+def train_moment_fwd(x_layers: torch.Tensor, graph: CSRGraph, edge_attr: torch.Tensor, weights, root1, bias1, root2, bias2,
+                     depth: int, gemm_mode: str) -> torch.Tensor:
+    """Forward of the kernel-integral block in the factored formulation (include/mdno_train.h mdno_train_moment_fwd):
+    x_layers f32 [2*depth+1, R, 64] with layer 0 given, layers 1.. written in place; `edge_attr` [E, ker_in] in the
+    caller's edge order (graph.perm maps it to CSR order), `weights` = (w0, b0, w1, b1, w2, b2).  Returns the edge-MLP's
+    last hidden activation H as the k-tiled image the backward reads again."""
+    lib = _lib.load()
+    L = 2 * depth
+    if x_layers.dim() != 3 or x_layers.shape[0] != L + 1 or x_layers.shape[2] != 64 or depth < 1:
+        raise MdnoError(f"train_moment_fwd: x_layers {tuple(x_layers.shape)}, expected [{L + 1}, R, 64] with depth >= 1")
+    w = [f32(t) for t in weights]
+    k, ker_in = w[2].shape[0], w[0].shape[1]
+    if tuple(w[4].shape) != (4096, k) or tuple(w[2].shape) != (k, k):
+        raise MdnoError(f"train_moment_fwd: edge-MLP shapes {[tuple(t.shape) for t in w]} (width 64 only)")
+    dev, R = x_layers.device, x_layers.shape[1]
+    ea = f32(edge_attr)
+    E = graph.edge_count()
+    if ea.shape[0] != E or ea.dim() != 2 or ea.shape[1] != ker_in:
+        raise MdnoError(f"train_moment_fwd: edge_attr {tuple(ea.shape)}, expected [{E}, {ker_in}]")
+    if E == 0:                  # (never read: the device edge count is 0; the pointer must not be null)
+        ea = torch.zeros((1, ker_in), dtype=torch.float32, device=dev)
+    mode = _lib.GEMM_MODES[gemm_mode]
+    h_img = torch.empty(lib.mdno_train_moment_h_floats(E, k), dtype=torch.float32, device=dev)
+    ws = _ws(lib.mdno_train_moment_fwd_workspace_bytes(R, k, graph.edge_cap, mode), dev)
+    check(lib.mdno_train_moment_fwd(ptr(ea), ptr(graph.perm), ptr(graph.num_edges), graph.edge_cap, ker_in, k, mode,
+                                    *[ptr(t) for t in w], ptr(graph.row_ptr), ptr(graph.src), ptr(graph.dst), R,
+                                    ptr(f32(root1)), ptr(f32(bias1)), ptr(f32(root2)), ptr(f32(bias2)), int(depth),
+                                    ptr(x_layers), ptr(h_img), ptr(ws), ws.numel(), stream_ptr(dev)), "mdno_train_moment_fwd")
+    return h_img
+
+
+def train_moment_bwd(g_out: torch.Tensor, x_layers: torch.Tensor, h_img: torch.Tensor, graph: CSRGraph, by_src: CSRGraph,
+                     w2: torch.Tensor, b2: torch.Tensor, root1, root2, depth: int, gemm_mode: str):
+    """Backward through the 2*depth factored applications (mdno_train_moment_bwd) ->
+    (gz [L,R,64], g_in [R,64], gz2 [E,k] = (H > 0) * dLoss/dH row-major, d_w2 [4096,k], d_b2 [4096])."""
+    lib = _lib.load()
+    L, R = 2 * depth, x_layers.shape[1]
+    if tuple(g_out.shape) != (R, 64) or x_layers.shape[0] != L + 1:
+        raise MdnoError(f"train_moment_bwd: g_out {tuple(g_out.shape)}, x_layers {tuple(x_layers.shape)}")
+    w2, b2 = f32(w2), f32(b2)
+    k = w2.shape[1]
+    E = graph.edge_count()
+    dev = x_layers.device
+    if h_img.numel() != lib.mdno_train_moment_h_floats(E, k):
+        raise MdnoError(f"train_moment_bwd: H image of {h_img.numel()} floats for {E} edges, k = {k}")
+    gz = torch.empty((L, R, 64), dtype=torch.float32, device=dev)
+    g_in = torch.empty((R, 64), dtype=torch.float32, device=dev)
+    gz2 = torch.empty((E, k), dtype=torch.float32, device=dev)
+    d_w2 = torch.empty((4096, k), dtype=torch.float32, device=dev)
+    d_b2 = torch.empty(4096, dtype=torch.float32, device=dev)
+    ws = _ws(lib.mdno_train_moment_bwd_workspace_bytes(R, k, E), dev)
+    gz2_arg = gz2 if E else torch.empty((1, k), dtype=torch.float32, device=dev)
+    check(lib.mdno_train_moment_bwd(ptr(f32(g_out)), ptr(x_layers), ptr(h_img), ptr(graph.row_ptr), ptr(graph.src),
+                                    ptr(by_src.row_ptr), ptr(by_src.perm), R, E, k, int(depth), _lib.GEMM_MODES[gemm_mode],
+                                    ptr(w2), ptr(b2), ptr(f32(root1)), ptr(f32(root2)), ptr(gz), ptr(g_in), ptr(gz2_arg),
+                                    ptr(d_w2), ptr(d_b2), ptr(ws), ws.numel(), stream_ptr(dev)), "mdno_train_moment_bwd")
+    return gz, g_in, gz2, d_w2, d_b2
+
+
 def colsum_atb_bf16(a: torch.Tensor, b: torch.Tensor):
     """(column sums of a bf16 [rows,n], a^T . b for b fp32 [rows,6 or 8]) in one pass over a -> ([n], [n,kb]);
     other shapes: the two separate ops."""

@@ -98,6 +98,51 @@ class KernelIntegralBlock(torch.autograd.Function):
         return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
 
 
+class FactoredKernelIntegralBlock(torch.autograd.Function):
+    """The same block in the factored formulation (`model.train_conv_mode`; csrc/train_moment.hip):
+    per destination the sum over its in-edges is taken before the contraction with W2, so neither W_e nor dW_e
+    [E, 4096] exists.  Kept for the backward: the feature stack and H = h2 as the k-tiled image (4 k bytes per edge).
+    fp32 storage; the forward runs in `gemm_mode` (bitwise the eval-mode factored forward), the backward's own
+    products are fp32 fmaf chains in every mode."""
+
+    @staticmethod
+    def forward(ctx, x0, edge_attr, graph, depth, gemm_mode, w0, b0, w1, b1, w2, b2, root1, bias1, root2, bias2):
+        R = x0.shape[0]
+        X = getattr(graph, "x_stack", None)
+        L = 2 * depth
+        if X is None or X.data_ptr() != x0.data_ptr() or tuple(X.shape) != (L + 1, R, 64):
+            X = torch.empty((L + 1, R, 64), dtype=torch.float32, device=x0.device)
+            X[0].copy_(x0)
+        ea = ops.f32(edge_attr).contiguous()
+        h_img = ops.train_moment_fwd(X, graph, ea, (w0, b0, w1, b1, w2, b2), root1, bias1, root2, bias2, depth, gemm_mode)
+        ctx.graph, ctx.depth, ctx.gemm_mode = graph, depth, gemm_mode
+        ctx.save_for_backward(ea, h_img, X, w0, b0, w1, w2, b2, root1, root2)
+        return X[L]
+
+    @staticmethod
+    def backward(ctx, g_out):
+        ea, h_img, X, w0, b0, w1, w2, b2, root1, root2 = ctx.saved_tensors
+        graph, depth, gemm_mode = ctx.graph, ctx.depth, ctx.gemm_mode
+        L, R = 2 * depth, X.shape[1]
+        E = graph.edge_count()
+        by_src = getattr(graph, "by_src", None) or ops.source_sorted(graph, R)
+        gz, g, gz2, d_w2, d_b2 = ops.train_moment_bwd(g_out.contiguous(), X, h_img, graph, by_src, w2, b2, root1, root2,
+                                                      depth, gemm_mode)
+        d_root1, d_bias1, d_root2, d_bias2 = ops.nnconv_bwd_root_pair(X[0:L], gz)
+        del gz
+        # edge-MLP backward below H, with the existing ops; h1 is formed again from the attributes (K = ker_in: cheap)
+        if graph.perm is not None:
+            ea = ops.permute_rows(ea, graph.perm, E)
+        h1 = ops.linear(ea, w0, b0, relu=True)
+        d_b1 = ops.colsum(gz2)
+        d_w1 = ops.gemm_atb(gz2, h1, gemm_mode=gemm_mode)
+        gz1 = ops.relu_bwd(ops.linear(gz2, ops.transpose(w1), None, gemm_mode=gemm_mode), h1)
+        del gz2, h1
+        d_b0 = ops.colsum(gz1)
+        d_w0 = ops.gemm_atb(gz1, ea)
+        return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
+
+
 class NodePrologue(torch.autograd.Function):
     """x0 = relu(fc1([emb(aa), lstm_fc(LSTM over the window)]))  (graph_kernel.py:279-298), B=1 semantics per
     sample.  Parameters arrive as tensors (autograd tracks them) and as the model's ParamPack (device pointers)."""
@@ -238,6 +283,35 @@ MAX_TRAIN_WINDOW = 16
 MAX_EMBEDDING_DIM = 16
 
 
+# `model.train_conv_mode`: how the kernel-integral block runs in training.  "materialized" (default): W_e and dW_e
+# [E, 4096] are formed (KernelIntegralBlock).  "factored": FactoredKernelIntegralBlock — for dense graphs, where 16 KiB
+# per edge does not fit.  "auto": the library's rule on the batch's counted edge list (mdno_conv_mode_for_graph: mean
+# degree >= 40 and >= 16,384 edges per member -> factored), materialized where the factored form does not apply.
+# The rule is the inference one: a crossover of its own for training has not been measured yet.
+TRAIN_CONV_MODES = ("materialized", "factored", "auto")
+
+
+def factored_training_applies(model) -> bool:
+    """Width 64, ker_width a multiple of 128 (csrc/moment.hip moment_supported), fp32 storage, mean aggregation."""
+    k = model.conv1.net.hip_weights()[2].shape[0]
+    convs = [model.conv1] + ([model.conv2] if getattr(model, "conv2", None) is not None else [])
+    return (model.fc1.out_features == 64 and k >= 128 and k % 128 == 0 and
+            getattr(model, "train_precision", "fp32") == "fp32" and all(getattr(c, "aggr", "mean") == "mean" for c in convs))
+
+
+def resolve_train_conv_mode(model, members: int, n_atoms: int, n_edges: int) -> str:
+    """The formulation a training step on this batch takes: "materialized" or "factored"."""
+    mode = getattr(model, "train_conv_mode", "materialized")
+    if mode == "materialized" or not factored_training_applies(model):
+        return "materialized"
+    if mode == "factored":
+        return "factored"
+    from . import _lib
+    pack = model.param_pack(next(model.parameters()).device, conv_mode="materialized")
+    rule = int(_lib.load().mdno_conv_mode_for_graph(pack.ref, int(members), int(n_atoms), int(n_edges)))
+    return "factored" if rule == _lib.CONV_MODES["factored"] else "materialized"
+
+
 def check_trainable(model, window: int) -> None:
     """Refuse, before any device work, a model or window the training kernels do not implement: the conv chain and
     its backward are 64x64 only (csrc/train_conv.hip), the prologue backward keeps at most 16 frames and 16 embedding
@@ -266,6 +340,16 @@ def check_trainable(model, window: int) -> None:
         raise MdnoError(f"train_precision={precision!r} (fp32, bf16)")
     if precision == "bf16" and (w1.shape[0] % 128 or w1.shape[1] % 32):
         raise NotImplementedError("bf16 training needs width 64 and ker_width a multiple of 128")
+    mode = getattr(model, "train_conv_mode", "materialized")
+    if mode not in TRAIN_CONV_MODES:
+        raise MdnoError(f"train_conv_mode={mode!r} {TRAIN_CONV_MODES}")
+    if mode == "factored":
+        if precision == "bf16":
+            raise NotImplementedError('train_conv_mode="factored" keeps fp32 storage: bf16 storage for the factored '
+                                      'training path is out of scope (use train_precision="fp32")')
+        if not factored_training_applies(model):
+            raise NotImplementedError(f'train_conv_mode="factored" needs width 64, ker_width a multiple of 128 (got '
+                                      f'{w1.shape[0]}) and mean aggregation')
 
 
 def train_forward(model, data) -> torch.Tensor:
@@ -317,10 +401,15 @@ def train_forward(model, data) -> torch.Tensor:
     w0, b0, w1, b1, w2, b2 = net.hip_weights()
     c2 = conv2 if conv2 is not None else model.conv1
     precision = getattr(model, "train_precision", "fp32")
-    x = KernelIntegralBlock.apply(x0, batch.edge_attr.to(dev), graph, depth,
-                                  "bf16" if precision == "bf16" else getattr(model, "gemm_mode", "f32"),
-                                  w0, b0, w1, b1, w2, b2,
-                                  model.conv1.root, model.conv1.bias, c2.root, c2.bias)
+    B = max(int(getattr(batch, "num_graphs", 1) or 1), 1)
+    if resolve_train_conv_mode(model, B, max(R // B, 1), int(ei.shape[1])) == "factored":
+        block = FactoredKernelIntegralBlock
+    else:
+        block = KernelIntegralBlock
+    x = block.apply(x0, batch.edge_attr.to(dev), graph, depth,
+                    "bf16" if precision == "bf16" else getattr(model, "gemm_mode", "f32"),
+                    w0, b0, w1, b1, w2, b2,
+                    model.conv1.root, model.conv1.bias, c2.root, c2.bias)
     return FcOut.apply(x, model.fc2.weight, model.fc2.bias)
 
 

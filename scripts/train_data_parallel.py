@@ -39,6 +39,9 @@ ap.add_argument("--kernel-width", type=int, default=1024)
 ap.add_argument("--depth", type=int, default=6)
 ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--precision", choices=["fp32", "bf16"], default="bf16")
+ap.add_argument("--train-conv-mode", choices=["materialized", "factored", "auto"], default="materialized",
+                help="kernel-integral block in training: W_e formed, factored per destination (dense graphs; needs "
+                     "--precision fp32), or by the counted-graph rule")
 ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                 help="nccl (RCCL), one GPU per rank; gloo only to rehearse with ranks sharing a card")
 ap.add_argument("--force-dist", action="store_true", help="run alone as a one-rank process group")
@@ -86,6 +89,7 @@ with torch.no_grad():     # as train_synthetic.py: damp the kernel's last layer 
         p_.mul_(0.05)
 model.to(dev)
 model.train_precision = a.precision
+model.train_conv_mode = a.train_conv_mode
 broadcast_parameters(model)                                       # every replica starts from rank 0's parameters
 opt = Adam(model.parameters(), lr=a.lr, weight_decay=5e-4)
 sched = torch.optim.lr_scheduler.StepLR(opt, step_size=50, gamma=0.8)

@@ -36,6 +36,9 @@ ap.add_argument("--cpu-batches", type=int, default=0)
 ap.add_argument("--precision", choices=["fp32", "bf16"], default="bf16",
                 help="bf16 (BASELINE configs[3]): h1, h2, W_e, dW_e stored in bf16, single-product bf16 GEMMs with "
                      "fp32 accumulation, fp32 master weights; fp32: split-bf16 GEMMs at fp32-level accuracy")
+ap.add_argument("--train-conv-mode", choices=["materialized", "factored", "auto"], default="materialized",
+                help="kernel-integral block in training: W_e formed, factored per destination (dense graphs; needs "
+                     "--precision fp32), or by the counted-graph rule")
 ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fused=True) instead of training.Adam (mdno_adam_step)")
 ap.add_argument("--host-collate", action="store_true",
                 help="collate every batch on the host from ContactMapDataset samples (what the reference's "
@@ -90,6 +93,7 @@ with torch.no_grad():     # the reference's init makes activations explode throu
 cpu_model = copy.deepcopy(model)
 model.to(dev)
 model.train_precision = a.precision
+model.train_conv_mode = a.train_conv_mode
 from molecular_dynamics_neural_operator_amd.training import Adam  # noqa: E402
 if a.torch_adam:      # torch's own (its single-kernel form where the build has it): the same update rule (graph_kernel.py:541-543)
     try:

@@ -23,11 +23,10 @@
 // rollout step), so grids are sized by capacity and whole tiles beyond *num_edges exit at once.
 #include "kernels.h"
 #include "mfma_f32.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 128, BK = 32, LDS_LD = BK + 4;  // 36 floats = 144 B rows
 

@@ -5,7 +5,8 @@
 // (x_hi = bf16(x), x_mid = bf16(x - x_hi), x_lo = bf16(x - x_hi - x_mid); the subtractions are exact
 // in fp32) and the product is accumulated in fp32 from the six leading plane products
 //     a.b ~= a_hi b_hi + (a_hi b_mid + a_mid b_hi) + (a_hi b_lo + a_lo b_hi + a_mid b_mid),
-// each a bf16 x bf16 MFMA with fp32 accumulation (products of bf16 pairs are exact in fp32).  The
+// each a bf16 x bf16 MFMA with fp32 accumulation (products of bf16 pairs are exact in fp32), summed
+// smallest first — the order is split_mma.h's mma6_bf16, the one definition every kernel uses.  The
 // dropped terms are <= 2^-24 |a b|: the result is as close to the fp64 product as a plain fp32 GEMM
 // (measured rms 9e-8 vs 2.4e-7 for an fp32 GEMM at K=1024; tests/test_gpu_parity.py).  6 MFMAs at 16x
 // the fp32-MFMA rate = 2.67x fewer matrix-pipe cycles than v_mfma_f32_32x32x2_f32.
@@ -40,8 +41,8 @@
 // SPLIT_F16 (gemm_mode 2) runs the k x k hidden layer with TWO fp16 planes instead:
 //     x = x_hi + 2^-11 x_lo',   x_hi = fp16(x),  x_lo' = fp16((x - x_hi) * 2^11)      (22-23 mantissa bits)
 //     a.b ~= a_hi b_hi + 2^-11 (a_hi b_lo' + a_lo' b_hi)                               (dropped: 2^-22 a_lo' b_lo')
-// — three fp16 x fp16 MFMAs (exact products, fp32 accumulation, the cross terms in their own
-// accumulator so that the 2^-11 is applied once, exactly) instead of six bf16 ones: half the matrix
+// — three fp16 x fp16 MFMAs (split_mma.h's MDNO_MMA3_F16: exact products, fp32 accumulation, the cross terms in their
+// own accumulator so that the 2^-11 is applied once, exactly) instead of six bf16 ones: half the matrix
 // work and two thirds of the staged bytes for an error vs fp64 still below a plain fp32 GEMM's
 // (rel. rms 7e-8 before accumulation error vs 2.4e-7; tests/test_gpu_parity.py).  fp16 has a 5-bit
 // exponent: the scheme is exact only while |x| < 65504, so the producers of the planes raise a device
@@ -49,14 +50,10 @@
 // right behind it, and exiting at once when the flag is clear — redo the chunk.  Values below 2^-14
 // lose relative, never absolute, accuracy (x_hi goes subnormal, x_lo' still carries 11 more bits).
 #include "kernels.h"
-#include "split_layout.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // The flag words: F16FlagWord (kernels.h).  `need`: which of the "seen" words the product's operands depend on.
 // Any failure sends the chunk down the bf16 path.
@@ -78,9 +75,6 @@ constexpr int PLANE_BYTES = 128 * TK * 2;      // 4 KiB per (128-row) operand pl
 // stage = A: TM/128 row tiles x 3 planes, B: 3 planes.  TM=256: 36 KiB (x2 buffers = 72 KiB, 2 workgroups
 // of 8 waves per CU); TM=128: 24 KiB (48 KiB, 3 workgroups of 4 waves per CU)
 constexpr int stage_bytes(int tm) { return (3 * tm / 128 + 3) * PLANE_BYTES; }
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(1))) const unsigned char glb_u8;
 
 // ---------------------------------------------------------------- fp32 [rows,K] -> tiled planes
 // thread = one 16-B chunk (8 consecutive k of one row)
@@ -439,15 +433,7 @@ __device__ __forceinline__ void mma_split_stage(f32x16 (&acc)[2][2], const unsig
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            // smallest terms first
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < 2; ++j) mma6_bf16(a[i], b[j], acc[i][j]);
 }
 
 // OUT (a SplitOut; the template parameters stay int): what the epilogue writes
@@ -458,6 +444,58 @@ enum SplitOut {
     OUT_F32_RELU = 3,     // fp32 row-major after ReLU (training: mdno_linear_split_fwd)
     OUT_PLANES_F16 = 4,   // two fp16 planes after ReLU (fp16 kernels: the next GEMM's operand; raises F16_ACT_RANGE on a value out of range)
 };
+
+// ---- what the three GEMM kernels (gemm_split_bf16_kernel, gemm_split_f16_kernel, gemm_split_f16_small_kernel) share
+// The row window: how many of the launch's rows hold data (<= 0: nothing to do)
+__device__ __forceinline__ long long split_row_window(const SplitGemmArgs& g) {
+    long long valid = g.num_edges ? (long long)(*g.num_edges) - g.row_begin : (long long)g.rows_valid;
+    if (valid > g.rows) valid = g.rows;
+    return valid;
+}
+
+// tile -> its row / column index among the tiles_mv x tiles_n tiles that hold valid rows: n fastest (neighbours share
+// the A row-panel) or m fastest (they share the B panel), for the two 256-row kernels (the few-rows kernel is always
+// m fastest and writes that out).  Expression macros, not a function: behind a function gemm_split_f16_kernel's
+// prologue forms its bias address with two more instructions.
+#define MDNO_SPLIT_TILE_ROW(tile, m_fastest, tiles_mv, tiles_n) ((m_fastest) ? (tile) % (tiles_mv) : (tile) / (tiles_n))
+#define MDNO_SPLIT_TILE_COL(tile, m_fastest, tiles_mv, tiles_n) ((m_fastest) ? (tile) / (tiles_mv) : (tile) % (tiles_n))
+
+// element (m, n) of the product, v = accumulators + bias, to the output OUT names (all but OUT_PLANES_F16)
+template <int OUT>
+__device__ __forceinline__ void split_store(const SplitGemmArgs& g, int m, int n, float v) {
+    static_assert(OUT == OUT_F32 || OUT == OUT_F32_RELU || OUT == OUT_H_TILED || OUT == OUT_PLANES, "see split_store_f16");
+    if (OUT == OUT_H_TILED) {   // k-tiled fp32 image [m/128][n/32][128][32] (csrc/moment.hip K1)
+        g.C[((size_t)(m >> 7) * (g.N >> 5) + (n >> 5)) * 4096 + (m & 127) * 32 + (n & 31)] = relu_f(v);
+    } else if (OUT == OUT_PLANES) {
+        __bf16 ph, pm, pl;
+        split3(relu_f(v), ph, pm, pl);
+        const size_t o = tiled_off(m, n, g.N >> 4, 0);
+        *reinterpret_cast<__bf16*>(g.Cp + o) = ph;
+        *reinterpret_cast<__bf16*>(g.Cp + o + PLANE_BYTES) = pm;
+        *reinterpret_cast<__bf16*>(g.Cp + o + 2 * PLANE_BYTES) = pl;
+    } else {
+        g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
+    }
+}
+
+// the same for the fp16 kernels, whose plane output is OUT_PLANES_F16.  bad / seen: what that epilogue learns about the
+// values it stores (one out of fp16 range; one large enough for the next product to use the image)
+template <int OUT>
+__device__ __forceinline__ void split_store_f16(const SplitGemmArgs& g, int m, int n, float v, bool& bad, bool& seen) {
+    if constexpr (OUT == OUT_PLANES_F16) {
+        const float rv = relu_f(v);
+        bad |= !(rv < F16_MAX);
+        seen |= rv >= F16_ACT_MIN;
+        _Float16 ph, pl;
+        split2h(rv, ph, pl);
+        const size_t o = tiled_off2(m, n, g.N >> 4, 0);
+        *reinterpret_cast<_Float16*>(g.Cp + o) = ph;
+        *reinterpret_cast<_Float16*>(g.Cp + o + PLANE_BYTES) = pl;
+    } else {
+        split_store<OUT>(g, m, n, v);
+    }
+}
+
 // one TM x 128 tile of the product: tile `orig` of `nwg` in the XCD-aware order
 template <int TM, int OUT>
 __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, unsigned char* lds, long long valid, int nwg, int orig) {
@@ -466,13 +504,10 @@ __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, uns
     constexpr int PIECES = STAGE_BYTES / 1024;           // 1 KiB DMA pieces per stage: 24 or 36
     constexpr int A_PIECES = PIECES - 12;
     constexpr int PPW = (PIECES + WAVES - 1) / WAVES;    // pieces per wave: 6 or 5
-    // XCD-aware tile order over the tiles that hold valid rows: workgroups b, b+8, ... share an XCD
-    // (round-robin dispatch); give each XCD a contiguous range of tiles.  Bijective for any count.
-    const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-    const int tiles_mv = nwg / g.tiles_n;
-    const int bm = (g.m_fastest ? tile % tiles_mv : tile / g.tiles_n) * TM;
-    const int bn = (g.m_fastest ? tile / tiles_mv : tile % g.tiles_n) * TN;
+    // XCD-aware order (xcd_tile_range) over the tiles that hold valid rows
+    const int tile = xcd_tile(orig, nwg), tiles_mv = nwg / g.tiles_n;
+    const int bm = MDNO_SPLIT_TILE_ROW(tile, g.m_fastest, tiles_mv, g.tiles_n) * TM;
+    const int bn = MDNO_SPLIT_TILE_COL(tile, g.m_fastest, tiles_mv, g.tiles_n) * TN;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform
@@ -550,7 +585,7 @@ __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, uns
 #undef MDNO_DMA_STAGE
 #undef MDNO_DMA_BARRIER
 
-    // epilogue: C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    // epilogue: column lane & 31, row mfma32_row(e, h) of each 32x32 tile
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = bn + wn * 64 + j * 32 + l31;
@@ -559,22 +594,8 @@ __device__ __forceinline__ void gemm_split_bf16_tile(const SplitGemmArgs& g, uns
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (m < valid) {
-                    const float v = acc[i][j][e] + bv;
-                    if (OUT == OUT_H_TILED) {   // k-tiled fp32 image [m/128][n/32][128][32] (csrc/moment.hip K1)
-                        g.C[((size_t)(m >> 7) * (g.N >> 5) + (n >> 5)) * 4096 + (m & 127) * 32 + (n & 31)] = relu_f(v);
-                    } else if (OUT == OUT_PLANES) {
-                        __bf16 ph, pm, pl;
-                        split3(relu_f(v), ph, pm, pl);
-                        const size_t o = tiled_off(m, n, g.N >> 4, 0);
-                        *reinterpret_cast<__bf16*>(g.Cp + o) = ph;
-                        *reinterpret_cast<__bf16*>(g.Cp + o + PLANE_BYTES) = pm;
-                        *reinterpret_cast<__bf16*>(g.Cp + o + 2 * PLANE_BYTES) = pl;
-                    } else {
-                        g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
-                    }
-                }
+                const int m = mfma32_row(e, h, bm + wm * 64 + i * 32);
+                if (m < valid) split_store<OUT>(g, m, n, acc[i][j][e] + bv);
             }
         }
     }
@@ -588,8 +609,7 @@ __global__ __launch_bounds__(TM * 2, 2) void gemm_split_bf16_kernel(SplitGemmArg
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     if (g.f16_flags != nullptr && !f16_blocked(g.f16_flags, g.f16_need)) return;   // bf16 fallback launch, not needed
     if (g.f16_flags != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(const_cast<int*>(g.f16_flags) + F16_FALLBACK_COUNT, 1);
-    long long valid = g.num_edges ? (long long)(*g.num_edges) - g.row_begin : (long long)g.rows_valid;
-    if (valid > g.rows) valid = g.rows;
+    const long long valid = split_row_window(g);
     if (valid <= 0) return;
     const int nwg = g.tiles_n * (int)((valid + TM - 1) / TM);
     if constexpr (STRIDE) {
@@ -611,56 +631,6 @@ __global__ __launch_bounds__(TM * 2, 2) void gemm_split_bf16_kernel(SplitGemmArg
 // (two k-steps = 32 k: 24 MFMAs + 16 fragment reads per wave, one barrier) and live in a ring of three
 // (3 x 48 KiB), two stages ahead of the MFMAs, with a COUNTED wait — `s_waitcnt vmcnt(6)` lets the
 // newest stage's six pieces stay in flight (loads return in order; the K loop issues no stores).
-template <int MI>   // MI 32-row tiles x 2 32-column tiles per wave
-__device__ __forceinline__ void mma_f16_kstep(f32x16 (&acc)[MI][2], f32x16 (&accx)[MI][2], const unsigned char* st,
-                                              int a_rd, int b_rd) {
-    f16x8 a[MI][2], b[2][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i) a[i][p] = *reinterpret_cast<const f16x8*>(st + p * PLANE_BYTES + a_rd + i * 32 * 32);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[j][p] = *reinterpret_cast<const f16x8*>(st + p * PLANE_BYTES + b_rd + j * 32 * 32);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[j][0], accx[i][j], 0, 0, 0);
-            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][1], accx[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-        }
-}
-
-// The same k-step with something to do between its (i, j) groups of three MFMAs: fill(g), g = 0 .. 2*MI-1, is
-// called after group g has been issued and pinned there — the LDS-DMA pieces of the stage after next go
-// out one per group, in the shadow of MFMAs already in the pipe, instead of as a burst of six in front of
-// the stage's first fragment read (an LDS-DMA piece costs the issuing wave 60-180 cycles, more inside a
-// burst: MI355X_MICROARCH.md, cycle constants).
-template <int MI, class F>
-__device__ __forceinline__ void mma_f16_kstep_fill(f32x16 (&acc)[MI][2], f32x16 (&accx)[MI][2], const unsigned char* st,
-                                                   int a_rd, int b_rd, F&& fill) {
-    f16x8 a[MI][2], b[2][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i) a[i][p] = *reinterpret_cast<const f16x8*>(st + p * PLANE_BYTES + a_rd + i * 32 * 32);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[j][p] = *reinterpret_cast<const f16x8*>(st + p * PLANE_BYTES + b_rd + j * 32 * 32);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[j][0], accx[i][j], 0, 0, 0);
-            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][1], accx[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            fill(i * 2 + j);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-}
-
 // one LDS-DMA piece (64 lanes x 16 B) as a buffer load: descriptor {base, bytes}, per-lane offset, scalar offset
 __device__ __forceinline__ void dma_piece_buffer(const unsigned char* base, int bytes, lds_u8* dst, unsigned voffset,
                                                  unsigned soffset) {
@@ -684,20 +654,18 @@ constexpr int F16_STAGE_BYTES = 3 * F16_TILE_BYTES;       // A tile 0 | A tile 1
 template <int OUT, int MI, bool ROW_SCALE = false>
 __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    static_assert(OUT == OUT_F32 || OUT == OUT_F32_RELU || OUT == OUT_H_TILED || OUT == OUT_PLANES_F16, "fp16 kernel outputs");
     constexpr int TM = F16_TM, WAVES = 16 / MI;
     constexpr int PPW = F16_STAGE_BYTES / 1024 / WAVES;   // one-KiB DMA pieces per wave per stage: 6 or 12
     if (g.f16_flags != nullptr && f16_blocked(g.f16_flags, g.f16_need)) return;   // out of fp16 range: the bf16 launch behind us runs
-    long long valid = g.num_edges ? (long long)(*g.num_edges) - g.row_begin : (long long)g.rows_valid;
-    if (valid > g.rows) valid = g.rows;
+    const long long valid = split_row_window(g);
     if (valid <= 0) return;
     const int nwg = g.tiles_n * (int)((valid + TM - 1) / TM);
     const int orig = blockIdx.x;
     if (orig >= nwg) return;
-    const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-    const int tiles_mv = nwg / g.tiles_n;
-    const int bm = (g.m_fastest ? tile % tiles_mv : tile / g.tiles_n) * TM;
-    const int bn = (g.m_fastest ? tile / tiles_mv : tile % g.tiles_n) * TN;
+    const int tile = xcd_tile(orig, nwg), tiles_mv = nwg / g.tiles_n;
+    const int bm = MDNO_SPLIT_TILE_ROW(tile, g.m_fastest, tiles_mv, g.tiles_n) * TM;
+    const int bn = MDNO_SPLIT_TILE_COL(tile, g.m_fastest, tiles_mv, g.tiles_n) * TN;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -747,6 +715,9 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
             for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; accx[i][j][e] = 0.f; }
     float bv0 = 0.f, bv1 = 0.f;      // fetched before the K loop and pinned (see gemm_split_bf16_kernel)
     float us0 = 1.f, us1 = 1.f;      // undo the power-of-two scale of the weight rows behind these two columns
+    // (the loads stay written out here and in gemm_split_bf16_tile: behind a helper the compiler forms the column
+    // address differently and the kernels' instruction sequences change; the pins differ anyway — an empty asm there,
+    // where the K loop's waits are full ones, a full wait here, where they are counted)
     if (g.bias) {
         bv0 = g.bias[bn + wn * 64 + l31];
         bv1 = g.bias[bn + wn * 64 + 32 + l31];
@@ -776,8 +747,10 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
         lds_u8* ldst = (lds_u8*)(lds + slot_in * F16_STAGE_BYTES + d0);
         // pieces of stage st+2: PPW / 2 behind the groups of each k-step (MI = 2: 3 + 3 of the 4 + 4 groups)
         constexpr int HALF = (PPW + 1) / 2;
-        // (written out rather than passed as a functor to mma_f16_kstep_fill: a lambda that touches a buffer
-        // descriptor makes the host pass drop this kernel's stub)
+        // (a k-step written out as a macro, the DMA pieces between its groups of three MFMAs, rather than a function
+        // taking the piece issue as a functor: a lambda that touches a buffer descriptor makes the host pass drop this
+        // kernel's stub.  An LDS-DMA piece costs the issuing wave 60-180 cycles, more inside a burst, so the pieces of
+        // the stage after next go out one per group, in the shadow of MFMAs already in the pipe)
 #define MDNO_F16_KSTEP_DMA(SB, P0, NP)                                                                                \
         {                                                                                                                 \
             f16x8 a_[MI][2], b_[2][2];                                                                                    \
@@ -789,9 +762,7 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
             }                                                                                                             \
             _Pragma("unroll") for (int i = 0; i < MI; ++i)                                                                \
                 _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                           \
-                    accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_[i][1], b_[j][0], accx[i][j], 0, 0, 0);         \
-                    accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_[i][0], b_[j][1], accx[i][j], 0, 0, 0);         \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_[i][0], b_[j][0], acc[i][j], 0, 0, 0);           \
+                    MDNO_MMA3_F16(a_[i], b_[j], acc[i][j], accx[i][j])                                                    \
                     __builtin_amdgcn_sched_barrier(0);                                                                    \
                     if (more && i * 2 + j < (NP))                                                                         \
                         MDNO_PIECE_DMA((P0) + i * 2 + j, ldst + ((P0) + i * 2 + j) * WAVES * 1024, ko);                   \
@@ -815,7 +786,7 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                ua[ROW_SCALE ? i : 0][e] = g.a_unscale[bm + wm * (MI * 32) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h];
+                ua[ROW_SCALE ? i : 0][e] = g.a_unscale[mfma32_row(e, h, bm + wm * (MI * 32) + i * 32)];
     }
     bool bad = false, seen = false;
 #pragma unroll
@@ -826,25 +797,11 @@ __global__ __launch_bounds__(1024 / MI) void gemm_split_f16_kernel(SplitGemmArgs
         for (int i = 0; i < MI; ++i) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = bm + wm * (MI * 32) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int m = mfma32_row(e, h, bm + wm * (MI * 32) + i * 32);
                 if (m < valid) {
                     float v = (acc[i][j][e] + accx[i][j][e] * F16_LO_UNSCALE) * us;
                     if (ROW_SCALE) v *= ua[ROW_SCALE ? i : 0][e];
-                    v += bv;
-                    if (OUT == OUT_H_TILED) {
-                        g.C[((size_t)(m >> 7) * (g.N >> 5) + (n >> 5)) * 4096 + (m & 127) * 32 + (n & 31)] = relu_f(v);
-                    } else if (OUT == OUT_PLANES_F16) {
-                        const float rv = relu_f(v);
-                        bad |= !(rv < F16_MAX);
-                        seen |= rv >= F16_ACT_MIN;
-                        _Float16 ph, pl;
-                        split2h(rv, ph, pl);
-                        const size_t o = tiled_off2(m, n, g.N >> 4, 0);
-                        *reinterpret_cast<_Float16*>(g.Cp + o) = ph;
-                        *reinterpret_cast<_Float16*>(g.Cp + o + PLANE_BYTES) = pl;
-                    } else {
-                        g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
-                    }
+                    split_store_f16<OUT>(g, m, n, v + bv, bad, seen);
                 }
             }
         }
@@ -873,22 +830,22 @@ constexpr int f16s_lds_bytes(int wm) {
 template <int OUT, int WM>
 __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    static_assert(OUT == OUT_F32 || OUT == OUT_F32_RELU || OUT == OUT_PLANES_F16, "few-rows kernel outputs (no k-tiled H)");
     constexpr int TM = 32 * WM, WAVES = 2 * WM, PPW = 2 + 4 / WM, STAGE = f16s_stage_bytes(WM);
     constexpr int A_BYTES = 4 * WM * 1024;                // A part of a stage: 4 runs (k-step, plane) of WM KiB
     const bool blocked = g.f16_flags != nullptr && f16_blocked(g.f16_flags, g.f16_need);
     if (blocked && g.Ap_b == nullptr) return;      // (the bf16 launch behind this one redoes the chunk)
     if (blocked && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(const_cast<int*>(g.f16_flags) + F16_FALLBACK_COUNT, 1);
-    long long valid = g.num_edges ? (long long)(*g.num_edges) - g.row_begin : (long long)g.rows_valid;
-    if (valid > g.rows) valid = g.rows;
+    const long long valid = split_row_window(g);
     if (valid <= 0) return;
     const int tiles_mv = (int)((valid + TM - 1) / TM);
     const int nwg = g.tiles_n * tiles_mv;
     const int orig = blockIdx.x;
     if (orig >= nwg) return;
-    // XCD x owns a contiguous run of tiles, row tiles fastest: the row tiles of one B panel are neighbours
-    const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-    const int bm = (tile % tiles_mv) * TM, bn = (tile / tiles_mv) * F16S_TN;
+    // row tiles fastest, whatever g.m_fastest says: the row tiles of one B panel are neighbours
+    const int tile = xcd_tile(orig, nwg);
+    const int bm = (tile % tiles_mv) * TM;
+    const int bn = (tile / tiles_mv) * F16S_TN;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -959,12 +916,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
                 a[p] = *reinterpret_cast<const bf16x8*>(lds + p * (WM * 1024) + a_rb);
                 b[p] = *reinterpret_cast<const bf16x8*>(lds + p * 2048 + b_rb);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+            mma6_bf16(a, b, acc);
         }
     }
 #pragma unroll
@@ -987,13 +939,11 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
         const unsigned char* sb = lds + slot * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const f16x8 a0 = *reinterpret_cast<const f16x8*>(sb + (ks * 2) * (WM * 1024) + a_rd);
-            const f16x8 a1 = *reinterpret_cast<const f16x8*>(sb + (ks * 2 + 1) * (WM * 1024) + a_rd);
-            const f16x8 b0 = *reinterpret_cast<const f16x8*>(sb + (ks * 2) * 2048 + b_rd);
-            const f16x8 b1 = *reinterpret_cast<const f16x8*>(sb + (ks * 2 + 1) * 2048 + b_rd);
-            accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, accx, 0, 0, 0);
-            accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, accx, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
+            const f16x8 a[2] = {*reinterpret_cast<const f16x8*>(sb + (ks * 2) * (WM * 1024) + a_rd),
+                                *reinterpret_cast<const f16x8*>(sb + (ks * 2 + 1) * (WM * 1024) + a_rd)};
+            const f16x8 b[2] = {*reinterpret_cast<const f16x8*>(sb + (ks * 2) * 2048 + b_rd),
+                                *reinterpret_cast<const f16x8*>(sb + (ks * 2 + 1) * 2048 + b_rd)};
+            MDNO_MMA3_F16(a, b, acc, accx)
         }
         slot = slot == F16S_RING - 1 ? 0 : slot + 1;
         slot_in = slot_in == F16S_RING - 1 ? 0 : slot_in + 1;
@@ -1003,7 +953,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
     float ua[16];      // (fetched before the first store: see gemm_split_f16_kernel)
 #pragma unroll
     for (int e = 0; e < 16; ++e)
-        ua[e] = (g.a_unscale && !blocked) ? g.a_unscale[bm + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h] : 1.f;
+        ua[e] = (g.a_unscale && !blocked) ? g.a_unscale[mfma32_row(e, h, bm + wm * 32)] : 1.f;
     bool bad = false, seen = false;
     const int n = bn + wn * 32 + l31;
     if (OUT == OUT_PLANES_F16) {
@@ -1011,11 +961,12 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
         // two-byte stores per lane.  Instead the wave turns its 32 x 32 tile through a private LDS patch (the ring is
         // idle once everybody has left the K loop) and each lane converts and stores 8 adjacent columns of a row:
         // 16 B per plane and store.  Rows of 40 floats: the two half-waves (rows r, r + 4) hit disjoint banks.
+        // (Not split_store_f16<OUT_PLANES_F16>: that one stores one element; this stores 8 columns per lane, and both images.)
         __syncthreads();
         float* patch = reinterpret_cast<float*>(lds) + wave * (32 * 40);
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-            patch[((e & 3) + 8 * (e >> 2) + 4 * h) * 40 + l31] = relu_f((acc[e] + accx[e] * F16_LO_UNSCALE) * us * ua[e] + bv);
+            patch[mfma32_row(e, h) * 40 + l31] = relu_f((acc[e] + accx[e] * F16_LO_UNSCALE) * us * ua[e] + bv);
         // (LDS operations of one wave execute in order: no wait between its writes and its reads)
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
@@ -1050,13 +1001,13 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_f16_small_kernel(SplitGem
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int m = bm + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (m < valid) {
-            const float v = (acc[e] + accx[e] * F16_LO_UNSCALE) * us * ua[e] + bv;
-            g.C[(size_t)m * g.N + n] = OUT == OUT_F32_RELU ? relu_f(v) : v;
-        }
+        const int m = mfma32_row(e, h, bm + wm * 32);
+        if (m < valid) split_store_f16<OUT>(g, m, n, (acc[e] + accx[e] * F16_LO_UNSCALE) * us * ua[e] + bv, bad, seen);
     }
 }
+
+#undef MDNO_SPLIT_TILE_ROW
+#undef MDNO_SPLIT_TILE_COL
 
 // few rows: the 256-row kernel would leave more than half of the CUs without a tile
 constexpr int F16S_MAX_BIG_TILES = 128;
@@ -1098,6 +1049,7 @@ int launch_split_f16_gemm(SplitGemmArgs g, hipStream_t s) {
         hipLaunchKernelGGL((gemm_split_f16_kernel<OUT, MI, true>), dim3(g.tiles_n * g.tiles_m), dim3(1024 / MI), lds_bytes, s, g);
         return check_launch("split-f16 GEMM");
     }
+    // (OUT_F32_RELU never gets here: its one caller, split_linear_f16, always sets a_unscale.  That instance exists, unlaunched.)
     hipLaunchKernelGGL((gemm_split_f16_kernel<OUT, MI>), dim3(g.tiles_n * g.tiles_m), dim3(1024 / MI), lds_bytes, s, g);
     return check_launch("split-f16 GEMM");
 }

@@ -34,16 +34,12 @@
 // stage t-1, whose last reads (waves 4-7, load phase t-1) completed — lgkmcnt(0) — before the barrier in
 // front of the earliest DMA issue into it.
 #include "kernels.h"
-#include "split_layout.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(1))) const unsigned char glb_u8;
 
 constexpr int PP_T = 256;                       // tile is PP_T x PP_T
 constexpr int PP_BK = 32;                       // k per stage
@@ -59,12 +55,11 @@ constexpr int PP_PIECES_PER_WAVE = PP_STAGE_BYTES / 1024 / 8;   // 4
 // EPI_SLAB: fp32 partial products of a K slice into slab z (the A^T.B products; added in slice order afterwards).
 enum { EPI_BIAS = 0, EPI_MASK = 1, EPI_SLAB = 2 };
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 // one 32x32x16 MFMA on 16-bit fragments held as bf16x8 registers: bf16, or (F16) the same bits read as fp16
 template <bool F16>
 __device__ __forceinline__ f32x16 mma16(bf16x8 a, bf16x8 b, f32x16 c) {
     if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
@@ -108,9 +103,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(PpArgs g) {
     // fastest, so that the tiles sharing an A row panel run on one L2.  Bijective for any count.
     const long long nwg = g.tiles_m * g.tiles_n;
     const long long orig = blockIdx.x;
-    const long long xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    const long long xcd_first = xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q;      // this XCD's first tile
-    const long long xcd_count = q + (xcd < r8 ? 1 : 0);
+    long long xcd_first, xcd_count;      // this XCD's first tile and how many it owns
+    xcd_tile_range(orig, nwg, xcd_first, xcd_count);
     const long long per_xcd = PERSIST ? (long long)(gridDim.x >> 3) : 0;      // workgroups per XCD (stride of the walk)
     long long loc = orig >> 3;                          // index inside the XCD's range
     if (PERSIST && loc >= xcd_count) return;
@@ -402,7 +396,7 @@ tile_loop:      // (PERSIST: one pass per tile of this workgroup; otherwise a si
             const float bv = j ? bv1 : bv0;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int r = mfma32_row(e, h);
                 float v = acc[i][j][e] + bv;
                 if (RELU) v = relu_f(v);
                 unsigned char* dst = patch + r * PATCH_ROW + (j * 32 + l31) * ESZ;

@@ -4,10 +4,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "split_mma.h"      // f32x16 (the common typedefs live there)
+
 namespace mdno {
 namespace f32mma {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int BK = 32, LD = BK + 4;
 
 __device__ __forceinline__ void mma4(const float4& a, const float4& b, f32x16& acc) {

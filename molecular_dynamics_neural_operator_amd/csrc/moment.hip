@@ -42,54 +42,14 @@
 #include "kernels.h"
 #include "mfma_f32.h"
 #include "moment_layout.h"
-#include "split_layout.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// (a, b) -> packed bf16 pair (one v_cvt_pk_bf16_f32) and the pair's values back in fp32
-__device__ __forceinline__ unsigned pack_bf16(float a, float b, float& fa, float& fb) {
-    const f32x2 v = {a, b};
-    const bf16x2 p = __builtin_convertvector(v, bf16x2);
-    const unsigned u = __builtin_bit_cast(unsigned, p);
-    fa = __builtin_bit_cast(float, u << 16);
-    fb = __builtin_bit_cast(float, u & 0xffff0000u);
-    return u;
-}
-
-// four fp32 -> 3 x four bf16 (hi, mid, lo), 8 bytes per plane at dst + p * plane_bytes
-__device__ __forceinline__ void split_store4(const float4 v, unsigned char* dst, int plane_bytes) {
-    float h0, h1, h2, h3, m0, m1, m2, m3, t0, t1;
-    uint2 hi, mid, lo;
-    hi.x = pack_bf16(v.x, v.y, h0, h1);
-    hi.y = pack_bf16(v.z, v.w, h2, h3);
-    const float r0 = v.x - h0, r1 = v.y - h1, r2 = v.z - h2, r3 = v.w - h3;
-    mid.x = pack_bf16(r0, r1, m0, m1);
-    mid.y = pack_bf16(r2, r3, m2, m3);
-    lo.x = pack_bf16(r0 - m0, r1 - m1, t0, t1);
-    lo.y = pack_bf16(r2 - m2, r3 - m3, t0, t1);
-    *reinterpret_cast<uint2*>(dst) = hi;
-    *reinterpret_cast<uint2*>(dst + plane_bytes) = mid;
-    *reinterpret_cast<uint2*>(dst + 2 * plane_bytes) = lo;
-}
-
-// the six leading plane products of (a0 + a1 + a2)(b0 + b1 + b2), smallest first
-#define MDNO_MMA6(A, B, ACC)                                                        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[1], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], B[0], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[2], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[0], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[1], ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[0], ACC, 0, 0, 0);
-
+// The plane products (mma6_bf16, mma3_f16) and the packed splits (split_store4, split2_store4) are split_mma.h's.
 // ---- two fp16 planes (gemm_mode SPLIT_F16; split_layout.h): x = hi + lo with hi = fp16(x), lo = fp16(x - hi), the lo
 // plane NOT scaled here, so that the three leading products share one accumulator (K1 has no registers for a second
 // one at three workgroups per CU).  |x - (hi + lo)| <= max(2^-23 |x|, 2^-25): the absolute floor is kept out of sight by
@@ -98,32 +58,6 @@ __device__ __forceinline__ void split_store4(const float4 v, unsigned char* dst,
 // 2^-38 of the row's / column's largest entry; K1: the feature rows by the largest |feature| among the destination's
 // neighbours (likewise), H by 2^5 (floor 2^-30; a workgroup whose H holds a value >= 2047 or none >= 2^-7 redoes its
 // destination on the bf16 planes — a decision that depends on that destination's own edges only).
-// (a, b) -> packed fp16 pair (one v_cvt_pk_f16_f32 on gfx950) and the pair's values back in fp32
-__device__ __forceinline__ unsigned pack_f16(float a, float b, float& fa, float& fb) {
-    const f32x2 v = {a, b};
-    const f16x2 p = __builtin_convertvector(v, f16x2);
-    fa = (float)p.x;
-    fb = (float)p.y;
-    return __builtin_bit_cast(unsigned, p);
-}
-
-// four fp32 (already scaled) -> 2 x four fp16 (hi, lo), 8 bytes per plane at dst + p * plane_bytes
-__device__ __forceinline__ void split2_store4(const float4 v, unsigned char* dst, int plane_bytes) {
-    float h0, h1, h2, h3, t0, t1;
-    uint2 hi, lo;
-    hi.x = pack_f16(v.x, v.y, h0, h1);
-    hi.y = pack_f16(v.z, v.w, h2, h3);
-    lo.x = pack_f16(v.x - h0, v.y - h1, t0, t1);
-    lo.y = pack_f16(v.z - h2, v.w - h3, t0, t1);
-    *reinterpret_cast<uint2*>(dst) = hi;
-    *reinterpret_cast<uint2*>(dst + plane_bytes) = lo;
-}
-
-// the three leading plane products of (a0 + a1)(b0 + b1), smallest first
-#define MDNO_MMA3H(A, B, ACC)                                                       \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], B[0], ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[1], ACC, 0, 0, 0);         \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[0], ACC, 0, 0, 0);
 
 // ---------------------------------------------------------------- W3 [64*64, k] -> W3R tiled [64k/32][64 o][32]
 // W3R[kappa][o] = W3[(i*64 + o)*k + c] with kappa = i*k + c (and B3[i][o] at kappa = 64 k + i): the B operand of K2,
@@ -465,8 +399,8 @@ __global__ __launch_bounds__(256, 3) void moment_kernel(const float* __restrict_
                     for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
                         for (int p = 0; p < 2; ++p) b[p] = __builtin_bit_cast(f16x8, tr_frag(hb + p * MO_HPLANE + cb * 64, MO_HROW));
-                        MDNO_MMA3H(a[0], b, acc[0][cb])
-                        MDNO_MMA3H(a[1], b, acc[1][cb])
+                        mma3_f16(a[0], b, acc[0][cb]);
+                        mma3_f16(a[1], b, acc[1][cb]);
                     }
                 } else {
                     bf16x8 a[2][3], b[3];
@@ -479,8 +413,8 @@ __global__ __launch_bounds__(256, 3) void moment_kernel(const float* __restrict_
                     for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
                         for (int p = 0; p < 3; ++p) b[p] = __builtin_bit_cast(bf16x8, tr_frag(hb + p * MO_HPLANE + cb * 64, MO_HROW));
-                        MDNO_MMA6(a[0], b, acc[0][cb])
-                        MDNO_MMA6(a[1], b, acc[1][cb])
+                        mma6_bf16(a[0], b, acc[0][cb]);
+                        mma6_bf16(a[1], b, acc[1][cb]);
                     }
                 }
             }
@@ -517,7 +451,7 @@ __global__ __launch_bounds__(256, 3) void moment_kernel(const float* __restrict_
                 const int c0 = cq * MO_CQ + wave * 64 + cb * 32;      // multiple of 32
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int i = ih * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int i = mfma32_row(e, h, ih * 32);
                     const size_t kt = ((size_t)i * K + c0) >> 5;
                     const float v = acc[ih][cb][e];
                     Sb[kt * 4096] = v;
@@ -608,7 +542,7 @@ __global__ __launch_bounds__(256) void moment_f32_kernel(const float* __restrict
             const int c0 = cq * MO_CQ + wave * 64 + cb * 32;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int i = ih * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int i = mfma32_row(e, h, ih * 32);
                 const size_t kt = ((size_t)i * K + c0) >> 5;
                 Sb[kt * 4096] = acc[ih][cb][e];
             }
@@ -703,7 +637,7 @@ __global__ __launch_bounds__(PJ_ROWS * 2) void project_kernel(const float* __res
             b0[p] = *reinterpret_cast<const bf16x8*>(b_rd0 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw0) << 4)); \
             b1[p] = *reinterpret_cast<const bf16x8*>(b_rd1 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw1) << 4)); \
         }                                                                                                \
-        MDNO_MMA6(a, b0, acc0) MDNO_MMA6(a, b1, acc1)                                                    \
+        mma6_bf16(a, b0, acc0); mma6_bf16(a, b1, acc1);                                                  \
     }
     const bool rows_live = wave < live;
     Tile P, Q;
@@ -735,7 +669,7 @@ __global__ __launch_bounds__(PJ_ROWS * 2) void project_kernel(const float* __res
     float* Po = part + (size_t)slice * part_stride;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int m = first + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int m = mfma32_row(e, h, first + wave * 32);
         if (m < cnt) {
             Po[(size_t)(row0 + m) * 64 + l31] = acc0[e];
             Po[(size_t)(row0 + m) * 64 + 32 + l31] = acc1[e];
@@ -833,7 +767,7 @@ __global__ __launch_bounds__(512) void project_f16_kernel(const float* __restric
             b0[p] = *reinterpret_cast<const f16x8*>(b_rd0 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw0) << 4)); \
             b1[p] = *reinterpret_cast<const f16x8*>(b_rd1 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw1) << 4)); \
         }                                                                                                \
-        MDNO_MMA3H(a, b0, acc0) MDNO_MMA3H(a, b1, acc1)                                                  \
+        mma3_f16(a, b0, acc0); mma3_f16(a, b1, acc1);                                                    \
     }
     const bool rows_live = wave < live;
     Tile P, Q;
@@ -865,7 +799,7 @@ __global__ __launch_bounds__(512) void project_f16_kernel(const float* __restric
     float* Po = part + (size_t)slice * part_stride;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int ml = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, m = first + ml;
+        const int ml = mfma32_row(e, h, wave * 32), m = first + ml;
         if (m < cnt) {
             const int er = rowexp[ml];
             Po[(size_t)(row0 + m) * 64 + l31] = ldexpf(acc0[e], ec0 - er);
@@ -915,7 +849,7 @@ __global__ __launch_bounds__(256) void project_f32_kernel(const float* __restric
     float* Po = part + (size_t)slice * part_stride;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int m = first + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int m = mfma32_row(e, h, first + wave * 32);
         if (m < cnt) {
             Po[(size_t)(row0 + m) * 64 + l31] = acc0[e];
             Po[(size_t)(row0 + m) * 64 + 32 + l31] = acc1[e];

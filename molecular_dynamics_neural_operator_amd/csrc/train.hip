@@ -7,11 +7,11 @@
 #include "kernels.h"
 #include "mfma_f32.h"
 #include "reduce.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
 
-using f32mma::f32x16;
 using f32mma::mma_64x64;
 constexpr int BK = f32mma::BK, LD = f32mma::LD;
 
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const float* __rest
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int m = mfma32_row(e, h, bm + wm * 64 + i * 32);
                 if (m < rows) {
                     float v = acc[i][j][e] + bv;
                     if (RELU) v = relu_f(v);
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void gemm_atb_mfma_kernel(const float* __re
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int m = mfma32_row(e, h, bm + wm * 64 + i * 32);
                 P[(size_t)m * N2 + n] = acc[i][j][e];
             }
     }

@@ -16,12 +16,10 @@
 #include "bf16.h"
 #include "kernels.h"
 #include "reduce.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------- cast
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ in, long long n4,
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const __bf16* __restr
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const long long m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const long long m = mfma32_row(e, h, bm + wm * 64 + i * 32);
                 if (m < rows) {
                     float v = acc[i][j][e] + bv;
                     if (RELU) v = relu_f(v);
@@ -311,7 +309,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const __bf16* __restr
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = bm + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int m = mfma32_row(e, h, bm + wm * 64 + i * 32);
                 P[(size_t)m * n2 + n] = acc[i][j][e];
             }
     }

@@ -18,12 +18,10 @@
 #include "conv64.h"
 #include "kernels.h"
 #include "reduce.h"
+#include "split_mma.h"
 
 namespace mdno {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __global__ __launch_bounds__(256) void inv_degree_kernel(const int* __restrict__ row_ptr, int rows, int mean,
                                                          float* __restrict__ inv) {
@@ -321,13 +319,9 @@ __global__ __launch_bounds__(256, 2) void nnconv_bwd_we_mfma_kernel(const float*
         for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
             for (int ib = 0; ib < 2; ++ib) {
-                const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][1], b[ib][1], zero, 0, 0, 0);      // (C = inline 0)
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][2], b[ib][0], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][2], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][1], b[ib][0], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][1], acc[ob][ib], 0, 0, 0);
-                acc[ob][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ob][0], b[ib][0], acc[ob][ib], 0, 0, 0);
+                // (a constant zero: the first product's C operand is the inline 0, no accumulator is cleared)
+                acc[ob][ib] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                mma6_bf16(a[ob], b[ib], acc[ob][ib]);
             }
         // tile -> LDS [i][o] (a wave's own tile: no workgroup barrier); four consecutive o per write
 #pragma unroll

@@ -13,7 +13,10 @@ pytestmark = pytest.mark.gpu
 GEMM_MODES = ("f32", "split_bf16", "split_f16")
 # (members x atoms, ker_width, depth): a single sample; 3 x 70; R = 522 crosses the 512-destination chunk; R = 74.
 # None of the row counts is a multiple of 64.  The oracle's fp64 W_e is E * 32 KiB: <= 0.9 GB at 9 x 58 (E = 28k).
-CASES = {"single": ((1, 90), 128, 1), "3x70": ((3, 70), 256, 2), "9x58": ((9, 58), 128, 2), "2x37": ((2, 37), 256, 1)}
+# k384 (a half-live second block of 256 hidden units; no multiple of 256 for the split-f16 gemm_atb below H) and k1024
+# (the width of the N = 504 box) on small boxes: E = 2,652 and 1,462.
+CASES = {"single": ((1, 90), 128, 1), "3x70": ((3, 70), 256, 2), "9x58": ((9, 58), 128, 2), "2x37": ((2, 37), 256, 1),
+         "k384": ((2, 37), 384, 2), "k1024": ((1, 40), 1024, 1)}
 WINDOW = 4
 
 

@@ -161,6 +161,17 @@ TRAIN_SIGNATURES = {
                                    _SZ, _P]),
 }
 
+# include/mdno_noise.h (seeded Gaussian noise on the device; additive, no version number of its own): name ->
+# (restype, argtypes), kept in step with that header (tests/test_noise_host.py checks both ways)
+_U64 = C.c_uint64
+_F = C.c_float
+NOISE_PURPOSES = {"rollout": 0, "train_window": 1}
+NOISE_SIGNATURES = {
+    "mdno_noise_fill": (_I, [_U64, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P]),
+    "mdno_noise_add_window": (_I, [_U64, _P, _P, _I, _I, _L, _I, _L, _F, _P, _P, _P]),
+    "mdno_rollout_plan_set_noise": (_I, [_P, _F, _U64, _P]),
+}
+
 _lib = None
 
 
@@ -191,7 +202,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP library is not built. Run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

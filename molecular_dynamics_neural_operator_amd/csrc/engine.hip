@@ -11,6 +11,7 @@
 // all 2*depth conv applications use the same W_e = net(edge_attr).  It is evaluated once per
 // forward instead of 2*depth times.
 #include "kernels.h"
+#include "../../include/mdno_noise.h"
 
 #include <string>
 #include <vector>
@@ -354,6 +355,11 @@ struct mdno_rollout_plan {
     hipGraphExec_t exec_n;
     Timer* timer;
     bool weights_cached;   // weight-derived operands are rebuilt per plan_run call, not per step
+    // stochastic rollout (mdno_rollout_plan_set_noise): sigma == 0 -> none of it is launched or captured
+    float noise_sigma;
+    unsigned long long noise_seed;
+    const int* noise_members;
+    hipStream_t capture_stream;      // the stream the graphs were captured on (NULL: plain launches)
 };
 
 static void plan_counter_words(const mdno_rollout_plan* pl, int** conv, int** mlp) {
@@ -389,15 +395,28 @@ static int plan_enqueue_step(mdno_rollout_plan* pl, hipStream_t s) {
                               pl->r.graph_scratch, pl->r.graph_scratch_bytes));
     const StepTail tail{pl->r.t_dev, pl->r.num_edges, pl->edges_per_step, pl->r.t_dev + 1,
                         (long long)pl->M * pl->N <= 256 ? pl->r.row_done : nullptr};
-    return forward_impl(&pl->p, pl->traj, 0, pl->r.t_dev, pl->M, W, pl->N, pl->aa, pl->aa_per_member, pl->r.row_ptr,
-                        pl->r.src, pl->r.dst, pl->r.num_edges, pl->edge_cap, pl->traj, W - 1, nullptr,
-                        nullptr, pl->traj, W, nullptr, pl->fw, pl->status, s,
-                        (pl->weights_cached ? WP_RUN_ONLY : WP_BOTH) | (act_flags ? WP_FLAGS_ZEROED : 0) |
-                            (head ? WP_PROLOGUE_DONE : 0),
-                        &tail);
+    MDNO_TRY(forward_impl(&pl->p, pl->traj, 0, pl->r.t_dev, pl->M, W, pl->N, pl->aa, pl->aa_per_member, pl->r.row_ptr,
+                          pl->r.src, pl->r.dst, pl->r.num_edges, pl->edge_cap, pl->traj, W - 1, nullptr,
+                          nullptr, pl->traj, W, nullptr, pl->fw, pl->status, s,
+                          (pl->weights_cached ? WP_RUN_ONLY : WP_BOTH) | (act_flags ? WP_FLAGS_ZEROED : 0) |
+                              (head ? WP_PROLOGUE_DONE : 0),
+                          &tail));
+    // the new frame is perturbed where it lies, before the next step's graph and windows read it
+    if (pl->noise_sigma != 0.f)
+        MDNO_TRY(noise_step(pl->traj, W, pl->r.t_dev, pl->M, pl->N, pl->noise_members, pl->noise_seed, pl->noise_sigma, s));
+    return MDNO_OK;
 }
 
 constexpr int kStepsPerGraph = 8;
+
+static void plan_drop_graphs(mdno_rollout_plan* pl) {
+    if (pl->exec) (void)hipGraphExecDestroy(pl->exec);
+    if (pl->graph) (void)hipGraphDestroy(pl->graph);
+    if (pl->exec_n) (void)hipGraphExecDestroy(pl->exec_n);
+    if (pl->graph_n) (void)hipGraphDestroy(pl->graph_n);
+    pl->exec = pl->exec_n = nullptr;
+    pl->graph = pl->graph_n = nullptr;
+}
 
 // `n` consecutive steps captured on `s` -> executable graph
 static int capture_steps(mdno_rollout_plan* pl, hipStream_t s, int n, hipGraph_t* graph, hipGraphExec_t* exec) {
@@ -422,6 +441,8 @@ static int capture_steps(mdno_rollout_plan* pl, hipStream_t s, int n, hipGraph_t
     }
     return MDNO_OK;
 }
+
+static int plan_capture(mdno_rollout_plan* pl);
 
 extern "C" int mdno_rollout_plan_create(mdno_rollout_plan** plan, const mdno_kernelnn_params* p, float* traj, int M,
                                         int W, int N, int max_steps, const int64_t* x_aminoacid, int aa_per_member,
@@ -454,19 +475,8 @@ extern "C" int mdno_rollout_plan_create(mdno_rollout_plan** plan, const mdno_ker
     pl->weights_cached = !separate_conv2_kernel(p);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (use_graph && s != nullptr) {
-        int rc = capture_steps(pl, s, 1, &pl->graph, &pl->exec);
-        // a short chain's step is a few dozen launches of a few microseconds: several steps per graph launch
-        if (rc == MDNO_OK && max_steps >= kStepsPerGraph && step_head_small_supported(M, N) &&
-            capture_steps(pl, s, kStepsPerGraph, &pl->graph_n, &pl->exec_n) != MDNO_OK) {
-            // the many-steps graph is an optimisation: without it the single-step graph above replays every step.  Said
-            // once on stderr (a short chain then runs at a fraction of its rate) and visible to the caller through
-            // mdno_rollout_plan_steps_per_launch; the plan itself is good, so the error string is not left behind
-            fprintf(stderr, "libmdno: the %d-steps-per-launch graph could not be built (%s); replaying single steps\n",
-                    kStepsPerGraph, mdno_last_error());
-            set_error("%s", "");
-            pl->graph_n = nullptr;
-            pl->exec_n = nullptr;
-        }
+        pl->capture_stream = s;
+        int rc = plan_capture(pl);
         if (rc != MDNO_OK) {
             mdno_rollout_plan_destroy(pl);
             return rc;
@@ -474,6 +484,45 @@ extern "C" int mdno_rollout_plan_create(mdno_rollout_plan** plan, const mdno_ker
     }
     *plan = pl;
     return MDNO_OK;
+}
+
+// the plan's step as it is now (with or without noise) -> its executable graphs on pl->capture_stream
+static int plan_capture(mdno_rollout_plan* pl) {
+    hipStream_t s = pl->capture_stream;
+    MDNO_TRY(capture_steps(pl, s, 1, &pl->graph, &pl->exec));
+    // a short chain's step is a few dozen launches of a few microseconds: several steps per graph launch
+    if (pl->max_steps >= kStepsPerGraph && step_head_small_supported(pl->M, pl->N) &&
+        capture_steps(pl, s, kStepsPerGraph, &pl->graph_n, &pl->exec_n) != MDNO_OK) {
+        // the many-steps graph is an optimisation: without it the single-step graph above replays every step.  Said
+        // once on stderr (a short chain then runs at a fraction of its rate) and visible to the caller through
+        // mdno_rollout_plan_steps_per_launch; the plan itself is good, so the error string is not left behind
+        fprintf(stderr, "libmdno: the %d-steps-per-launch graph could not be built (%s); replaying single steps\n",
+                kStepsPerGraph, mdno_last_error());
+        set_error("%s", "");
+        pl->graph_n = nullptr;
+        pl->exec_n = nullptr;
+    }
+    return MDNO_OK;
+}
+
+extern "C" int mdno_rollout_plan_set_noise(mdno_rollout_plan* pl, float sigma, uint64_t seed, const int32_t* member_ids) {
+    MDNO_REQUIRE(pl != nullptr, MDNO_EINVAL, "mdno_rollout_plan_set_noise: null plan");
+    MDNO_REQUIRE(sigma >= 0.f && sigma < INFINITY, MDNO_EINVAL, "mdno_rollout_plan_set_noise: sigma=%g", (double)sigma);
+    MDNO_REQUIRE(sigma == 0.f || member_ids != nullptr, MDNO_EINVAL, "mdno_rollout_plan_set_noise: null member_ids");
+    MDNO_REQUIRE(sigma == 0.f || pl->M <= 65535, MDNO_EINVAL, "mdno_rollout_plan_set_noise: M=%d (at most 65535 members per plan)", pl->M);
+    const bool was = pl->noise_sigma != 0.f, now = sigma != 0.f;
+    const bool same = was == now && (!now || (pl->noise_sigma == sigma && pl->noise_seed == seed && pl->noise_members == member_ids));
+    pl->noise_sigma = sigma;
+    pl->noise_seed = (unsigned long long)seed;
+    pl->noise_members = now ? member_ids : nullptr;
+    if (same || !pl->capture_stream) return MDNO_OK;
+    // the captured step holds the noise launch (or its absence) and its arguments: capture it again.  (A plan that is
+    // given noise right after its creation has thus captured its graphs twice, per creation and per regrown capacity:
+    // a cost of the noise-on path only, kept so that mdno_rollout_plan_create stays as it is.  If the capture fails
+    // here the error is returned and the plan is left WITHOUT graphs: it would run plain launches, same frames.)
+    MDNO_HIP(hipStreamSynchronize(pl->capture_stream));
+    plan_drop_graphs(pl);
+    return plan_capture(pl);
 }
 
 extern "C" int mdno_rollout_plan_steps_per_launch(mdno_rollout_plan* plan) {
@@ -573,10 +622,7 @@ extern "C" int mdno_rollout_plan_fallback_counts(mdno_rollout_plan* pl, int64_t 
 extern "C" int mdno_rollout_plan_destroy(mdno_rollout_plan* pl) {
     if (!pl) return MDNO_OK;
     (void)mdno_rollout_plan_timer_detach(pl);
-    if (pl->exec) (void)hipGraphExecDestroy(pl->exec);
-    if (pl->graph) (void)hipGraphDestroy(pl->graph);
-    if (pl->exec_n) (void)hipGraphExecDestroy(pl->exec_n);
-    if (pl->graph_n) (void)hipGraphDestroy(pl->graph_n);
+    plan_drop_graphs(pl);
     delete pl;
     return MDNO_OK;
 }

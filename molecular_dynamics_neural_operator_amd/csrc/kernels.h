@@ -201,4 +201,9 @@ int step_head_small(const mdno_kernelnn_params* p, const float* frames, int W, c
 int fc_out(const float* x, const float* w, const float* b, int rows, int width, int out_width, float* out_frames,
            int t_out, const int* t_dev, hipStream_t s, const StepTail* tail = nullptr);
 
+// Stochastic rollout (noise.hip, philox.h): traj[W + step][m][a][c] += sigma * z(seed, member_ids[m], step, a * 3 + c) for
+// the step whose tail has just moved the counter on (step = *t_dev - 1: the absolute step number, whatever launched it)
+int noise_step(float* traj, int W, const int* t_dev, int M, int N, const int* member_ids, unsigned long long seed,
+               float sigma, hipStream_t s);
+
 }  // namespace mdno

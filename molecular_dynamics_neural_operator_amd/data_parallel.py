@@ -200,13 +200,13 @@ class DataParallelTrainer:
                 raise ValueError("`source` is given, but a batch holds PairData samples")
         check_batch_lists(batches, self.coll.group)
 
-    def _shard(self, batch, source):
+    def _shard(self, batch, source, noise=None):
         B = len(batch)
         s, e = shard_range(B, self.rank, self.world)
         if e == s:
             return B, 0, None, None
         if source is not None:
-            data = source.batch(np.asarray(batch, dtype=np.int64).reshape(-1)[s:e])
+            data = source.batch(np.asarray(batch, dtype=np.int64).reshape(-1)[s:e], **(noise or {}))
             return B, e - s, data, data.y
         part = list(batch[s:e])
         return B, e - s, part, torch.cat([x.y for x in part])
@@ -246,17 +246,24 @@ class DataParallelTrainer:
         check_train_status(model)
         return combine_losses(vals.cpu().tolist() if per else [], sizes, size_average)
 
-    def train_epoch(self, batches, source=None) -> Tuple[float, float]:
+    def train_epoch(self, batches, source=None, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0) -> Tuple[float, float]:
         """One training pass over the global batch list (lists of PairData, or lists of sample indices into `source`,
-        a DeviceTrajectory) -> (avg relative-L2 loss, avg MSE), the same numbers on every rank."""
+        a DeviceTrajectory) -> (avg relative-L2 loss, avg MSE), the same numbers on every rank.
+        noise_std > 0 (index batches only): `source.batch(..., noise_std, noise_seed, epoch)` — keyed by dataset index,
+        so a sample's noise is the same on whichever rank its shard falls."""
         batches = list(batches)
         self._check_batches(batches, source)
+        noise = None
+        if float(noise_std) != 0.0:
+            if source is None:
+                raise ValueError("noise_std needs batches of sample indices and `source` (a DeviceTrajectory)")
+            noise = dict(noise_std=float(noise_std), noise_seed=int(noise_seed), epoch=int(epoch))
         model, opt = self.model, self.optimizer
         sa = bool(self.loss_fn.size_average)
         model.train()
         per, weights, sizes = [], [], []
         for batch in batches:
-            B, Br, data, y = self._shard(batch, source)
+            B, Br, data, y = self._shard(batch, source, noise)
             opt.zero_grad(set_to_none=True)
             e0 = self._event() if self.timing else None
             if Br:

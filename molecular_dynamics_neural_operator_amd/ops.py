@@ -907,6 +907,71 @@ def collate_samples(pos: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor, m
 
 
 # ------------------------------------------------------------------------------------------------
+def _noise_seed(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise MdnoError(f"noise seed {seed} outside [0, 2^64)")
+    return seed
+
+
+def _noise_ids(ids, dev, what: str) -> torch.Tensor:
+    """Stream ids (members, sample indices) as the int32 device vector the kernels read."""
+    t = torch.as_tensor(ids).reshape(-1)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise MdnoError(f"{what} must be integers")
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 2 ** 31):
+        raise MdnoError(f"{what} must lie in [0, 2^31)")
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def noise_fill(seed: int, stream_ids, index: int, n_atoms: int, frames: int = 1, purpose="rollout", sigma: float = 1.0,
+               device=None, with_words: bool = False):
+    """The raw generator (include/mdno_noise.h mdno_noise_fill; csrc/philox.h): sigma * z for every stream of
+    `stream_ids` (ints or an integer tensor [M]) at `index` (step or epoch, < 2^48) -> f32 [M, frames * n_atoms * 3],
+    element (frame * n_atoms + atom) * 3 + component; with `with_words` also the two Philox words behind every value,
+    u32 as int64 [M, elems, 2].  purpose: "rollout" / "train_window" (or its number)."""
+    lib = _lib.load()
+    dev = _lib.require_gpu(device)
+    ids = _noise_ids(stream_ids, dev, "stream_ids")
+    M, E = int(ids.numel()), int(frames) * int(n_atoms) * 3
+    if isinstance(purpose, str):
+        if purpose not in _lib.NOISE_PURPOSES:
+            raise MdnoError(f"purpose={purpose!r}: expected one of {sorted(_lib.NOISE_PURPOSES)} or a number in [0, 256)")
+        purpose = _lib.NOISE_PURPOSES[purpose]
+    if not isinstance(purpose, int) or isinstance(purpose, bool) or not 0 <= purpose < 256:
+        raise MdnoError(f"purpose={purpose!r}: expected one of {sorted(_lib.NOISE_PURPOSES)} or a number in [0, 256)")
+    z = torch.empty((M, E), dtype=torch.float32, device=dev)
+    words = torch.empty((M, E, 2), dtype=torch.int32, device=dev) if with_words else None
+    check(lib.mdno_noise_fill(_noise_seed(seed), ptr(ids), M, int(index), int(n_atoms), E,
+                              purpose, float(sigma), ptr(z), ptr(words), stream_ptr(dev)),
+          "mdno_noise_fill")
+    if with_words:
+        return z, words.to(torch.int64) & 0xFFFFFFFF
+    return z
+
+
+def noise_add_window(x_position: torch.Tensor, sample_ids, row_offsets: torch.Tensor, max_rows: int, sigma: float,
+                     seed: int, epoch: int) -> torch.Tensor:
+    """x_position f32 [W, R, 3] of a collated batch + sigma * z, as a new tensor (include/mdno_noise.h
+    mdno_noise_add_window): sample b owns rows row_offsets[b] .. row_offsets[b+1]-1 (i32 [B+1] on the device) and draws
+    from stream sample_ids[b] (its index in the dataset) at index `epoch`."""
+    lib = _lib.load()
+    x = f32(x_position)
+    dev = x.device
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise MdnoError(f"x_position shape {tuple(x.shape)}: expected [W, R, 3]")
+    ids = _noise_ids(sample_ids, dev, "sample_ids")
+    B = int(ids.numel())
+    if row_offsets.dtype != torch.int32 or row_offsets.numel() != B + 1:
+        raise MdnoError("row_offsets must be int32 [B + 1]")
+    out = torch.empty_like(x)
+    check(lib.mdno_noise_add_window(_noise_seed(seed), ptr(ids), ptr(row_offsets), B, int(x.shape[0]), int(x.shape[1]),
+                                    int(max_rows), int(epoch), float(sigma), ptr(x), ptr(out), stream_ptr(dev)),
+          "mdno_noise_add_window")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 def lploss_rel_fwd(out: torch.Tensor, y: torch.Tensor, size_average: bool):
     """LpLoss.rel, p = 2, and the batch MSE in one pass (include/mdno.h mdno_lploss_rel_fwd): out, y f32 [B, D] ->
     (loss_mse f32 [2] = [loss, mse], stats f32 [B, 4] for the backward)."""

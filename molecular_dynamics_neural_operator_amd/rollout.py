@@ -41,10 +41,17 @@ AUTO_MATERIALIZED_MAX_WORKSPACE = 64 << 30
 
 
 class RolloutEngine:
-    """Owns the trajectory buffer [W+max_steps, M, N, 3], the workspace and the captured step."""
+    """Owns the trajectory buffer [W+max_steps, M, N, 3], the workspace and the captured step.
+
+    noise_sigma > 0: a stochastic rollout (include/mdno_noise.h mdno_rollout_plan_set_noise) —
+    every step adds noise_sigma * z(noise_seed, member_ids[m], absolute step, atom, component) to the frame it produces,
+    before the frame is stored and read again.  `member_ids` (default 0 .. M-1) are the members' GLOBAL ids: member g
+    draws the same noise alone, in any batch, group or rank (pass `shard_members(...)` on a rank).  With noise_sigma = 0
+    (the default) nothing of this is launched or captured."""
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0,
-                 max_steps: int = 1000, edge_cap: Optional[int] = None, device=None, use_graph: bool = True):
+                 max_steps: int = 1000, edge_cap: Optional[int] = None, device=None, use_graph: bool = True,
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None):
         self.lib = _lib.load()
         self.device = require_gpu(device if device not in (None, "cuda") else None)
         fc2 = getattr(model, "fc2", None)
@@ -55,6 +62,14 @@ class RolloutEngine:
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
         self.threshold = float(threshold)
         self.max_steps = int(max_steps)
+        self.noise_sigma, self.noise_seed = float(noise_sigma), int(noise_seed)
+        if not (0.0 <= self.noise_sigma < float("inf")) or not 0 <= self.noise_seed < 2 ** 64:
+            raise MdnoError(f"noise_sigma={noise_sigma} must be finite and >= 0, noise_seed={noise_seed} in [0, 2^64)")
+        ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
+        if len(ids) != self.M or any(not 0 <= i < 2 ** 31 for i in ids):
+            raise MdnoError(f"member_ids: expected {self.M} ids in [0, 2^31), got {ids[:8]}{'..' if len(ids) > 8 else ''}")
+        self.member_ids = ids
+        self._member_ids_dev = None      # int32 [M] on the device, made when noise is on (the plan keeps its address)
         self.edge_cap = int(edge_cap) if edge_cap is not None else self.M * self.N * self.N
         self.edge_cap = max(self.edge_cap, self.M * self.N)
         # no capacity given and the complete-graph bound is large (N > 256): the capacity is fitted to the graph of
@@ -151,6 +166,11 @@ class RolloutEngine:
             self.workspace.numel(),
             ptr(self.edges_per_step), ptr(self.status), int(self.use_graph), self.stream.cuda_stream),
             "mdno_rollout_plan_create")
+        if self.noise_sigma > 0.0:       # (a rebuilt plan — regrown capacity — draws the same noise for the same steps)
+            if self._member_ids_dev is None:
+                self._member_ids_dev = torch.tensor(self.member_ids, dtype=torch.int32, device=self.device)
+            check(self.lib.mdno_rollout_plan_set_noise(self.plan, self.noise_sigma, self.noise_seed,
+                                                       ptr(self._member_ids_dev)), "mdno_rollout_plan_set_noise")
         if self._timer_records:          # the timer lived in the plan just destroyed: its records are gone, the attachment is not
             check(self.lib.mdno_rollout_plan_timer_attach(self.plan, self._timer_records), "timer_attach")
 
@@ -203,13 +223,17 @@ class RolloutEngine:
         """Produce frame W from the start sample's OWN graph and edge attributes, as the reference's
         first loop iteration does (graph_kernel.py:401-404: `dataset[start]` carries the graph of the
         window's FIRST frame, dataset.py:189-201; only later steps rebuild it on the newest frame).
-        Single-member engines only; call after reset()."""
+        Single-member engines only; call after reset().  With noise_sigma > 0 the frame gets the noise of step 0 like
+        any other step's (the values `ops.noise_fill` gives for this member, added in the same fp32 arithmetic)."""
         if self.M != 1 or self.steps_done != 0:
             raise MdnoError("first_step_from_sample: needs M == 1 and a freshly reset engine")
         graph = ops.coo_to_csr(edge_index.to(self.device), self.N)
         # an explicit edge list runs in the engine's own formulation (the factored form takes any destination-sorted graph)
         out, _ = ops.kernelnn_forward(self.pack, self.traj[:self.W], self.aa, graph,
                                       edge_attr=edge_attr.to(self.device))
+        if self.noise_sigma > 0.0:
+            out = out + ops.noise_fill(self.noise_seed, self.member_ids, 0, self.N, sigma=self.noise_sigma,
+                                       device=self.device).view(self.N, 3)
         self.traj[self.W, 0].copy_(out)
         self.edges_per_step[0] = int(edge_index.shape[1])
         torch.cuda.current_stream(self.device).synchronize()
@@ -363,8 +387,13 @@ class GroupedRolloutEngine:
     reset / step / synchronize / run / frames interface; `traj` and `edges_per_step` are assembled on access."""
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0, max_steps: int = 1000,
-                 edge_cap: Optional[int] = None, device=None, use_graph: bool = True, groups: int = 2):
+                 edge_cap: Optional[int] = None, device=None, use_graph: bool = True, groups: int = 2,
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None):
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
+        ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
+        if len(ids) != self.M:
+            raise MdnoError(f"member_ids: expected {self.M} ids, got {len(ids)}")
+        self.member_ids = ids
         g = max(1, min(int(groups), self.M))
         base, extra = divmod(self.M, g)
         self.bounds, lo = [], 0
@@ -374,7 +403,8 @@ class GroupedRolloutEngine:
             lo = hi
         self.engines = [RolloutEngine(model, hi - lo, n_atoms, window, threshold, max_steps=max_steps,
                                       edge_cap=None if edge_cap is None else max(1, -(-int(edge_cap) * (hi - lo) // self.M)),
-                                      device=device, use_graph=use_graph) for lo, hi in self.bounds]
+                                      device=device, use_graph=use_graph, noise_sigma=noise_sigma, noise_seed=noise_seed,
+                                      member_ids=ids[lo:hi]) for lo, hi in self.bounds]
         self.device = self.engines[0].device
         self.max_steps = int(max_steps)
 

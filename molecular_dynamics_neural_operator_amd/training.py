@@ -253,7 +253,11 @@ class DeviceTrajectory:
         first = start + self.W + self.horizon - 1
         return self.pos[first:first + steps]
 
-    def batch(self, indices) -> PairData:
+    def batch(self, indices, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0) -> PairData:
+        """noise_std > 0: the input windows (`x_position` only — `y`, `edge_attr` and `edge_index` stay clean) get
+        noise_std * z(noise_seed, sample index, epoch, frame, atom, component) added on the device (include/mdno_noise.h
+        mdno_noise_add_window).  The key is the sample's index in the dataset: a sample's noise does not depend on the
+        batch it is in, the batch size or the rank.  The batch carries `sample_ids` / `rows_per_sample` either way."""
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.length:
             raise IndexError(f"sample indices must lie in [0, {self.length})")
@@ -275,7 +279,24 @@ class DeviceTrajectory:
             self._aa_tiled[B] = self.x_aminoacid.repeat(B)
         out = PairData(x_aminoacid=self._aa_tiled[B], x_position=xp, y=y, edge_attr=ea, edge_index=ei)
         out.num_graphs = B
+        out.sample_ids, out.rows_per_sample = idx.copy(), self.N
+        if float(noise_std) != 0.0:
+            out.x_position = add_window_noise(out, noise_std, noise_seed, epoch)
         return out
+
+
+def add_window_noise(batch: PairData, noise_std: float, noise_seed: int = 0, epoch: int = 0) -> torch.Tensor:
+    """The noisy `x_position` [W, B*N, 3] of a collated batch made by `DeviceTrajectory.batch` (it knows which dataset
+    sample every row belongs to): a new tensor, the batch itself is left as it is."""
+    ids = getattr(batch, "sample_ids", None)
+    if ids is None:
+        raise MdnoError("window noise needs batches from DeviceTrajectory.batch (they carry their samples' dataset "
+                        "indices); host-collated samples have none")
+    if not (0.0 <= float(noise_std) < float("inf")):
+        raise MdnoError(f"noise_std={noise_std} must be finite and >= 0")
+    n, dev = int(batch.rows_per_sample), batch.x_position.device
+    offs = torch.arange(0, (len(ids) + 1) * n, n, dtype=torch.int32, device=dev)
+    return ops.noise_add_window(batch.x_position, ids, offs, n, noise_std, noise_seed, epoch)
 
 
 # Longest window the prologue backward keeps per atom (csrc/train_nodes.hip MAX_W), largest embedding it handles
@@ -467,12 +488,16 @@ class Adam(torch.optim.Optimizer):
         return loss
 
 
-def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = None):
+def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = None, noise_std: float = 0.0,
+                noise_seed: int = 0, epoch: int = 0):
     """One pass over `batches` — an iterable of lists of PairData (as the reference's DataListLoader yields)
     or of collated batches (`DeviceTrajectory.batch`): returns (avg relative-L2 loss, avg MSE) like train()
     (graph_kernel.py:445-474).  The per-batch losses stay on the device until the pass is over (the
     reference's `l2.item()` per batch would stall the GPU once per step); they are then added on the host in
-    double precision in batch order, which is what `avg_loss += l2.item()` does."""
+    double precision in batch order, which is what `avg_loss += l2.item()` does.
+    noise_std > 0: every batch — collated by `DeviceTrajectory.batch` — trains on input windows perturbed by
+    `add_window_noise(batch, noise_std, noise_seed, epoch)`; the caller's batches are left clean.  `validate_epoch`
+    never adds noise."""
     model.train()
     losses, mses = [], []
     one = None
@@ -482,6 +507,12 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
         else:
             B = len(batch)
         optimizer.zero_grad()
+        if float(noise_std) != 0.0:
+            if not isinstance(batch, PairData):
+                raise MdnoError("noise_std needs collated batches from DeviceTrajectory.batch")
+            clean, batch = batch, PairData(batch.x_aminoacid, None, batch.y, batch.edge_attr, batch.edge_index)
+            batch.num_graphs = getattr(clean, "num_graphs", 1)
+            batch.x_position = add_window_noise(clean, noise_std, noise_seed, epoch)
         out = train_forward(model, batch)
         y = torch.cat([s.y for s in batch]).to(out.device) if not isinstance(batch, PairData) else batch.y.to(out.device)
         if hasattr(loss_fn, "rel_with_mse"):      # LpLoss: loss and the logged MSE from one pass (csrc/loss.hip)

@@ -1,9 +1,14 @@
-import sys, time, numpy as np, torch
+import argparse, sys, time, numpy as np, torch
 sys.path.insert(0, '.')
 from molecular_dynamics_neural_operator_amd import synthetic as syn
 from molecular_dynamics_neural_operator_amd.graph_kernel import KernelNN
 from molecular_dynamics_neural_operator_amd.rollout import RolloutEngine
 from molecular_dynamics_neural_operator_amd.weights import near_identity_state_dict
+ap = argparse.ArgumentParser()
+ap.add_argument('--noise-sigma', type=float, default=0.0, help='stochastic rollout: per-step Gaussian noise on the produced frame (A)')
+ap.add_argument('--noise-seed', type=int, default=0)
+a = ap.parse_args()
+noise = dict(noise_sigma=a.noise_sigma, noise_seed=a.noise_seed)
 dev = torch.device('cuda:0')
 for N, steps in ((28, 20000), (504, 1500)):
     W = 10
@@ -13,7 +18,7 @@ for N, steps in ((28, 20000), (504, 1500)):
     model = KernelNN(64, 1024, 6, 6, 7, 3, 20, 4)
     model.load_state_dict(near_identity_state_dict(64, 1024, seed=0, kernel_gain=1e-3, feature_gain=0.1))
     model.eval().to(dev)
-    eng = RolloutEngine(model, 1, N, W, 8.0, max_steps=steps, device=dev)
+    eng = RolloutEngine(model, 1, N, W, 8.0, max_steps=steps, device=dev, **noise)
     eng.reset(win, aa)
     t0 = time.perf_counter()
     done = 0
@@ -27,7 +32,7 @@ for N, steps in ((28, 20000), (504, 1500)):
     print(f"N={N}: {steps} steps in {dt:.2f}s = {steps/dt:.0f} frames/s, conv_mode {eng.conv_mode}, finite {bool(torch.isfinite(fr).all())}, "
           f"edges first/last {int(e[0])}/{int(e[-1])}, max displacement from start {float((fr[-1,0]-fr[0,0]).abs().max()):.3f} A")
     # the same trajectory from a fresh engine stepping one by one for the first 40 steps
-    e2 = RolloutEngine(model, 1, N, W, 8.0, max_steps=40, device=dev, use_graph=False)
+    e2 = RolloutEngine(model, 1, N, W, 8.0, max_steps=40, device=dev, use_graph=False, **noise)
     e2.reset(win, aa)
     for _ in range(40): e2.step(1)
     e2.synchronize()

@@ -45,6 +45,8 @@ ap.add_argument("--train-conv-mode", choices=["materialized", "factored", "auto"
 ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                 help="nccl (RCCL), one GPU per rank; gloo only to rehearse with ranks sharing a card")
 ap.add_argument("--force-dist", action="store_true", help="run alone as a one-rank process group")
+ap.add_argument("--noise-std", type=float, default=0.0, help="Gaussian noise on the input windows of every training batch")
+ap.add_argument("--noise-seed", type=int, default=0)
 ap.add_argument("--workdir", default="/tmp/mdno_train_dp")
 a = ap.parse_args()
 
@@ -109,7 +111,7 @@ for ep in range(a.epochs):
     dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    tl, mse = trainer.train_epoch(batches, src)
+    tl, mse = trainer.train_epoch(batches, src, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vl = trainer.validate_epoch(vbatches, src)[0]

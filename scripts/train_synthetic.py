@@ -43,6 +43,9 @@ ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fuse
 ap.add_argument("--host-collate", action="store_true",
                 help="collate every batch on the host from ContactMapDataset samples (what the reference's "
                      "DataListLoader does) instead of on the device from the resident trajectory")
+ap.add_argument("--noise-std", type=float, default=0.0,
+                help="Gaussian noise on the input windows of every training batch (device-collated batches only)")
+ap.add_argument("--noise-seed", type=int, default=0)
 ap.add_argument("--workdir", default="/tmp/mdno_train")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -120,7 +123,7 @@ torch.cuda.synchronize()
 torch.cuda.reset_peak_memory_stats()
 for ep in range(a.epochs):
     t0 = time.perf_counter()
-    tl, mse = train_epoch(model, batches, opt, loss_fn)
+    tl, mse = train_epoch(model, batches, opt, loss_fn, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vl = validate()

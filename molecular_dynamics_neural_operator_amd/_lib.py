@@ -172,6 +172,17 @@ NOISE_SIGNATURES = {
     "mdno_rollout_plan_set_noise": (_I, [_P, _F, _U64, _P]),
 }
 
+# include/mdno_unroll.h (gradients w.r.t. the model's inputs, targets of an unrolled step; additive, no version number
+# of its own): name -> (restype, argtypes), kept in step with that header (tests/test_unroll_host.py checks both ways)
+UNROLL_SIGNATURES = {
+    "mdno_edge_mlp_input_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P, _P]),
+    "mdno_edge_attr_from_pos": (_I, [_P, _P, _P, _P, _L, _I, _P, _P]),
+    "mdno_edge_attr_pos_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "mdno_node_prologue_bwd_frames": (_I, [C.POINTER(KernelNNParams), _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _SZ, _P]),
+    "mdno_collate_targets": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -202,7 +213,8 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP library is not built. Run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
+            list(UNROLL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -13,6 +13,7 @@
 // order by a second kernel — so they are bitwise reproducible (no float atomics); the embedding gradient, a
 // scatter by residue type, is gathered per table entry in atom order.
 #include "kernels.h"
+#include "../../include/mdno_unroll.h"
 
 namespace mdno {
 namespace {
@@ -43,9 +44,12 @@ struct PrologueBwdArgs {
     const float* g0;          // [R, width] dLoss/dx0
     float* part;              // [blocks][stride] partial sums: lstm 96 | emb num_emb*emb_dim | fc1_w width*in_w | fc1_b width
     int stride;
+    float* d_frames;          // [W, R, 3] dLoss/dframes, or NULL (read by the DF instantiations only)
 };
 
-template <int EMB>      // compile-time bound on emb_dim (a multiple of 4)
+// EMB: compile-time bound on emb_dim (a multiple of 4).  DF: also write a.d_frames (mdno_node_prologue_bwd_frames); the
+// DF = false instantiations are the code mdno_node_prologue_bwd has always launched.
+template <int EMB, bool DF>
 __global__ __launch_bounds__(ROWS) void node_prologue_bwd_kernel(PrologueBwdArgs a) {
     __shared__ float gz_s[ROWS][65];                   // g0 * (x0 > 0): this wave's atoms x 64 output columns of a pass
     __shared__ float w_s[64][EMB + H + 1];             // the pass's 64 rows of fc1_w, zero-padded
@@ -240,7 +244,16 @@ __global__ __launch_bounds__(ROWS) void node_prologue_bwd_kernel(PrologueBwdArgs
     }
 
     // ---- LSTM + lstm_fc backward for this atom; per-thread parameter gradients
-    if (!lstm) return;
+    if (!lstm) {
+        if (DF && live) {      // the coordinates of the last frame ARE the features; the frames before it are not read
+            for (int t = 0; t < a.W; ++t) {
+                float* d = a.d_frames + ((size_t)t * a.R + r) * 3;
+#pragma unroll
+                for (int k = 0; k < H; ++k) d[k] = t == a.W - 1 ? dfeat[EMB + k] : 0.f;
+            }
+        }
+        return;
+    }
     float glstm[N_LSTM];
 #pragma unroll
     for (int i = 0; i < N_LSTM; ++i) glstm[i] = 0.f;
@@ -286,6 +299,16 @@ __global__ __launch_bounds__(ROWS) void node_prologue_bwd_kernel(PrologueBwdArgs
                         dh[k] = fmaf(whh[g][k], dpre[g], dh[k]);
                     }
                     glstm[72 + g] += dpre[g];                                                      // b_ih = b_hh
+                }
+                if (DF) {                  // d x_t = W_ih^T . dpre_t, gates in order
+                    float* d = a.d_frames + ((size_t)t * a.R + r) * 3;
+#pragma unroll
+                    for (int k = 0; k < H; ++k) {
+                        float sx = 0.f;
+#pragma unroll
+                        for (int g = 0; g < 4 * H; ++g) sx = fmaf(wih[g][k], dpre[g], sx);
+                        d[k] = sx;
+                    }
                 }
             }
         }
@@ -384,33 +407,40 @@ extern "C" size_t mdno_node_prologue_bwd_workspace_bytes(const mdno_kernelnn_par
     return align_up((size_t)((rows + ROWS - 1) / ROWS) * tot * sizeof(float), 256);
 }
 
-extern "C" int mdno_node_prologue_bwd(const mdno_kernelnn_params* p, const float* frames, int M, int W, int N,
-                                      const int64_t* x_aminoacid, int aa_per_member, const float* x0, const float* g0,
-                                      float* d_lstm, float* d_emb, float* d_fc1_w, float* d_fc1_b, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
+// d_frames NULL: mdno_node_prologue_bwd, the launches and bits it has always had
+static int prologue_bwd(const char* what, const mdno_kernelnn_params* p, const float* frames, int M, int W, int N,
+                        const int64_t* x_aminoacid, int aa_per_member, const float* x0, const float* g0, float* d_lstm,
+                        float* d_emb, float* d_fc1_w, float* d_fc1_b, float* d_frames, void* workspace,
+                        size_t workspace_bytes, void* stream) {
     MDNO_REQUIRE(p && frames && x_aminoacid && x0 && g0 && d_emb && d_fc1_w && d_fc1_b && workspace, MDNO_EINVAL,
-                 "mdno_node_prologue_bwd: null pointer");
+                 "%s: null pointer", what);
     const bool lstm = p->lstm_w_ih != nullptr;
     MDNO_REQUIRE(!lstm || (p->lstm_w_hh && p->lstm_b_ih && p->lstm_b_hh && p->lstm_fc_w && p->lstm_fc_b && d_lstm),
-                 MDNO_EINVAL, "mdno_node_prologue_bwd: partial LSTM set");
-    MDNO_REQUIRE(M > 0 && N > 0 && W > 0 && W <= MAX_W, MDNO_EUNSUPPORTED, "mdno_node_prologue_bwd: window %d (1..%d)", W,
+                 MDNO_EINVAL, "%s: partial LSTM set", what);
+    MDNO_REQUIRE(M > 0 && N > 0 && W > 0 && W <= MAX_W, MDNO_EUNSUPPORTED, "%s: window %d (1..%d)", what, W,
                  MAX_W);
     MDNO_REQUIRE(p->x_position_dim == H && p->embedding_dim >= 0 && p->embedding_dim <= MAX_EMB &&
                      p->in_width == p->embedding_dim + H,
-                 MDNO_EUNSUPPORTED, "mdno_node_prologue_bwd: unsupported dims");
+                 MDNO_EUNSUPPORTED, "%s: unsupported dims", what);
     const int R = M * N, blocks = (R + ROWS - 1) / ROWS;
     int ne, nw, tot;
     prologue_counts(p, &ne, &nw, &tot);
     MDNO_REQUIRE(workspace_bytes >= mdno_node_prologue_bwd_workspace_bytes(p, R), MDNO_EWORKSPACE,
-                 "mdno_node_prologue_bwd: workspace too small");
+                 "%s: workspace too small", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(workspace);
     PrologueBwdArgs a{frames, R, N, W, (const long long*)x_aminoacid, aa_per_member, p->lstm_w_ih, p->lstm_w_hh,
                       p->lstm_b_ih, p->lstm_b_hh, p->lstm_fc_w, p->lstm_fc_b, p->emb_w, p->fc1_w, p->fc1_b,
-                      p->num_embeddings, p->embedding_dim, p->width, x0, g0, part, tot};
-    if (p->embedding_dim <= 4) hipLaunchKernelGGL(node_prologue_bwd_kernel<4>, dim3(blocks), dim3(ROWS), 0, s, a);
-    else if (p->embedding_dim <= 8) hipLaunchKernelGGL(node_prologue_bwd_kernel<8>, dim3(blocks), dim3(ROWS), 0, s, a);
-    else hipLaunchKernelGGL(node_prologue_bwd_kernel<MAX_EMB>, dim3(blocks), dim3(ROWS), 0, s, a);
+                      p->num_embeddings, p->embedding_dim, p->width, x0, g0, part, tot, d_frames};
+    if (d_frames) {
+        if (p->embedding_dim <= 4) hipLaunchKernelGGL((node_prologue_bwd_kernel<4, true>), dim3(blocks), dim3(ROWS), 0, s, a);
+        else if (p->embedding_dim <= 8) hipLaunchKernelGGL((node_prologue_bwd_kernel<8, true>), dim3(blocks), dim3(ROWS), 0, s, a);
+        else hipLaunchKernelGGL((node_prologue_bwd_kernel<MAX_EMB, true>), dim3(blocks), dim3(ROWS), 0, s, a);
+    } else {
+        if (p->embedding_dim <= 4) hipLaunchKernelGGL((node_prologue_bwd_kernel<4, false>), dim3(blocks), dim3(ROWS), 0, s, a);
+        else if (p->embedding_dim <= 8) hipLaunchKernelGGL((node_prologue_bwd_kernel<8, false>), dim3(blocks), dim3(ROWS), 0, s, a);
+        else hipLaunchKernelGGL((node_prologue_bwd_kernel<MAX_EMB, false>), dim3(blocks), dim3(ROWS), 0, s, a);
+    }
     auto reduce = [&](int off, int count, float* out) {
         if (count <= 0) return;      // (embedding_dim 0: no embedding gradient)
         hipLaunchKernelGGL(reduce_blocks_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float*)part + off,
@@ -424,6 +454,24 @@ extern "C" int mdno_node_prologue_bwd(const mdno_kernelnn_params* p, const float
     reduce(N_LSTM + ne, nw, d_fc1_w);
     reduce(N_LSTM + ne + nw, p->width, d_fc1_b);
     return check_launch("node_prologue_bwd");
+}
+
+extern "C" int mdno_node_prologue_bwd(const mdno_kernelnn_params* p, const float* frames, int M, int W, int N,
+                                      const int64_t* x_aminoacid, int aa_per_member, const float* x0, const float* g0,
+                                      float* d_lstm, float* d_emb, float* d_fc1_w, float* d_fc1_b, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return prologue_bwd("mdno_node_prologue_bwd", p, frames, M, W, N, x_aminoacid, aa_per_member, x0, g0, d_lstm, d_emb,
+                        d_fc1_w, d_fc1_b, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mdno_node_prologue_bwd_frames(const mdno_kernelnn_params* p, const float* frames, int M, int W, int N,
+                                             const int64_t* x_aminoacid, int aa_per_member, const float* x0,
+                                             const float* g0, float* d_lstm, float* d_emb, float* d_fc1_w, float* d_fc1_b,
+                                             float* d_frames, void* workspace, size_t workspace_bytes, void* stream) {
+    MDNO_REQUIRE(W > 0 && W <= MAX_W, MDNO_EINVAL, "mdno_node_prologue_bwd_frames: window %d (1..%d)", W, MAX_W);
+    MDNO_REQUIRE(d_frames, MDNO_EINVAL, "mdno_node_prologue_bwd_frames: null pointer (d_frames)");
+    return prologue_bwd("mdno_node_prologue_bwd_frames", p, frames, M, W, N, x_aminoacid, aa_per_member, x0, g0, d_lstm,
+                        d_emb, d_fc1_w, d_fc1_b, d_frames, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mdno_fc_out_bwd_workspace_bytes(int rows, int width, int out_width) {

@@ -858,8 +858,10 @@ def fc_out_bwd(x: torch.Tensor, w: torch.Tensor, g: torch.Tensor):
 
 
 def node_prologue_bwd(pack: ParamPack, frames: torch.Tensor, x_aminoacid: torch.Tensor, x0: torch.Tensor,
-                      g0: torch.Tensor):
-    """Backward of `node_prologue`: -> dict of gradients under the state_dict key names."""
+                      g0: torch.Tensor, need_frames: bool = False):
+    """Backward of `node_prologue`: -> dict of gradients under the state_dict key names; `need_frames`: also
+    dLoss/dframes f32 [W,M,N,3] under "frames" (include/mdno_unroll.h mdno_node_prologue_bwd_frames: the same launches,
+    the same parameter gradients bit for bit)."""
     lib = _lib.load()
     frames = f32(frames)
     if frames.dim() == 3:
@@ -875,10 +877,19 @@ def node_prologue_bwd(pack: ParamPack, frames: torch.Tensor, x_aminoacid: torch.
     d_w = torch.empty((p.width, p.in_width), dtype=torch.float32, device=dev)
     d_b = torch.empty(p.width, dtype=torch.float32, device=dev)
     ws = _ws(lib.mdno_node_prologue_bwd_workspace_bytes(pack.ref, M * N), dev)
-    check(lib.mdno_node_prologue_bwd(pack.ref, ptr(frames), M, W, N, ptr(aa), int(aa.numel() == M * N and M > 1),
-                                     ptr(f32(x0)), ptr(f32(g0)), ptr(d_lstm), ptr(emb_out), ptr(d_w), ptr(d_b), ptr(ws),
-                                     ws.numel(), stream_ptr(dev)), "mdno_node_prologue_bwd")
+    if need_frames:
+        d_frames = torch.empty_like(frames)
+        check(lib.mdno_node_prologue_bwd_frames(pack.ref, ptr(frames), M, W, N, ptr(aa), int(aa.numel() == M * N and M > 1),
+                                                ptr(f32(x0)), ptr(f32(g0)), ptr(d_lstm), ptr(emb_out), ptr(d_w), ptr(d_b),
+                                                ptr(d_frames), ptr(ws), ws.numel(), stream_ptr(dev)),
+              "mdno_node_prologue_bwd_frames")
+    else:
+        check(lib.mdno_node_prologue_bwd(pack.ref, ptr(frames), M, W, N, ptr(aa), int(aa.numel() == M * N and M > 1),
+                                         ptr(f32(x0)), ptr(f32(g0)), ptr(d_lstm), ptr(emb_out), ptr(d_w), ptr(d_b), ptr(ws),
+                                         ws.numel(), stream_ptr(dev)), "mdno_node_prologue_bwd")
     out = {"emb.weight": d_emb, "fc1.weight": d_w, "fc1.bias": d_b}
+    if need_frames:
+        out["frames"] = d_frames
     if has_lstm:
         # six DISJOINT slices of one buffer (the kernel writes b_hh's gradient — the same values as b_ih's — a second
         # time at [96:108]): autograd's AccumulateGrad keeps the tensor it is handed, so no two .grad tensors may
@@ -904,6 +915,70 @@ def collate_samples(pos: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor, m
                                    ptr(x_position), ptr(y), ptr(edge_index), ptr(edge_attr), stream_ptr(dev)),
           "mdno_collate_samples")
     return x_position, y, edge_index, edge_attr
+
+
+def collate_targets(pos: torch.Tensor, meta: torch.Tensor, B: int, N: int, W: int, horizon: int, steps: int) -> torch.Tensor:
+    """Targets of an unrolled step (include/mdno_unroll.h mdno_collate_targets): y f32 [steps, B*N, 3], step k of sample
+    b = frame meta[b] + W + horizon - 1 + k of the resident trajectory `pos` [T,N,3]; one launch."""
+    lib = _lib.load()
+    if int(steps) < 1:
+        raise MdnoError(f"collate_targets: steps={steps} (>= 1)")
+    y = torch.empty((int(steps), B * N, 3), dtype=torch.float32, device=pos.device)
+    check(lib.mdno_collate_targets(ptr(pos), int(pos.shape[0]), ptr(meta), B, N, W, horizon, int(steps), ptr(y),
+                                   stream_ptr(pos.device)), "mdno_collate_targets")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
+# Gradients with respect to the model's inputs (include/mdno_unroll.h, csrc/input_grad.hip)
+def edge_mlp_input_bwd(gz1: torch.Tensor, w0: torch.Tensor, num_edges: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_edge_attr f32 [rows, ker_in] = gz1 [rows, k] . w0 [k, ker_in] for the first `num_edges` (i32 [1], device) rows,
+    in gz1's (CSR) edge order; rows past the count are left as they are (`out`: the buffer to write, else a new one)."""
+    lib = _lib.load()
+    gz1, w0 = f32(gz1), f32(w0)
+    rows, k = gz1.shape
+    ker_in = w0.shape[1]
+    if w0.shape[0] != k or not 1 <= ker_in <= 8:
+        raise MdnoError(f"edge_mlp_input_bwd: gz1 {tuple(gz1.shape)}, w0 {tuple(w0.shape)} (ker_in 1..8)")
+    if out is None:
+        out = torch.empty((rows, ker_in), dtype=torch.float32, device=gz1.device)
+    elif tuple(out.shape) != (rows, ker_in) or out.dtype != torch.float32:
+        raise MdnoError(f"edge_mlp_input_bwd: out must be f32 {(rows, ker_in)}")
+    if rows == 0:
+        return out
+    check(lib.mdno_edge_mlp_input_bwd(ptr(gz1), ptr(w0), ptr(num_edges), rows, k, ker_in, ptr(out), stream_ptr(gz1.device)),
+          "mdno_edge_mlp_input_bwd")
+    return out
+
+
+def edge_attr_from_pos(pos: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
+    """edge_attr f32 [E, 6] = [pos[src p], pos[dst p]] in the graph's CSR edge order (mdno_edge_attr_from_pos): the
+    attributes the forward forms from `edge_pos` for the same graph."""
+    lib = _lib.load()
+    pos = f32(pos).reshape(-1, 3)
+    E = graph.edge_count()
+    ea = torch.empty((E, 6), dtype=torch.float32, device=pos.device)
+    if E:
+        check(lib.mdno_edge_attr_from_pos(ptr(pos), ptr(graph.src), ptr(graph.dst), ptr(graph.num_edges), E, pos.shape[0],
+                                          ptr(ea), stream_ptr(pos.device)), "mdno_edge_attr_from_pos")
+    return ea
+
+
+def edge_attr_pos_bwd(d_edge_attr: torch.Tensor, graph: CSRGraph, by_src: CSRGraph, num_rows: int) -> torch.Tensor:
+    """The adjoint of `edge_attr_from_pos` (mdno_edge_attr_pos_bwd): d_pos f32 [num_rows, 3]; `by_src` =
+    `source_sorted(graph, num_rows)`."""
+    lib = _lib.load()
+    g = f32(d_edge_attr)
+    E = graph.edge_count()
+    if g.dim() != 2 or tuple(g.shape) != (E, 6):
+        raise MdnoError(f"edge_attr_pos_bwd: d_edge_attr {tuple(g.shape)}, expected {(E, 6)}")
+    d_pos = torch.empty((num_rows, 3), dtype=torch.float32, device=g.device)
+    if E == 0:                  # (never read: both row-pointer arrays end at 0; the pointer must not be null)
+        g = torch.zeros((1, 6), dtype=torch.float32, device=g.device)
+    check(lib.mdno_edge_attr_pos_bwd(ptr(g), ptr(graph.row_ptr), ptr(by_src.row_ptr), ptr(by_src.perm), int(num_rows),
+                                     ptr(d_pos), stream_ptr(g.device)), "mdno_edge_attr_pos_bwd")
+    return d_pos
 
 
 # ------------------------------------------------------------------------------------------------

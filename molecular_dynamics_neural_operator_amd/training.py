@@ -95,7 +95,19 @@ class KernelIntegralBlock(torch.autograd.Function):
             gz1 = ops.relu_bwd(ops.linear(gz2, ops.transpose(w1), None, gemm_mode=gemm_mode), h1)
             d_b0 = ops.colsum(gz1)
             d_w0 = ops.gemm_atb(gz1, ea)
-        return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
+        d_ea = _edge_attr_grad(ctx, gz1, w0, graph) if ctx.needs_input_grad[1] else None
+        return (g, d_ea, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
+
+
+def _edge_attr_grad(ctx, gz1, w0, graph):
+    """dLoss/d edge_attr of a kernel-integral block, in the caller's edge order: gz1 . W0 in CSR order
+    (mdno_edge_mlp_input_bwd), then `graph.perm` undone (mdno_scatter_rows)."""
+    if getattr(ctx, "bf16", False):
+        raise NotImplementedError('train_precision="bf16" has no gradient with respect to edge_attr (fp32 only)')
+    d_ea = ops.edge_mlp_input_bwd(gz1, w0, graph.num_edges)
+    if graph.perm is not None:
+        d_ea = ops.scatter_rows(d_ea, graph.perm, d_ea.shape[0])
+    return d_ea
 
 
 class FactoredKernelIntegralBlock(torch.autograd.Function):
@@ -140,7 +152,8 @@ class FactoredKernelIntegralBlock(torch.autograd.Function):
         del gz2, h1
         d_b0 = ops.colsum(gz1)
         d_w0 = ops.gemm_atb(gz1, ea)
-        return (g, None, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
+        d_ea = _edge_attr_grad(ctx, gz1, w0, graph) if ctx.needs_input_grad[1] else None
+        return (g, d_ea, None, None, None, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, d_root1, d_bias1, d_root2, d_bias2)
 
 
 class NodePrologue(torch.autograd.Function):
@@ -157,8 +170,9 @@ class NodePrologue(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g0):
         frames, aa, x0 = ctx.saved_tensors
-        grads = ops.node_prologue_bwd(ctx.pack, frames, aa, x0, g0.contiguous())
-        return (None, None, None) + tuple(grads[n] for n in ctx.names)
+        need_frames = ctx.needs_input_grad[1]
+        grads = ops.node_prologue_bwd(ctx.pack, frames, aa, x0, g0.contiguous(), need_frames=need_frames)
+        return (None, grads["frames"] if need_frames else None, None) + tuple(grads[n] for n in ctx.names)
 
 
 class FcOut(torch.autograd.Function):
@@ -174,6 +188,24 @@ class FcOut(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dx, d_w, d_b = ops.fc_out_bwd(x, w, g.contiguous())
         return dx, d_w, d_b
+
+
+class EdgeAttrFromPositions(torch.autograd.Function):
+    """edge_attr [E, 6] = [pos[src p], pos[dst p]] in `graph`'s CSR edge order, differentiable in `pos` [R, 3]
+    (include/mdno_unroll.h mdno_edge_attr_from_pos / mdno_edge_attr_pos_bwd).  The graph is data: no gradient goes
+    through its topology.  `graph.by_src` (ops.source_sorted) is used by the backward where it is already there."""
+
+    @staticmethod
+    def forward(ctx, pos, graph):
+        ctx.graph, ctx.rows = graph, pos.reshape(-1, 3).shape[0]
+        ctx.shape = tuple(pos.shape)
+        return ops.edge_attr_from_pos(pos, graph)
+
+    @staticmethod
+    def backward(ctx, g):
+        graph = ctx.graph
+        by_src = getattr(graph, "by_src", None) or ops.source_sorted(graph, ctx.rows)
+        return ops.edge_attr_pos_bwd(g.contiguous(), graph, by_src, ctx.rows).view(ctx.shape), None
 
 
 _PROLOGUE_KEYS = ("lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "lstm_fc.weight",
@@ -253,14 +285,26 @@ class DeviceTrajectory:
         first = start + self.W + self.horizon - 1
         return self.pos[first:first + steps]
 
-    def batch(self, indices, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0) -> PairData:
-        """noise_std > 0: the input windows (`x_position` only — `y`, `edge_attr` and `edge_index` stay clean) get
+    def batch(self, indices, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0, unroll: int = 1) -> PairData:
+        """unroll = K > 1: the batch also carries `y_unroll` f32 [K, B*N, 3], the true frames an unrolled step of K
+        model steps is scored against (frame idx + W + k of every sample, k < K; one more launch: include/mdno_unroll.h
+        mdno_collate_targets); `y` stays `y_unroll[0]`.  Needs horizon 1 (the window slides one frame per step) and
+        every sample index <= len - K.
+        noise_std > 0: the input windows (`x_position` only — `y`, `edge_attr` and `edge_index` stay clean) get
         noise_std * z(noise_seed, sample index, epoch, frame, atom, component) added on the device (include/mdno_noise.h
         mdno_noise_add_window).  The key is the sample's index in the dataset: a sample's noise does not depend on the
         batch it is in, the batch size or the rank.  The batch carries `sample_ids` / `rows_per_sample` either way."""
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.length:
             raise IndexError(f"sample indices must lie in [0, {self.length})")
+        K = int(unroll)
+        if K < 1:
+            raise MdnoError(f"unroll={unroll} (>= 1)")
+        if K > 1 and self.horizon != 1:
+            raise MdnoError(f"unroll={K} needs horizon 1 (got {self.horizon}): the window slides one frame per step")
+        if idx.max() > self.length - K:
+            raise IndexError(f"unroll={K}: sample indices must lie in [0, {self.length - K}] (the last target is frame "
+                             f"index + window + {K - 1})")
         B = int(idx.size)
         cnt = self.counts[idx]
         slot = self._meta_buffer(3 * B + 1)
@@ -280,6 +324,10 @@ class DeviceTrajectory:
         out = PairData(x_aminoacid=self._aa_tiled[B], x_position=xp, y=y, edge_attr=ea, edge_index=ei)
         out.num_graphs = B
         out.sample_ids, out.rows_per_sample = idx.copy(), self.N
+        if K > 1:
+            out.y_unroll = ops.collate_targets(self.pos, meta_d, B, self.N, self.W, self.horizon, K)
+        else:
+            out.y_unroll = y.unsqueeze(0)
         if float(noise_std) != 0.0:
             out.x_position = add_window_noise(out, noise_std, noise_seed, epoch)
         return out
@@ -333,11 +381,12 @@ def resolve_train_conv_mode(model, members: int, n_atoms: int, n_edges: int) -> 
     return "factored" if rule == _lib.CONV_MODES["factored"] else "materialized"
 
 
-def check_trainable(model, window: int) -> None:
+def check_trainable(model, window: int, input_grad: bool = False) -> None:
     """Refuse, before any device work, a model or window the training kernels do not implement: the conv chain and
     its backward are 64x64 only (csrc/train_conv.hip), the prologue backward keeps at most 16 frames and 16 embedding
     channels per atom (csrc/train_nodes.hip), the edge-MLP's first layer reads at most 8 attributes
-    (csrc/edge_mlp.hip), and bf16 training tiles k by 128."""
+    (csrc/edge_mlp.hip), and bf16 training tiles k by 128.  `input_grad`: the step also wants gradients with respect to
+    its inputs (an input that requires grad, an unrolled step that is not detached) — fp32 storage only."""
     conv2 = getattr(model, "conv2", None)
     if conv2 is not None and model.conv1.net is not conv2.net:
         raise NotImplementedError("training assumes the reference's single shared edge-MLP (graph_kernel.py:271-273)")
@@ -361,6 +410,10 @@ def check_trainable(model, window: int) -> None:
         raise MdnoError(f"train_precision={precision!r} (fp32, bf16)")
     if precision == "bf16" and (w1.shape[0] % 128 or w1.shape[1] % 32):
         raise NotImplementedError("bf16 training needs width 64 and ker_width a multiple of 128")
+    if precision == "bf16" and input_grad:
+        raise NotImplementedError('train_precision="bf16" has no gradients with respect to the inputs (x_position, '
+                                  'edge_attr) and no unrolled step that feeds them back: bf16 storage for the input '
+                                  'gradients is out of scope (use train_precision="fp32", or unroll with detach=True)')
     mode = getattr(model, "train_conv_mode", "materialized")
     if mode not in TRAIN_CONV_MODES:
         raise MdnoError(f"train_conv_mode={mode!r} {TRAIN_CONV_MODES}")
@@ -373,21 +426,38 @@ def check_trainable(model, window: int) -> None:
                                       f'{w1.shape[0]}) and mean aggregation')
 
 
+def _wants_grad(t) -> bool:
+    return torch.is_tensor(t) and t.requires_grad and torch.is_grad_enabled()
+
+
 def train_forward(model, data) -> torch.Tensor:
     """Differentiable forward of `KernelNN` for one sample, a list of samples, or an already collated batch
     (`collate`, `DeviceTrajectory.batch`) -> [B*N, out].  Nothing here waits for the device: index errors
     (amino-acid id or node id out of range — IndexError in the reference) are left in `model`'s training
-    status word and raised by `check_train_status(model)`, which `train_epoch` calls once per epoch."""
+    status word and raised by `check_train_status(model)`, which `train_epoch` calls once per epoch.
+    `requires_grad` on `data.x_position` / `data.edge_attr` is honoured (fp32 training): their `.grad` is
+    d out / d input through the LSTM prologue and through the edge-MLP (edge_attr in the caller's edge order);
+    without it the backward launches and allocates exactly what it always has."""
     batch = collate(data) if not isinstance(data, PairData) else data
-    check_trainable(model, batch.x_position.shape[0] if batch.x_position.dim() == 3 else 1)
+    check_trainable(model, batch.x_position.shape[0] if batch.x_position.dim() == 3 else 1,
+                    input_grad=_wants_grad(batch.x_position) or _wants_grad(batch.edge_attr))
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise MdnoError("training needs the model on the GPU (model.to('cuda')); no CPU fallback")
     xp = batch.x_position.to(dev, torch.float32)
     if xp.dim() == 2:
         xp = xp.unsqueeze(0)
+    B = max(int(getattr(batch, "num_graphs", 1) or 1), 1)
+    return _forward_step(model, xp, batch.x_aminoacid.to(dev), B, edge_index=batch.edge_index,
+                         edge_attr=batch.edge_attr)[0]
+
+
+def _forward_step(model, xp, aa, B: int, edge_index=None, edge_attr=None, graph=None):
+    """One differentiable forward on windows xp [W, R, 3] (on the model's device) -> (out [R, out_width], graph).  The
+    edges: `edge_index` [2, E] with `edge_attr` in its order (sorted here), or an already sorted `graph` (a CSRGraph
+    without `perm`) with `edge_attr` in ITS order — a fed-back step of `unrolled_forward`."""
+    dev = xp.device
     W, R, _ = xp.shape
-    aa = batch.x_aminoacid.to(dev)
     # per-atom prologue (graph_kernel.py:279-298 with B=1 semantics per sample): HIP forward + backward.
     # The ParamPack holds device pointers to the parameters' CURRENT storage (fp32 contiguous parameters
     # are viewed, not copied), the tensors themselves are passed so that autograd routes their gradients.
@@ -411,9 +481,9 @@ def train_forward(model, data) -> torch.Tensor:
         # no conv application (graph_kernel.py:299-302 loop zero times): fc2 reads x0, and the edge-MLP, root and
         # bias parameters take no part in the loss — their .grad stays None, as under torch autograd; the edge list
         # is not read, as in the reference
-        return FcOut.apply(x0, model.fc2.weight, model.fc2.bias)
-    ei = batch.edge_index.to(dev)
-    graph = ops.coo_to_csr(ei, R, validate=False, status=status)
+        return FcOut.apply(x0, model.fc2.weight, model.fc2.bias), graph
+    if graph is None:
+        graph = ops.coo_to_csr(edge_index.to(dev), R, validate=False, status=status)
     # the same edges grouped by source, for the input-gradient kernel: built now, next to the forward's sort
     # (ids already validated by it), so that the backward starts with everything in place
     graph.by_src = ops.source_sorted(graph, R, status=status) if torch.is_grad_enabled() else None
@@ -422,16 +492,63 @@ def train_forward(model, data) -> torch.Tensor:
     w0, b0, w1, b1, w2, b2 = net.hip_weights()
     c2 = conv2 if conv2 is not None else model.conv1
     precision = getattr(model, "train_precision", "fp32")
-    B = max(int(getattr(batch, "num_graphs", 1) or 1), 1)
-    if resolve_train_conv_mode(model, B, max(R // B, 1), int(ei.shape[1])) == "factored":
+    if resolve_train_conv_mode(model, B, max(R // B, 1), graph.edge_count()) == "factored":
         block = FactoredKernelIntegralBlock
     else:
         block = KernelIntegralBlock
-    x = block.apply(x0, batch.edge_attr.to(dev), graph, depth,
+    x = block.apply(x0, edge_attr.to(dev), graph, depth,
                     "bf16" if precision == "bf16" else getattr(model, "gemm_mode", "f32"),
                     w0, b0, w1, b1, w2, b2,
                     model.conv1.root, model.conv1.bias, c2.root, c2.bias)
-    return FcOut.apply(x, model.fc2.weight, model.fc2.bias)
+    return FcOut.apply(x, model.fc2.weight, model.fc2.bias), graph
+
+
+def unrolled_forward(model, batch, steps: int, cutoff: float = 8.0, detach: bool = False):
+    """`steps` model steps from a training window, each prediction fed back as `recursive_propagation` does
+    (graph_kernel.py: the window slides by one frame, the new frame's radius graph and edge attributes replace the
+    stored ones) -> (outs, graphs): `outs[k]` [B*N, 3] is the prediction of frame t + 1 + k, `graphs[k]` the CSRGraph
+    step k ran on.  Gradients flow back through the fed-back frames — through the slid window (the LSTM prologue) and
+    through the edge attributes `EdgeAttrFromPositions` forms from the predicted frame; the radius graph itself is
+    data, built per sample on the detached frame, and no gradient goes through its topology.  `detach=True` cuts the
+    gradient at every fed-back frame (the pushforward variant): none of the input-gradient kernels then runs.
+    Step 1 is `train_forward(model, batch)` on the dataset's stored edge list and attributes; `train_conv_mode` is
+    resolved per step on that step's edge count.  Every fed-back step reads its edge count back from the device
+    (one device-to-host word: its buffers are sized by it) — the one place the training path waits for the device.
+    The model predicts frames at horizon 1; `batch` is one sample, a list, or a collated batch of B samples."""
+    steps = int(steps)
+    if steps < 1:
+        raise MdnoError(f"unrolled_forward: steps={steps} (>= 1)")
+    batch = collate(batch) if not isinstance(batch, PairData) else batch
+    W = batch.x_position.shape[0] if batch.x_position.dim() == 3 else 1
+    feeds_grad = steps > 1 and not detach and torch.is_grad_enabled()
+    check_trainable(model, W, input_grad=feeds_grad or _wants_grad(batch.x_position) or _wants_grad(batch.edge_attr))
+    if steps > 1 and model.fc2.out_features != 3:
+        raise MdnoError(f"unrolled_forward: the model predicts {model.fc2.out_features} values per atom, a frame has 3")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise MdnoError("training needs the model on the GPU (model.to('cuda')); no CPU fallback")
+    xp = batch.x_position.to(dev, torch.float32)
+    if xp.dim() == 2:
+        xp = xp.unsqueeze(0)
+    aa = batch.x_aminoacid.to(dev)
+    B = max(int(getattr(batch, "num_graphs", 1) or 1), 1)
+    R = xp.shape[1]
+    if R % B:
+        raise MdnoError(f"unrolled_forward: {R} rows in {B} graphs")
+    out, graph = _forward_step(model, xp, aa, B, edge_index=batch.edge_index, edge_attr=batch.edge_attr)
+    outs, graphs = [out], [graph]
+    for _ in range(1, steps):
+        frame = out.detach() if detach else out
+        xp = torch.cat([xp[1:], frame.unsqueeze(0)], dim=0)
+        rg = ops.radius_graph(frame.detach(), R // B, cutoff)
+        E = rg.edge_count()                                # the device->host read of this step
+        cap = max(E, 1)
+        graph = ops.CSRGraph(rg.row_ptr, rg.src[:cap], rg.dst[:cap], rg.num_edges, cap, None, rg.status, n_edges=E)
+        ea = EdgeAttrFromPositions.apply(frame, graph)
+        out, graph = _forward_step(model, xp, aa, B, edge_attr=ea, graph=graph)
+        outs.append(out)
+        graphs.append(graph)
+    return outs, graphs
 
 
 def check_train_status(model) -> None:
@@ -489,7 +606,7 @@ class Adam(torch.optim.Optimizer):
 
 
 def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = None, noise_std: float = 0.0,
-                noise_seed: int = 0, epoch: int = 0):
+                noise_seed: int = 0, epoch: int = 0, unroll: int = 1, unroll_detach: bool = False, cutoff: float = 8.0):
     """One pass over `batches` — an iterable of lists of PairData (as the reference's DataListLoader yields)
     or of collated batches (`DeviceTrajectory.batch`): returns (avg relative-L2 loss, avg MSE) like train()
     (graph_kernel.py:445-474).  The per-batch losses stay on the device until the pass is over (the
@@ -497,7 +614,16 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
     double precision in batch order, which is what `avg_loss += l2.item()` does.
     noise_std > 0: every batch — collated by `DeviceTrajectory.batch` — trains on input windows perturbed by
     `add_window_noise(batch, noise_std, noise_seed, epoch)`; the caller's batches are left clean.  `validate_epoch`
-    never adds noise."""
+    never adds noise.
+    unroll = K > 1: every batch — collated by `DeviceTrajectory.batch(indices, unroll=K)`, which adds the K true frames
+    `y_unroll` — trains on `unrolled_forward(model, batch, K, cutoff, detach=unroll_detach)`: the loss is the mean over
+    the K steps of `loss_fn(out_k, y_k)`, and the returned pair is that mean and the mean MSE of the K steps.  unroll = 1
+    is the one-step path: the same launches, the same bits."""
+    K = int(unroll)
+    if K < 1:
+        raise MdnoError(f"unroll={unroll} (>= 1)")
+    if K > 1 and getattr(model, "train_precision", "fp32") == "bf16" and not unroll_detach:
+        check_trainable(model, 1, input_grad=True)
     model.train()
     losses, mses = [], []
     one = None
@@ -513,6 +639,17 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
             clean, batch = batch, PairData(batch.x_aminoacid, None, batch.y, batch.edge_attr, batch.edge_index)
             batch.num_graphs = getattr(clean, "num_graphs", 1)
             batch.x_position = add_window_noise(clean, noise_std, noise_seed, epoch)
+            if K > 1:
+                batch.y_unroll = getattr(clean, "y_unroll", None)
+        if K > 1:
+            l2, mse = _unrolled_loss(model, batch, B, K, loss_fn, cutoff, unroll_detach)
+            if one is None or one.device != l2.device:
+                one = torch.ones((), dtype=l2.dtype, device=l2.device)
+            l2.backward(one)
+            optimizer.step()
+            losses.append(l2.detach())
+            mses.append(mse)
+            continue
         out = train_forward(model, batch)
         y = torch.cat([s.y for s in batch]).to(out.device) if not isinstance(batch, PairData) else batch.y.to(out.device)
         if hasattr(loss_fn, "rel_with_mse"):      # LpLoss: loss and the logged MSE from one pass (csrc/loss.hip)
@@ -534,6 +671,28 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
     vals = torch.stack([v.reshape(()) for v in losses] + [v.detach().reshape(()) for v in mses]).double().cpu().tolist()
     tot, tot_mse = sum(vals[:n]), sum(vals[n:])
     return tot / n, tot_mse / n
+
+
+def _unrolled_loss(model, batch, B: int, K: int, loss_fn, cutoff: float, detach: bool):
+    """(mean over the K steps of loss_fn(out_k, y_k), mean MSE of the K steps) for one collated batch."""
+    if not isinstance(batch, PairData):
+        raise MdnoError("unroll > 1 needs collated batches from DeviceTrajectory.batch(indices, unroll=K): "
+                        "host-collated lists carry no targets beyond the first step")
+    ys = getattr(batch, "y_unroll", None)
+    if ys is None or ys.shape[0] < K:
+        raise MdnoError(f"unroll={K} needs batches from DeviceTrajectory.batch(indices, unroll={K}) (y_unroll "
+                        f"{'missing' if ys is None else 'has %d steps' % ys.shape[0]})")
+    outs, _ = unrolled_forward(model, batch, K, cutoff=cutoff, detach=detach)
+    total, total_mse = None, None
+    for k, out in enumerate(outs):
+        y = ys[k].to(out.device)
+        if hasattr(loss_fn, "rel_with_mse"):
+            l2, mse = loss_fn.rel_with_mse(out.view(B, -1), y.view(B, -1))
+        else:
+            l2, mse = loss_fn(out.view(B, -1), y.view(B, -1)), F.mse_loss(out.detach(), y)
+        total = l2 if total is None else total + l2
+        total_mse = mse.detach() if total_mse is None else total_mse + mse.detach()
+    return total / K, total_mse / K
 
 
 def validate_epoch(model, batches, loss_fn, batch_size: Optional[int] = None):

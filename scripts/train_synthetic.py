@@ -46,6 +46,11 @@ ap.add_argument("--host-collate", action="store_true",
 ap.add_argument("--noise-std", type=float, default=0.0,
                 help="Gaussian noise on the input windows of every training batch (device-collated batches only)")
 ap.add_argument("--noise-seed", type=int, default=0)
+ap.add_argument("--unroll", type=int, default=1,
+                help="train on K model steps per window, each prediction fed back (training.unrolled_forward; "
+                     "device-collated batches, --precision fp32 unless --unroll-detach)")
+ap.add_argument("--unroll-detach", action="store_true",
+                help="cut the gradient at every fed-back frame (the pushforward variant)")
 ap.add_argument("--workdir", default="/tmp/mdno_train")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -60,6 +65,8 @@ write_trajectory_npz(path, traj, cms, syn.amino_acids(N, seed=0))
 dset = ContactMapDataset(str(path), window_size=W, horizon=1)
 n_train = int(len(dset) * 0.8)                                    # partition split (graph_kernel.py:509-520)
 train_idx, valid_idx = list(range(n_train)), list(range(n_train, len(dset)))
+if a.unroll > 1 and a.host_collate:
+    ap.error("--unroll needs device-collated batches (drop --host-collate)")
 B = a.batch_size
 traj_dev = None if a.host_collate else DeviceTrajectory(dset, dev)
 
@@ -71,6 +78,7 @@ class Batches:
     def __init__(self, idx):
         self.idx = [idx[s:s + B] for s in range(0, len(idx) - B + 1, B)]
         self.host = [[dset[i] for i in b] for b in self.idx] if traj_dev is None else None
+        self.unroll = 1
 
     def __len__(self):
         return len(self.idx)
@@ -79,14 +87,16 @@ class Batches:
         if isinstance(k, slice):
             out = Batches([])
             out.idx, out.host = self.idx[k], (self.host[k] if self.host is not None else None)
+            out.unroll = self.unroll
             return out
-        return self.host[k] if self.host is not None else traj_dev.batch(self.idx[k])
+        return self.host[k] if self.host is not None else traj_dev.batch(self.idx[k], unroll=self.unroll)
 
     def __iter__(self):
         return (self[k] for k in range(len(self)))
 
 
 batches, vbatches = Batches(train_idx), Batches(valid_idx)
+batches.unroll = a.unroll          # (the training indices end n_valid samples before the data does: every target exists)
 
 torch.manual_seed(0)
 model = KernelNN(64, a.kernel_width, a.depth, 6, 7, 3, 20, 4)
@@ -118,12 +128,14 @@ summary = {"frames": a.frames, "batch_size": B, "train_batches": len(batches), "
            int(sum(dset[i].edge_index.shape[1] for i in batches.idx[0])), "kernel_width": a.kernel_width,
            "depth": a.depth, "collate": "host" if a.host_collate else "device"}
 summary["precision"] = a.precision
+summary["unroll"], summary["unroll_detach"] = a.unroll, a.unroll_detach
 train_epoch(model, batches[:1], opt, loss_fn)          # warm-up (allocator, kernels)
 torch.cuda.synchronize()
 torch.cuda.reset_peak_memory_stats()
 for ep in range(a.epochs):
     t0 = time.perf_counter()
-    tl, mse = train_epoch(model, batches, opt, loss_fn, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep)
+    tl, mse = train_epoch(model, batches, opt, loss_fn, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep,
+                          unroll=a.unroll, unroll_detach=a.unroll_detach)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vl = validate()

@@ -183,6 +183,16 @@ UNROLL_SIGNATURES = {
     "mdno_collate_targets": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),
 }
 
+# include/mdno_pbc.h (orthorhombic periodic boundary conditions; additive, no version number of its own): name ->
+# (restype, argtypes), kept in step with that header (tests/test_pbc_host.py checks both ways).  `box` is a HOST
+# pointer to three doubles (ops.box_arg).
+PBC_SIGNATURES = {
+    "mdno_radius_graph_pbc": (_I, [_P, _I, _I, _D, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "mdno_rollout_plan_set_box": (_I, [_P, _P, _P]),
+    "mdno_forecast_score_pbc": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "mdno_contact_maps_pbc": (_I, [_P, _L, _I, _D, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -214,7 +224,7 @@ def load() -> C.CDLL:
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
-            list(UNROLL_SIGNATURES.items()):
+            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

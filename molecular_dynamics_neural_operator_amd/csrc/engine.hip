@@ -11,7 +11,9 @@
 // all 2*depth conv applications use the same W_e = net(edge_attr).  It is evaluated once per
 // forward instead of 2*depth times.
 #include "kernels.h"
+#include "pbc.h"
 #include "../../include/mdno_noise.h"
+#include "../../include/mdno_pbc.h"
 
 #include <string>
 #include <vector>
@@ -360,6 +362,10 @@ struct mdno_rollout_plan {
     unsigned long long noise_seed;
     const int* noise_members;
     hipStream_t capture_stream;      // the stream the graphs were captured on (NULL: plain launches)
+    // periodic rollout (mdno_rollout_plan_set_box): no periodic axis -> none of it is launched or captured
+    bool pbc_on;
+    PbcBox box;
+    float* pbc_attr;                 // f32 [edge_cap, 6], caller-owned: the step's edge attributes
 };
 
 static void plan_counter_words(const mdno_rollout_plan* pl, int** conv, int** mlp) {
@@ -384,8 +390,13 @@ static int plan_enqueue_step(mdno_rollout_plan* pl, hipStream_t s) {
                                                pl->fw.factored ? pl->p.ker_width : pl->p.width * pl->p.width,
                                                pl->edge_cap, pl->p.gemm_mode);
     const int n_zero = act_flags ? kEdgeMlpActivationFlags : 0;
-    const bool head = step_head_small_supported(pl->M, pl->N);      // short chain: graph and node prologue in one launch
-    if (head)
+    // short chain: graph and node prologue in one launch (the open graph only)
+    const bool head = !pl->pbc_on && step_head_small_supported(pl->M, pl->N);
+    if (pl->pbc_on)      // periodic graph of the same frame: CSR + the attribute rows the forward below reads
+        MDNO_TRY(radius_graph_pbc(pl->traj, W - 1, pl->r.t_dev, pl->M, pl->N, pl->threshold, pl->box, pl->r.row_ptr,
+                                  pl->r.src, pl->r.dst, pl->pbc_attr, pl->edge_cap, pl->r.num_edges, pl->status, s,
+                                  act_flags, n_zero));
+    else if (head)
         MDNO_TRY(step_head_small(&pl->p, pl->traj, W, pl->r.t_dev, pl->M, pl->N, pl->aa, pl->aa_per_member, pl->fw.xa,
                                  pl->threshold, pl->r.row_ptr, pl->r.src, pl->r.dst, pl->edge_cap, pl->r.num_edges,
                                  pl->status, act_flags, n_zero, s));
@@ -396,8 +407,8 @@ static int plan_enqueue_step(mdno_rollout_plan* pl, hipStream_t s) {
     const StepTail tail{pl->r.t_dev, pl->r.num_edges, pl->edges_per_step, pl->r.t_dev + 1,
                         (long long)pl->M * pl->N <= 256 ? pl->r.row_done : nullptr};
     MDNO_TRY(forward_impl(&pl->p, pl->traj, 0, pl->r.t_dev, pl->M, W, pl->N, pl->aa, pl->aa_per_member, pl->r.row_ptr,
-                          pl->r.src, pl->r.dst, pl->r.num_edges, pl->edge_cap, pl->traj, W - 1, nullptr,
-                          nullptr, pl->traj, W, nullptr, pl->fw, pl->status, s,
+                          pl->r.src, pl->r.dst, pl->r.num_edges, pl->edge_cap, pl->pbc_on ? nullptr : pl->traj, W - 1,
+                          pl->pbc_on ? pl->pbc_attr : nullptr, nullptr, pl->traj, W, nullptr, pl->fw, pl->status, s,
                           (pl->weights_cached ? WP_RUN_ONLY : WP_BOTH) | (act_flags ? WP_FLAGS_ZEROED : 0) |
                               (head ? WP_PROLOGUE_DONE : 0),
                           &tail));
@@ -520,6 +531,31 @@ extern "C" int mdno_rollout_plan_set_noise(mdno_rollout_plan* pl, float sigma, u
     // given noise right after its creation has thus captured its graphs twice, per creation and per regrown capacity:
     // a cost of the noise-on path only, kept so that mdno_rollout_plan_create stays as it is.  If the capture fails
     // here the error is returned and the plan is left WITHOUT graphs: it would run plain launches, same frames.)
+    MDNO_HIP(hipStreamSynchronize(pl->capture_stream));
+    plan_drop_graphs(pl);
+    return plan_capture(pl);
+}
+
+extern "C" int mdno_rollout_plan_set_box(mdno_rollout_plan* pl, const double* box, float* edge_attr) {
+    MDNO_REQUIRE(pl != nullptr, MDNO_EINVAL, "mdno_rollout_plan_set_box: null plan");
+    PbcBox b{};
+    if (box != nullptr) MDNO_TRY(pbc_box_from(box, pl->threshold, &b, "mdno_rollout_plan_set_box"));
+    const bool now = b.any();
+    MDNO_REQUIRE(!now || pl->p.ker_in == 6, MDNO_EINVAL,
+                 "mdno_rollout_plan_set_box: ker_in=%d, the periodic edge attributes are [image of the source, destination] (6)",
+                 pl->p.ker_in);
+    MDNO_REQUIRE(!now || edge_attr != nullptr, MDNO_EINVAL, "mdno_rollout_plan_set_box: null edge_attr with a periodic axis");
+    MDNO_REQUIRE(!now || (reinterpret_cast<uintptr_t>(edge_attr) & 7) == 0, MDNO_EINVAL,
+                 "mdno_rollout_plan_set_box: edge_attr not 8-B aligned");
+    const bool was = pl->pbc_on;
+    const bool same = was == now && (!now || (pl->pbc_attr == edge_attr && pl->box.L[0] == b.L[0] && pl->box.L[1] == b.L[1] &&
+                                              pl->box.L[2] == b.L[2]));
+    pl->pbc_on = now;
+    pl->box = b;
+    pl->pbc_attr = now ? edge_attr : nullptr;
+    if (same || !pl->capture_stream) return MDNO_OK;
+    // the captured step holds the graph kernels, the box and the edge source: capture it again (as set_noise does; if
+    // the capture fails the error is returned and the plan is left without graphs: plain launches, same frames)
     MDNO_HIP(hipStreamSynchronize(pl->capture_stream));
     plan_drop_graphs(pl);
     return plan_capture(pl);

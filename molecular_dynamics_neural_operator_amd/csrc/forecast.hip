@@ -26,8 +26,13 @@
 // in tile order.  Counts are integers: both forms give the same ones.
 //
 // mdno_contact_maps: the dense u8 [F, N, N] maps themselves, sixteen pair tests per thread, one 16-byte store each.
-#include "graph_small.h"
+//
+// The kernels that test pairs are templated on the pair test (pbc.h): OpenPair is within() itself, PbcPair the
+// minimum-image test of a periodic box (mdno_forecast_score_pbc / mdno_contact_maps_pbc, include/mdno_pbc.h) — symmetric
+// in its two atoms bit for bit as well (rint is odd), so the i <= j counting holds for both.
+#include "pbc.h"
 #include "reduce.h"
+#include "../../include/mdno_pbc.h"
 
 #include <cmath>
 
@@ -88,9 +93,10 @@ __device__ double rmsd2_from_moments(const double* s, double G, double n) {
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }   // false for NaN and Inf
 
 // ---------------------------------------------------------------------------------------------- LDS form
+template <class Pair>
 __global__ __launch_bounds__(kThreads) void forecast_score_lds_kernel(const float* __restrict__ frames,
                                                                       const float* __restrict__ truth,
-                                                                      int truth_per_member, int M, int N, double cutoff,
+                                                                      int truth_per_member, int M, int N, const Pair pair,
                                                                       double* __restrict__ mse, double* __restrict__ rmsd,
                                                                       int* __restrict__ flags,
                                                                       long long* __restrict__ counts) {
@@ -162,8 +168,8 @@ __global__ __launch_bounds__(kThreads) void forecast_score_lds_kernel(const floa
             const bool first = c < n1;
             const int i = first ? r : i2;
             const int j = first ? r + c : i2 + (c - n1);
-            const bool in_f = within(first ? p1x : p2x, first ? p1y : p2y, first ? p1z : p2z, p + 3 * j, cutoff);
-            const bool in_t = within(first ? q1x : q2x, first ? q1y : q2y, first ? q1z : q2z, q + 3 * j, cutoff);
+            const bool in_f = pair(first ? p1x : p2x, first ? p1y : p2y, first ? p1z : p2z, p + 3 * j);
+            const bool in_t = pair(first ? q1x : q2x, first ? q1y : q2y, first ? q1z : q2z, q + 3 * j);
             const int w = j == i ? 1 : 2;
             cnt[0] += in_f ? w : 0;
             cnt[1] += in_t ? w : 0;
@@ -258,10 +264,11 @@ __global__ __launch_bounds__(kThreads) void forecast_tile_cov_kernel(const float
 
 // cpart [SM, T2, T2, 3] (entries with bj < bi are never written nor read): thread t owns atom bi*256 + t and walks the
 // atoms of tile bj from LDS.  A diagonal tile counts its ordered pairs directly, the others twice.
+template <class Pair>
 __global__ __launch_bounds__(kThreads) void forecast_tile_contacts_kernel(const float* __restrict__ frames,
                                                                           const float* __restrict__ truth,
                                                                           int truth_per_member, int M, int N,
-                                                                          double cutoff, int* __restrict__ cpart) {
+                                                                          const Pair pair, int* __restrict__ cpart) {
     const int bi = blockIdx.y, bj = blockIdx.z, T2 = gridDim.y;
     if (bj < bi) return;
     __shared__ float pj[kPairTile * 3], qj[kPairTile * 3];
@@ -282,8 +289,8 @@ __global__ __launch_bounds__(kThreads) void forecast_tile_contacts_kernel(const 
         const double qx = Q[3 * (size_t)i], qy = Q[3 * (size_t)i + 1], qz = Q[3 * (size_t)i + 2];
         const int w = bi == bj ? 1 : 2;
         for (int j = 0; j < nj; ++j) {
-            const bool in_f = within(px, py, pz, pj + 3 * j, cutoff);
-            const bool in_t = within(qx, qy, qz, qj + 3 * j, cutoff);
+            const bool in_f = pair(px, py, pz, pj + 3 * j);
+            const bool in_t = pair(qx, qy, qz, qj + 3 * j);
             cnt[0] += in_f ? w : 0;
             cnt[1] += in_t ? w : 0;
             cnt[2] += (in_f && in_t) ? w : 0;
@@ -347,8 +354,9 @@ __global__ __launch_bounds__(64) void forecast_first_flag_kernel(const int* __re
 
 // ---------------------------------------------------------------------------------------------- dense maps
 // maps u8 [F*N*N] flat, 16 consecutive bytes per thread as one 16-byte store (the tail of the last thread by bytes)
+template <class Pair>
 __global__ __launch_bounds__(kThreads) void contact_maps_kernel(const float* __restrict__ frames, long long F, int N,
-                                                                double cutoff, unsigned char* __restrict__ maps) {
+                                                                const Pair pair, unsigned char* __restrict__ maps) {
     const long long nn = (long long)N * N, total = F * nn;
     const long long base = ((long long)blockIdx.x * kThreads + threadIdx.x) * 16;
     if (base >= total) return;
@@ -362,7 +370,7 @@ __global__ __launch_bounds__(kThreads) void contact_maps_kernel(const float* __r
 #pragma unroll
     for (int b = 0; b < 16; ++b) {
         if (b < count) {
-            if (within(xi, yi, zi, pos + 3 * (size_t)j, cutoff)) word[b >> 2] |= 1u << (8 * (b & 3));
+            if (pair(xi, yi, zi, pos + 3 * (size_t)j)) word[b >> 2] |= 1u << (8 * (b & 3));
             if (++j == N) {
                 j = 0;
                 if (++i == N) {
@@ -417,11 +425,10 @@ extern "C" size_t mdno_forecast_score_workspace_bytes(int S, int M, int N, int f
     return ScoreCarve(nullptr, (long long)S * M, N, use_lds_form(N, form)).total;
 }
 
-extern "C" int mdno_forecast_score(const float* frames, const float* truth, int truth_per_member, int S, int M, int N,
-                                   double cutoff, double* mse, double* rmsd, int64_t* counts, int32_t* first_nonfinite,
-                                   int form, void* workspace, size_t workspace_bytes, void* stream) {
-    MDNO_REQUIRE(S >= 0 && M >= 0 && N >= 0, MDNO_EINVAL, "forecast_score: S=%d M=%d N=%d", S, M, N);
-    MDNO_REQUIRE(cutoff_ok(cutoff), MDNO_EINVAL, "forecast_score: cutoff %g is not a finite non-negative number", cutoff);
+template <class Pair>
+static int forecast_score_impl(const float* frames, const float* truth, int truth_per_member, int S, int M, int N,
+                               const Pair& pair, double* mse, double* rmsd, int64_t* counts, int32_t* first_nonfinite,
+                               int form, void* workspace, size_t workspace_bytes, void* stream) {
     MDNO_REQUIRE(form >= MDNO_FORECAST_AUTO && form <= MDNO_FORECAST_TILED, MDNO_EINVAL, "forecast_score: form=%d", form);
     MDNO_REQUIRE(M == 0 || first_nonfinite, MDNO_EINVAL, "forecast_score: null pointer (first_nonfinite)");
     const long long SM = (long long)S * M;
@@ -444,15 +451,15 @@ extern "C" int mdno_forecast_score(const float* frames, const float* truth, int 
     MDNO_REQUIRE(workspace_bytes >= c.total, MDNO_EWORKSPACE, "forecast_score: workspace %zu < %zu", workspace_bytes, c.total);
     long long* cnt = reinterpret_cast<long long*>(counts);
     if (lds) {
-        hipLaunchKernelGGL(forecast_score_lds_kernel, dim3((unsigned)SM), dim3(kThreads), (size_t)N * 24, st, frames, truth,
-                           truth_per_member, M, N, cutoff, mse, rmsd, c.flags, cnt);
+        hipLaunchKernelGGL(forecast_score_lds_kernel<Pair>, dim3((unsigned)SM), dim3(kThreads), (size_t)N * 24, st, frames, truth,
+                           truth_per_member, M, N, pair, mse, rmsd, c.flags, cnt);
     } else {
         hipLaunchKernelGGL(forecast_tile_sums_kernel, dim3((unsigned)SM, T), dim3(kThreads), 0, st, frames, truth,
                            truth_per_member, M, N, c.part1);
         hipLaunchKernelGGL(forecast_tile_cov_kernel, dim3((unsigned)SM, T), dim3(kThreads), 0, st, frames, truth,
                            truth_per_member, M, N, c.part1, c.part2);
-        hipLaunchKernelGGL(forecast_tile_contacts_kernel, dim3((unsigned)SM, T2, T2), dim3(kThreads), 0, st, frames, truth,
-                           truth_per_member, M, N, cutoff, c.cpart);
+        hipLaunchKernelGGL(forecast_tile_contacts_kernel<Pair>, dim3((unsigned)SM, T2, T2), dim3(kThreads), 0, st, frames, truth,
+                           truth_per_member, M, N, pair, c.cpart);
         hipLaunchKernelGGL(forecast_tile_finish_kernel, dim3((unsigned)SM), dim3(kThreads), 0, st, c.part1, c.part2, c.cpart,
                            N, T, T2, mse, rmsd, c.flags, cnt);
     }
@@ -460,16 +467,49 @@ extern "C" int mdno_forecast_score(const float* frames, const float* truth, int 
     return check_launch("forecast_score");
 }
 
-extern "C" int mdno_contact_maps(const float* frames, int64_t F, int N, double cutoff, uint8_t* maps, void* stream) {
-    MDNO_REQUIRE(F >= 0 && N >= 0, MDNO_EINVAL, "contact_maps: F=%lld N=%d", (long long)F, N);
-    MDNO_REQUIRE(cutoff_ok(cutoff), MDNO_EINVAL, "contact_maps: cutoff %g is not a finite non-negative number", cutoff);
+extern "C" int mdno_forecast_score(const float* frames, const float* truth, int truth_per_member, int S, int M, int N,
+                                   double cutoff, double* mse, double* rmsd, int64_t* counts, int32_t* first_nonfinite,
+                                   int form, void* workspace, size_t workspace_bytes, void* stream) {
+    MDNO_REQUIRE(S >= 0 && M >= 0 && N >= 0, MDNO_EINVAL, "forecast_score: S=%d M=%d N=%d", S, M, N);
+    MDNO_REQUIRE(cutoff_ok(cutoff), MDNO_EINVAL, "forecast_score: cutoff %g is not a finite non-negative number", cutoff);
+    return forecast_score_impl(frames, truth, truth_per_member, S, M, N, OpenPair{cutoff}, mse, rmsd, counts, first_nonfinite,
+                               form, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mdno_forecast_score_pbc(const float* frames, const float* truth, int truth_per_member, int S, int M, int N,
+                                       double cutoff, const double* box, double* mse, double* rmsd, int64_t* counts,
+                                       int32_t* first_nonfinite, int form, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    MDNO_REQUIRE(S >= 0 && M >= 0 && N >= 0, MDNO_EINVAL, "forecast_score_pbc: S=%d M=%d N=%d", S, M, N);
+    PbcPair pair{cutoff, {}};
+    MDNO_TRY(pbc_box_from(box, cutoff, &pair.box, "mdno_forecast_score_pbc"));
+    return forecast_score_impl(frames, truth, truth_per_member, S, M, N, pair, mse, rmsd, counts, first_nonfinite, form,
+                               workspace, workspace_bytes, stream);
+}
+
+template <class Pair>
+static int contact_maps_impl(const float* frames, int64_t F, int N, const Pair& pair, uint8_t* maps, void* stream) {
     if (F == 0 || N == 0) return MDNO_OK;
     MDNO_REQUIRE(frames && maps, MDNO_EINVAL, "contact_maps: null pointer");
     MDNO_REQUIRE((reinterpret_cast<uintptr_t>(maps) & 15) == 0, MDNO_EINVAL, "contact_maps: maps not 16-B aligned");
     const long long total = (long long)F * N * N;
     const long long blocks = (total + 16ll * kThreads - 1) / (16ll * kThreads);
     MDNO_REQUIRE(blocks < (1ll << 31) - 1, MDNO_EUNSUPPORTED, "contact_maps: %lld bytes exceed one launch", total);
-    hipLaunchKernelGGL(contact_maps_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream), frames,
-                       (long long)F, N, cutoff, maps);
+    hipLaunchKernelGGL(contact_maps_kernel<Pair>, dim3((unsigned)blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       frames, (long long)F, N, pair, maps);
     return check_launch("contact_maps");
+}
+
+extern "C" int mdno_contact_maps(const float* frames, int64_t F, int N, double cutoff, uint8_t* maps, void* stream) {
+    MDNO_REQUIRE(F >= 0 && N >= 0, MDNO_EINVAL, "contact_maps: F=%lld N=%d", (long long)F, N);
+    MDNO_REQUIRE(cutoff_ok(cutoff), MDNO_EINVAL, "contact_maps: cutoff %g is not a finite non-negative number", cutoff);
+    return contact_maps_impl(frames, F, N, OpenPair{cutoff}, maps, stream);
+}
+
+extern "C" int mdno_contact_maps_pbc(const float* frames, int64_t F, int N, double cutoff, const double* box, uint8_t* maps,
+                                     void* stream) {
+    MDNO_REQUIRE(F >= 0 && N >= 0, MDNO_EINVAL, "contact_maps_pbc: F=%lld N=%d", (long long)F, N);
+    PbcPair pair{cutoff, {}};
+    MDNO_TRY(pbc_box_from(box, cutoff, &pair.box, "mdno_contact_maps_pbc"));
+    return contact_maps_impl(frames, F, N, pair, maps, stream);
 }

@@ -40,8 +40,10 @@ __global__ __launch_bounds__(256) void radius_count_kernel(const float* __restri
     if (lane == 0) deg[r] = cnt;
 }
 
+}  // namespace
+
 // Pass 2: exclusive scan of deg -> row_ptr, clipped at edge_cap (single workgroup; R is small
-// next to the per-edge work that follows).
+// next to the per-edge work that follows).  External linkage (kernels.h): the periodic graph (pbc.hip) launches it too.
 __global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__ deg, int R, long long cap,
                                                          int* __restrict__ row_ptr, int* __restrict__ num_edges,
                                                          int* __restrict__ status, int* __restrict__ zero_words,
@@ -79,6 +81,8 @@ __global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__
         if (total > cap && status) atomicOr(status, MDNO_STATUS_EDGE_OVERFLOW);
     }
 }
+
+namespace {
 
 // Pass 3: write each row's sources in ascending order (ballot + prefix popcount keeps the order
 // deterministic) and, optionally, the destination of every edge.

@@ -30,6 +30,13 @@ int radius_graph(const float* frames, int frame, const int* t_dev, int M, int N,
                  int* src, int* dst, long long edge_cap, int* num_edges, int* status, hipStream_t s,
                  int* zero_words = nullptr, int n_zero = 0, void* scratch = nullptr, size_t scratch_bytes = 0);
 
+// exclusive scan of deg [R] -> row_ptr [R + 1] clipped at cap, *num_edges, the overflow bit of *status, and n_zero
+// (<= 64) words of zero_words reset: one 1,024-thread workgroup (graph.hip; shared by the open and the periodic graph)
+__global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__ deg, int R, long long cap,
+                                                         int* __restrict__ row_ptr, int* __restrict__ num_edges,
+                                                         int* __restrict__ status, int* __restrict__ zero_words,
+                                                         int n_zero);
+
 struct EdgeMlpWeights {
     const float *w0, *b0, *w1, *b1, *w2, *b2;
 };

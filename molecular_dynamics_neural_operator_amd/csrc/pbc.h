@@ -1,0 +1,62 @@
+// Orthorhombic periodic boundary conditions: THE minimum-image rule (include/mdno_pbc.h), used by the
+// periodic radius graph (pbc.hip), by a rollout step with a box (engine.hip) and by the periodic scoring kernels
+// (forecast.hip).  One definition: every kernel that tests a pair under a box calls within_pbc below.
+#pragma once
+#include "graph_small.h"
+
+namespace mdno {
+
+// box lengths and their reciprocals (1.0 / L, formed once on the host); L == 0: the axis is open (inv == 0 as well)
+struct PbcBox {
+    double L[3];
+    double inv[3];
+    bool any() const { return L[0] > 0.0 || L[1] > 0.0 || L[2] > 0.0; }
+};
+
+// Validates `box` (f64 [3]: every entry finite and >= 0; 0 = open axis; a periodic axis needs L >= 2 * cutoff so that a
+// pair has at most one image inside the strict cutoff) and fills `out`.  MDNO_EINVAL with a message otherwise.
+int pbc_box_from(const double* box, double cutoff, PbcBox* out, const char* who);
+
+// k * L for the image of source coordinate xj next to destination coordinate xi on one axis: all in fp64 on the fp32
+// coordinates, k = rint(d / L) round-half-even (rint is odd: the rule is symmetric in i and j), k = 0 on an open axis
+__device__ __forceinline__ double pbc_shift(double xi, double xj, double L, double inv) {
+    const double k = L > 0.0 ? rint((xj - xi) * inv) : 0.0;
+    return k * L;
+}
+
+// the pair test of within() (graph_small.h: same differences, same summation order, strict <) on the minimum image;
+// sh[a] = the shift that was tested, so that the caller can form the source's image (float)(x_j - sh)
+__device__ __forceinline__ bool within_pbc(double xi, double yi, double zi, const float* __restrict__ pj, double cutoff,
+                                           const PbcBox& b, double sh[3]) {
+    const double xj = pj[0], yj = pj[1], zj = pj[2];
+    sh[0] = pbc_shift(xi, xj, b.L[0], b.inv[0]);
+    sh[1] = pbc_shift(yi, yj, b.L[1], b.inv[1]);
+    sh[2] = pbc_shift(zi, zj, b.L[2], b.inv[2]);
+    const double dx = (xj - xi) - sh[0], dy = (yj - yi) - sh[1], dz = (zj - zi) - sh[2];
+    const double s = (dx * dx + dy * dy) + dz * dz;
+    return sqrt(s) < cutoff;
+}
+
+// Pair tests as kernel arguments (forecast.hip is templated on one of them): the open test is within() itself
+struct OpenPair {
+    double cutoff;
+    __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj) const {
+        return within(xi, yi, zi, pj, cutoff);
+    }
+};
+struct PbcPair {
+    double cutoff;
+    PbcBox box;
+    __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj) const {
+        double sh[3];
+        return within_pbc(xi, yi, zi, pj, cutoff, box, sh);
+    }
+};
+
+// Periodic radius graph of frame (frame + *t_dev) of frames f32 [T, M*N, 3]: the arguments of radius_graph (kernels.h)
+// plus the box and edge_attr f32 [edge_cap, 6] (NULL: topology only).  Brute force, one wave per destination row.
+int radius_graph_pbc(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, const PbcBox& box,
+                     int* row_ptr, int* src, int* dst, float* edge_attr, long long edge_cap, int* num_edges, int* status,
+                     hipStream_t s, int* zero_words = nullptr, int n_zero = 0);
+
+}  // namespace mdno

@@ -72,17 +72,20 @@ class ForecastScore:
                              torch.cat([p.contacts for p in parts], 1), torch.cat([p.first_nonfinite for p in parts], 0))
 
 
-def score_forecast(frames: torch.Tensor, truth: torch.Tensor, threshold: float = 8.0, form: str = "auto") -> ForecastScore:
+def score_forecast(frames: torch.Tensor, truth: torch.Tensor, threshold: float = 8.0, form: str = "auto",
+                   box=None) -> ForecastScore:
     """frames f32 [S, M, N, 3] (device) against truth [S, N, 3] (the same for every member) or [S, M, N, 3].
     Asynchronous on the current stream: nothing is read back, nothing waits for the device.  CPU tensors, wrong ranks
     and mismatched S, M or N raise `MdnoError` before any device work.  `form` forces one of the two kernel forms
-    (ops.forecast_score); the default chooses by N."""
-    return ForecastScore(*ops.forecast_score(frames, truth, threshold, form))
+    (ops.forecast_score); the default chooses by N.  `box` = (Lx, Ly, Lz), 0 for an open axis: contacts are counted
+    under the minimum-image rule of a periodic cell (include/mdno_pbc.h); mse, rmsd and first_nonfinite are unchanged."""
+    return ForecastScore(*ops.forecast_score(frames, truth, threshold, form, box))
 
 
-def contact_maps(frames: torch.Tensor, threshold: float = 8.0) -> torch.Tensor:
-    """u8 [..., N, N] for frames [..., N, 3]: the reference's `get_contact_map`, for the movie."""
-    return ops.contact_maps(frames, threshold)
+def contact_maps(frames: torch.Tensor, threshold: float = 8.0, box=None) -> torch.Tensor:
+    """u8 [..., N, N] for frames [..., N, 3]: the reference's `get_contact_map`, for the movie.  `box`: a periodic cell
+    (Lx, Ly, Lz), contacts by the minimum image."""
+    return ops.contact_maps(frames, threshold, box)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -574,18 +574,29 @@ class KernelNNNotebook(KernelNN):
 
 
 # --------------------------------------------------------------------------- graph construction
-def construct_pairdata(x_position, x_aminoacid, threshold: float = 8.0) -> PairData:
+def construct_pairdata(x_position, x_aminoacid, threshold: float = 8.0, box=None) -> PairData:
     """Radius graph + edge attributes of the LAST frame of ``x_position`` ([W,N,3]; a single frame
-    [N,3] is accepted as in the notebook).  Returns tensors on the GPU."""
+    [N,3] is accepted as in the notebook).  Returns tensors on the GPU.
+
+    ``box`` = (Lx, Ly, Lz), 0 for an open axis: the minimum-image graph of a periodic cell (include/mdno_pbc.h).
+    The sample then carries the IMAGED attributes — edge (s -> t) has [image of s next to t, position of t] — and its
+    edge list in the graph kernel's own order (sorted by target, sources ascending): ``edge_index[0]`` = sources."""
+    box = ops.check_box(box, threshold)
     dev = require_gpu()
     xp = torch.as_tensor(np.asarray(x_position) if not torch.is_tensor(x_position) else x_position)
     xp = xp.to(device=dev, dtype=torch.float32)
     single = xp.dim() == 2
     last = (xp if single else xp[-1]).contiguous()
     n = last.shape[0]
-    g = ops.radius_graph(last, n, threshold)
-    edge_index = g.to_edge_index()
-    edge_attr = torch.cat([last[edge_index[0]], last[edge_index[1]]], dim=1)
+    if box is not None:
+        g, attr = ops.radius_graph_pbc(last, n, threshold, box)
+        e = g.edge_count()
+        edge_index = torch.stack([g.src[:e], g.dst[:e]]).to(torch.long)
+        edge_attr = attr[:e]
+    else:
+        g = ops.radius_graph(last, n, threshold)
+        edge_index = g.to_edge_index()
+        edge_attr = torch.cat([last[edge_index[0]], last[edge_index[1]]], dim=1)
     if torch.is_tensor(x_aminoacid):
         x_aminoacid = x_aminoacid.to(dev)
     return PairData(x_aminoacid=x_aminoacid, x_position=xp, edge_attr=edge_attr, edge_index=edge_index)

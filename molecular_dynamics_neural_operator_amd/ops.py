@@ -60,6 +60,69 @@ def radius_graph(pos: torch.Tensor, n_atoms: int, cutoff: float = 8.0, edge_cap:
     return CSRGraph(row_ptr, src, dst, ne, cap, None, status)
 
 
+def check_box(box, cutoff: float, what: str = "box"):
+    """A periodic box (include/mdno_pbc.h) as three Python floats, or None for `box` None or all zero (no periodic
+    axis: the open path).  Three finite lengths >= 0 (0 = open axis), every periodic one >= 2 * cutoff; anything else
+    raises MdnoError — on the host, before any device work."""
+    import math
+    if box is None:
+        return None
+    if torch.is_tensor(box):
+        box = box.detach().cpu().reshape(-1).tolist()
+    try:
+        vals = [float(v) for v in (box if hasattr(box, "__len__") else list(box))]
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}={box!r}: expected three lengths (Lx, Ly, Lz)") from None
+    if len(vals) != 3:
+        raise MdnoError(f"{what} has {len(vals)} entries, expected (Lx, Ly, Lz)")
+    cutoff = float(cutoff)
+    if not (math.isfinite(cutoff) and cutoff >= 0.0):
+        raise MdnoError(f"cutoff {cutoff} is not a finite non-negative number")
+    for a, L in enumerate(vals):
+        if not (math.isfinite(L) and L >= 0.0):
+            raise MdnoError(f"{what}[{a}] = {L}: a finite length, or 0 for an open axis")
+        if L != 0.0 and not L >= 2.0 * cutoff:
+            raise MdnoError(f"{what}[{a}] = {L} < 2 * cutoff = {2.0 * cutoff}: a pair would have more than one image "
+                            f"inside the cutoff")
+    return tuple(vals) if any(v > 0.0 for v in vals) else None
+
+
+def box_arg(box):
+    """(Lx, Ly, Lz) as the host `const double*` the C ABI takes (keep the returned array alive across the call)."""
+    return (C.c_double * 3)(*box)
+
+
+def radius_graph_pbc(pos: torch.Tensor, n_atoms: int, cutoff: float, box, edge_cap: Optional[int] = None,
+                     with_attr: bool = True):
+    """Periodic radius graph (include/mdno_pbc.h): pos f32 [M*N,3] (or [M,N,3]), box = (Lx, Ly, Lz) with 0 for an open
+    axis -> (CSRGraph, edge_attr f32 [edge_cap, 6] or None).  Row p of edge_attr is [image of pos[src[p]] next to the
+    destination, pos[dst[p]]]; rows from the edge count on are not written.  Brute force at every size."""
+    vals = check_box(box, cutoff)
+    if vals is None:
+        vals = (0.0, 0.0, 0.0)      # no periodic axis: the open graph, with its attributes
+    if not torch.is_tensor(pos) or not pos.is_cuda:
+        raise MdnoError("radius_graph_pbc: pos must be a GPU tensor (no CPU fallback exists)")
+    lib = _lib.load()
+    pos = f32(pos).reshape(-1, 3)
+    R = pos.shape[0]
+    if n_atoms <= 0 or R == 0 or R % n_atoms:
+        raise MdnoError(f"{R} rows is not a positive multiple of n_atoms={n_atoms}")
+    M = R // n_atoms
+    cap = int(edge_cap) if edge_cap is not None else M * n_atoms * n_atoms
+    cap = max(cap, R)
+    dev = pos.device
+    row_ptr = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    src = torch.empty(cap, dtype=torch.int32, device=dev)
+    dst = torch.empty(cap, dtype=torch.int32, device=dev)
+    ne = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    attr = torch.empty((cap, 6), dtype=torch.float32, device=dev) if with_attr else None
+    b = box_arg(vals)
+    check(lib.mdno_radius_graph_pbc(ptr(pos), M, n_atoms, float(cutoff), b, ptr(row_ptr), ptr(src), ptr(dst), ptr(attr), cap,
+                                    ptr(ne), ptr(status), stream_ptr(dev)), "mdno_radius_graph_pbc")
+    return CSRGraph(row_ptr, src, dst, ne, cap, None, status), attr
+
+
 def coo_to_csr(edge_index: torch.Tensor, num_nodes: int, validate: bool = True,
                status: Optional[torch.Tensor] = None) -> CSRGraph:
     """edge_index i64 [2,E] (row 0 = source, row 1 = target) -> CSRGraph with `perm`.  A node id
@@ -1198,11 +1261,13 @@ def _device_frames(t, what: str, ranks) -> torch.Tensor:
     return f32(t)
 
 
-def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.0, form: str = "auto"):
+def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.0, form: str = "auto", box=None):
     """frames f32 [S,M,N,3] against truth [S,N,3] (shared by the members) or [S,M,N,3] ->
     (mse f64 [S,M], rmsd f64 [S,M], counts i64 [S,M,3], first_nonfinite i32 [M]); mdno_forecast_score.  Asynchronous on
     the current stream, nothing is read back.  `form`: "auto" (one workgroup per (s, m) up to 2,048 atoms, tiled above),
-    "lds" or "tiled" to force one (same counts; a test hook)."""
+    "lds" or "tiled" to force one (same counts; a test hook).  `box` = (Lx, Ly, Lz): contacts under the minimum-image
+    rule of include/mdno_pbc.h (mdno_forecast_score_pbc); mse, rmsd and first_nonfinite do not depend on it."""
+    box = check_box(box, cutoff)
     frames = _device_frames(frames, "frames", (4,))
     truth = _device_frames(truth, "truth", (3, 4))
     if truth.device != frames.device:
@@ -1226,16 +1291,21 @@ def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.
     first = torch.empty(M, dtype=torch.int32, device=dev)
     nbytes = lib.mdno_forecast_score_workspace_bytes(S, M, N, FORECAST_FORMS[form])
     ws = _ws(nbytes, dev) if scored else None
-    check(lib.mdno_forecast_score(ptr(frames) if scored else None, ptr(truth) if scored else None, int(truth.dim() == 4),
-                                  S, M, N, float(cutoff), ptr(mse) if scored else None, ptr(rmsd) if scored else None,
-                                  ptr(counts) if scored else None, ptr(first) if M else None, FORECAST_FORMS[form],
-                                  ptr(ws), ws.numel() if scored else 0, stream_ptr(dev)), "mdno_forecast_score")
+    head = (ptr(frames) if scored else None, ptr(truth) if scored else None, int(truth.dim() == 4), S, M, N, float(cutoff))
+    tail = (ptr(mse) if scored else None, ptr(rmsd) if scored else None, ptr(counts) if scored else None,
+            ptr(first) if M else None, FORECAST_FORMS[form], ptr(ws), ws.numel() if scored else 0, stream_ptr(dev))
+    if box is None:
+        check(lib.mdno_forecast_score(*head, *tail), "mdno_forecast_score")
+    else:
+        check(lib.mdno_forecast_score_pbc(*head, box_arg(box), *tail), "mdno_forecast_score_pbc")
     return mse, rmsd, counts, first
 
 
-def contact_maps(frames: torch.Tensor, cutoff: float = 8.0) -> torch.Tensor:
+def contact_maps(frames: torch.Tensor, cutoff: float = 8.0, box=None) -> torch.Tensor:
     """frames f32 [..., N, 3] -> u8 [..., N, N], 1 where the pair is within `cutoff` (the radius graph's own test, self
-    pairs included): the dense map get_contact_map (graph_kernel.py:416-424) builds.  mdno_contact_maps."""
+    pairs included): the dense map get_contact_map (graph_kernel.py:416-424) builds.  mdno_contact_maps.  `box` =
+    (Lx, Ly, Lz): the minimum-image test of include/mdno_pbc.h (mdno_contact_maps_pbc)."""
+    box = check_box(box, cutoff)
     frames = _device_frames(frames, "frames", tuple(range(2, 9)))
     lib = _lib.load()
     N = frames.shape[-2]
@@ -1245,6 +1315,10 @@ def contact_maps(frames: torch.Tensor, cutoff: float = 8.0) -> torch.Tensor:
         F *= d
     maps = torch.empty(lead + (N, N), dtype=torch.uint8, device=frames.device)
     empty = F == 0 or N == 0
-    check(lib.mdno_contact_maps(None if empty else ptr(frames), F, N, float(cutoff), None if empty else ptr(maps),
-                                stream_ptr(frames.device)), "mdno_contact_maps")
+    if box is None:
+        check(lib.mdno_contact_maps(None if empty else ptr(frames), F, N, float(cutoff), None if empty else ptr(maps),
+                                    stream_ptr(frames.device)), "mdno_contact_maps")
+    else:
+        check(lib.mdno_contact_maps_pbc(None if empty else ptr(frames), F, N, float(cutoff), box_arg(box),
+                                        None if empty else ptr(maps), stream_ptr(frames.device)), "mdno_contact_maps_pbc")
     return maps

@@ -40,6 +40,26 @@ AUTO_FACTORED_MIN_EDGES = 16384        # per member
 AUTO_MATERIALIZED_MAX_WORKSPACE = 64 << 30
 
 
+def _model_ker_in(model) -> Optional[int]:
+    """Edge attributes per edge of a KernelNN or an ops.ParamPack, read on the host (None: not recognisable here)."""
+    if isinstance(model, ops.ParamPack):
+        return int(model.tensors["k_w0"].shape[1])
+    try:
+        return int(model.state_dict()["conv1.net.layers.0.weight"].shape[1])
+    except (AttributeError, KeyError):
+        return None
+
+
+def check_rollout_box(model, box, threshold: float):
+    """`box` of an engine as ops.check_box returns it, plus what a periodic step needs of the model (ker_in == 6);
+    MdnoError otherwise, before any device work."""
+    box = ops.check_box(box, threshold)
+    if box is not None and _model_ker_in(model) not in (None, 6):
+        raise MdnoError(f"box: the model reads ker_in={_model_ker_in(model)} edge attributes, a periodic step forms "
+                        f"[image of the source, destination] (6)")
+    return box
+
+
 class RolloutEngine:
     """Owns the trajectory buffer [W+max_steps, M, N, 3], the workspace and the captured step.
 
@@ -47,11 +67,21 @@ class RolloutEngine:
     every step adds noise_sigma * z(noise_seed, member_ids[m], absolute step, atom, component) to the frame it produces,
     before the frame is stored and read again.  `member_ids` (default 0 .. M-1) are the members' GLOBAL ids: member g
     draws the same noise alone, in any batch, group or rank (pass `shard_members(...)` on a rank).  With noise_sigma = 0
-    (the default) nothing of this is launched or captured."""
+    (the default) nothing of this is launched or captured.
+
+    box = (Lx, Ly, Lz): a periodic rollout (include/mdno_pbc.h mdno_rollout_plan_set_box) —
+    every step builds the minimum-image radius graph of its newest frame and the forward reads the imaged edge
+    attributes the graph kernel wrote (a buffer [edge_cap, 6] the engine owns).  0 = an open axis; every periodic axis
+    needs L >= 2 * threshold; one box for all members, constant in time.  Frames are never wrapped.  With box = None
+    (the default) nothing of this is launched or captured.  `first_step_from_sample` is unchanged: the sample brings
+    its own edges (graph_kernel.construct_pairdata(..., box=))."""
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0,
                  max_steps: int = 1000, edge_cap: Optional[int] = None, device=None, use_graph: bool = True,
-                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None):
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None):
+        self.box = check_rollout_box(model, box, threshold)
+        self._box_attr = None            # f32 [edge_cap, 6] on the device, made with every plan of a periodic engine
+        self._box_arg = None
         self.lib = _lib.load()
         self.device = require_gpu(device if device not in (None, "cuda") else None)
         fc2 = getattr(model, "fc2", None)
@@ -115,7 +145,11 @@ class RolloutEngine:
         at; (count, True) when there are more."""
         R = self.M * self.N
         probe_cap = max(AUTO_FACTORED_MIN_DEGREE * R, self.M * AUTO_FACTORED_MIN_EDGES) + R
-        g = ops.radius_graph(self.traj[self.W - 1].reshape(R, 3), self.N, self.threshold, edge_cap=probe_cap)
+        last = self.traj[self.W - 1].reshape(R, 3)
+        if self.box is not None:
+            g, _ = ops.radius_graph_pbc(last, self.N, self.threshold, self.box, edge_cap=probe_cap, with_attr=False)
+        else:
+            g = ops.radius_graph(last, self.N, self.threshold, edge_cap=probe_cap)
         return int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
 
     def _fit_capacity(self, e: int, over: bool) -> bool:
@@ -171,8 +205,32 @@ class RolloutEngine:
                 self._member_ids_dev = torch.tensor(self.member_ids, dtype=torch.int32, device=self.device)
             check(self.lib.mdno_rollout_plan_set_noise(self.plan, self.noise_sigma, self.noise_seed,
                                                        ptr(self._member_ids_dev)), "mdno_rollout_plan_set_noise")
+        self._box_attr = None
+        if self.box is not None:         # (a rebuilt plan has a new capacity: a new attribute buffer)
+            self._box_attr = torch.empty((self.edge_cap, 6), dtype=torch.float32, device=self.device)
+            self._box_arg = ops.box_arg(self.box)
+            check(self.lib.mdno_rollout_plan_set_box(self.plan, self._box_arg, ptr(self._box_attr)),
+                  "mdno_rollout_plan_set_box")
         if self._timer_records:          # the timer lived in the plan just destroyed: its records are gone, the attachment is not
             check(self.lib.mdno_rollout_plan_timer_attach(self.plan, self._timer_records), "timer_attach")
+
+    def set_box(self, box) -> None:
+        """Give the engine another periodic cell, or None for the open step (mdno_rollout_plan_set_box: with None the
+        plan has the launches and the captured graph of one that never had a box).  Before the first step after
+        reset() only; later resets keep it."""
+        box = check_rollout_box(self.model, box, self.threshold)
+        if self.steps_done != 0:
+            raise MdnoError("set_box: only before the first step after reset()")
+        self.box = box
+        if not self.plan:
+            return
+        self._box_attr = None
+        if box is None:
+            check(self.lib.mdno_rollout_plan_set_box(self.plan, None, None), "mdno_rollout_plan_set_box")
+            return
+        self._box_attr = torch.empty((self.edge_cap, 6), dtype=torch.float32, device=self.device)
+        self._box_arg = ops.box_arg(box)
+        check(self.lib.mdno_rollout_plan_set_box(self.plan, self._box_arg, ptr(self._box_attr)), "mdno_rollout_plan_set_box")
 
     @property
     def steps_per_launch(self) -> int:
@@ -347,17 +405,22 @@ class RolloutEngine:
                             f"{self.steps_done} produced")
         return first_step, steps
 
+    _OWN_BOX = object()
+
     def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
-              threshold: Optional[float] = None):
+              threshold: Optional[float] = None, box=_OWN_BOX):
         """Score the produced frames of steps first_step .. first_step + steps - 1 (default: all) against
         truth f32 [steps, N, 3] (every member against the same frames) or [steps, M, N, 3] -> `forecast.ForecastScore`.
         The frames are read where they are (a view of the trajectory buffer, untouched); the scoring kernels run on
         the current stream after the engine's enqueued steps, without waiting on the host.  `threshold`: the contact
-        cutoff, the engine's own by default."""
+        cutoff, the engine's own by default.  `box`: the periodic cell the contacts are counted in, the engine's own by
+        default (None: open)."""
         from .forecast import score_forecast
         first_step, steps = self._score_range(first_step, steps)
+        threshold = self.threshold if threshold is None else threshold
+        box = self.box if box is RolloutEngine._OWN_BOX else ops.check_box(box, threshold)
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        return score_forecast(self.produced(first_step, steps), truth, self.threshold if threshold is None else threshold)
+        return score_forecast(self.produced(first_step, steps), truth, threshold, box=box)
 
     def close(self) -> None:
         if self.plan:
@@ -388,7 +451,8 @@ class GroupedRolloutEngine:
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0, max_steps: int = 1000,
                  edge_cap: Optional[int] = None, device=None, use_graph: bool = True, groups: int = 2,
-                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None):
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None):
+        self.box = check_rollout_box(model, box, threshold)      # one box for every group
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
         ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
         if len(ids) != self.M:
@@ -404,7 +468,7 @@ class GroupedRolloutEngine:
         self.engines = [RolloutEngine(model, hi - lo, n_atoms, window, threshold, max_steps=max_steps,
                                       edge_cap=None if edge_cap is None else max(1, -(-int(edge_cap) * (hi - lo) // self.M)),
                                       device=device, use_graph=use_graph, noise_sigma=noise_sigma, noise_seed=noise_seed,
-                                      member_ids=ids[lo:hi]) for lo, hi in self.bounds]
+                                      member_ids=ids[lo:hi], box=self.box) for lo, hi in self.bounds]
         self.device = self.engines[0].device
         self.max_steps = int(max_steps)
 
@@ -440,7 +504,10 @@ class GroupedRolloutEngine:
             R = self.M * self.N
             probe_cap = max(AUTO_FACTORED_MIN_DEGREE * R, self.M * AUTO_FACTORED_MIN_EDGES) + R
             last = f32(window[self.W - 1].to(self.device)).reshape(R, 3)
-            g = ops.radius_graph(last, self.N, e0.threshold, edge_cap=probe_cap)
+            if self.box is not None:
+                g, _ = ops.radius_graph_pbc(last, self.N, e0.threshold, self.box, edge_cap=probe_cap, with_attr=False)
+            else:
+                g = ops.radius_graph(last, self.N, e0.threshold, edge_cap=probe_cap)
             n_e, over = int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
             if over:
                 n_e = max(n_e, self.M * max(AUTO_FACTORED_MIN_DEGREE * self.N, AUTO_FACTORED_MIN_EDGES))
@@ -490,14 +557,14 @@ class GroupedRolloutEngine:
         return torch.cat([e.produced(first_step, steps) for e in self.engines], dim=1)
 
     def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
-              threshold: Optional[float] = None):
+              threshold: Optional[float] = None, box=RolloutEngine._OWN_BOX):
         """`RolloutEngine.score` for every group on its own frames, members in order: the bits of
-        `score_forecast(self.frames(), truth)` without assembling the trajectory."""
+        `score_forecast(self.frames(), truth)` without assembling the trajectory (`box`: the engines' own by default)."""
         from .forecast import ForecastScore
         if torch.is_tensor(truth) and truth.dim() == 4 and truth.shape[1] != self.M:
             raise MdnoError(f"truth shape {tuple(truth.shape)}: expected {self.M} members")
         per_member = torch.is_tensor(truth) and truth.dim() == 4
-        return ForecastScore.cat([e.score(truth[:, lo:hi].contiguous() if per_member else truth, first_step, steps, threshold)
+        return ForecastScore.cat([e.score(truth[:, lo:hi].contiguous() if per_member else truth, first_step, steps, threshold, box)
                                   for e, (lo, hi) in zip(self.engines, self.bounds)])
 
     @property

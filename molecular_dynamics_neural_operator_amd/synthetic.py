@@ -34,6 +34,14 @@ def box_frame(n_atoms: int = 504, density: float = 0.1, seed: int = 1) -> np.nda
     return ((rng.random((n_atoms, 3)) - 0.5) * side).astype(np.float32)
 
 
+def periodic_box_frame(n_atoms: int = 504, density: float = 0.1, seed: int = 1):
+    """Uniform atoms in a PERIODIC cube of side L = (n/density)^(1/3): (float32 [n_atoms, 3] in [0, L), L).  The bulk
+    counterpart of `box_frame`: under the minimum-image rule (include/mdno_pbc.h) every atom has the bulk degree."""
+    rng = np.random.default_rng(seed)
+    side = (n_atoms / density) ** (1.0 / 3.0)
+    return (rng.random((n_atoms, 3)) * side).astype(np.float32), float(side)
+
+
 def jitter_window(base: np.ndarray, window: int = 10, sigma: float = 0.05, seed: int = 0) -> np.ndarray:
     """`window` frames = base + N(0, sigma^2) per frame -> float32 [W, N, 3]."""
     rng = np.random.default_rng(seed + 7919)

@@ -7,8 +7,10 @@ from molecular_dynamics_neural_operator_amd.weights import near_identity_state_d
 ap = argparse.ArgumentParser()
 ap.add_argument('--noise-sigma', type=float, default=0.0, help='stochastic rollout: per-step Gaussian noise on the produced frame (A)')
 ap.add_argument('--noise-seed', type=int, default=0)
+ap.add_argument('--box', type=float, nargs=3, default=None, metavar=('LX', 'LY', 'LZ'),
+                help='periodic rollout: orthorhombic cell in A (0 = open axis, every periodic axis >= 16), e.g. 17.15 17.15 17.15')
 a = ap.parse_args()
-noise = dict(noise_sigma=a.noise_sigma, noise_seed=a.noise_seed)
+noise = dict(noise_sigma=a.noise_sigma, noise_seed=a.noise_seed, box=a.box)
 dev = torch.device('cuda:0')
 for N, steps in ((28, 20000), (504, 1500)):
     W = 10

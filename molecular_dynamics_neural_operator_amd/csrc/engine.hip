@@ -392,18 +392,14 @@ static int plan_enqueue_step(mdno_rollout_plan* pl, hipStream_t s) {
     const int n_zero = act_flags ? kEdgeMlpActivationFlags : 0;
     // short chain: graph and node prologue in one launch (the open graph only)
     const bool head = !pl->pbc_on && step_head_small_supported(pl->M, pl->N);
-    if (pl->pbc_on)      // periodic graph of the same frame: CSR + the attribute rows the forward below reads
-        MDNO_TRY(radius_graph_pbc(pl->traj, W - 1, pl->r.t_dev, pl->M, pl->N, pl->threshold, pl->box, pl->r.row_ptr,
-                                  pl->r.src, pl->r.dst, pl->pbc_attr, pl->edge_cap, pl->r.num_edges, pl->status, s,
-                                  act_flags, n_zero));
-    else if (head)
+    if (head)
         MDNO_TRY(step_head_small(&pl->p, pl->traj, W, pl->r.t_dev, pl->M, pl->N, pl->aa, pl->aa_per_member, pl->fw.xa,
                                  pl->threshold, pl->r.row_ptr, pl->r.src, pl->r.dst, pl->edge_cap, pl->r.num_edges,
                                  pl->status, act_flags, n_zero, s));
-    else
-        MDNO_TRY(radius_graph(pl->traj, W - 1, pl->r.t_dev, pl->M, pl->N, pl->threshold, pl->r.row_ptr, pl->r.src,
-                              pl->r.dst, pl->edge_cap, pl->r.num_edges, pl->status, s, act_flags, n_zero,
-                              pl->r.graph_scratch, pl->r.graph_scratch_bytes));
+    else      // (a periodic plan: CSR + the attribute rows the forward below reads)
+        MDNO_TRY(radius_graph(pl->traj, W - 1, pl->r.t_dev, pl->M, pl->N, pl->threshold, pl->pbc_on ? &pl->box : nullptr,
+                              pl->pbc_attr, pl->r.row_ptr, pl->r.src, pl->r.dst, pl->edge_cap, pl->r.num_edges, pl->status,
+                              s, act_flags, n_zero, pl->r.graph_scratch, pl->r.graph_scratch_bytes));
     const StepTail tail{pl->r.t_dev, pl->r.num_edges, pl->edges_per_step, pl->r.t_dev + 1,
                         (long long)pl->M * pl->N <= 256 ? pl->r.row_done : nullptr};
     MDNO_TRY(forward_impl(&pl->p, pl->traj, 0, pl->r.t_dev, pl->M, W, pl->N, pl->aa, pl->aa_per_member, pl->r.row_ptr,

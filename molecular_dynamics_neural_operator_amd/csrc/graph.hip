@@ -4,13 +4,13 @@
 // (O(N^2) f64), coo_matrix, and a Python loop over edges — executed once per rollout step with two
 // PCIe crossings (graph_kernel.py:406-410).  Here the frame never leaves HBM.  Three forms, one result: one workgroup
 // for a short chain (graph_small.h), brute force per member (N^2 pair tests: 15 us at N = 504), and from 8,192 atoms
-// per member on a cell list (below).
+// per member on a cell list (below).  The brute-force form is templated on the pair rule (pbc.h): under a periodic box
+// it is the minimum-image graph at every size, and its fill pass also writes the edge attribute rows.
 //
 // Bit-exactness: the pair test is evaluated exactly as scipy does on f32 coordinates — differences,
 // squares and the 3-term sum in f64 (squares of f32 differences are exact in f64, so FMA
 // contraction cannot change the sum), correctly rounded f64 sqrt, strict `<` against the f64 cutoff.
-#include "kernels.h"
-#include "graph_small.h"
+#include "pbc.h"
 
 namespace mdno {
 
@@ -19,10 +19,39 @@ namespace {
 constexpr int kRowsPerBlock = 4;  // one wave per destination row
 
 
-// Pass 1: in-degree of every row.  Lane l tests atoms j = l, l+64, ... of the row's own member.
-__global__ __launch_bounds__(256) void radius_count_kernel(const float* __restrict__ frames, int frame,
-                                                           const int* __restrict__ t_dev, int N, int R,
-                                                           double cutoff, int* __restrict__ deg) {
+// One 1,024-element chunk of a workgroup-wide exclusive scan (1,024 threads, 16 words of LDS in wsum): returns
+// *carry_s + the sum of v over the threads below this one and moves *carry_s on by the chunk's total.  Ends on a barrier.
+template <class T>
+__device__ __forceinline__ T scan_chunk(T v, T* wsum, T* carry_s) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    T incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    T woff = 0;
+    for (int k = 0; k < w; ++k) woff += wsum[k];
+    const T excl = *carry_s + woff + incl - v;
+    __syncthreads();
+    if (tid == 1023) *carry_s = excl + v;
+    __syncthreads();
+    return excl;
+}
+
+// Passes 1 and 3 of the brute-force form, one wave per destination row: lane l tests atoms j = l, l+64, ... of the
+// row's own member under the pair rule (pbc.h: OpenPair is within() itself, PbcPair the minimum image of a box).
+// FILL = false: in-degree of every row -> deg[r].  FILL = true: the row's sources in ascending order (ballot + prefix
+// popcount keeps the order deterministic), optionally the destination of every edge and, for a rule with an image,
+// the attribute row [image of the source next to the destination, destination] beside src[p]: the shift k * L that
+// the test used is the shift the attribute is formed with, so the edge-MLP sees exactly the image inside the cutoff.
+template <class Pair, bool FILL>
+__global__ __launch_bounds__(256) void radius_row_kernel(const float* __restrict__ frames, int frame,
+                                                         const int* __restrict__ t_dev, int N, int R, const Pair pair,
+                                                         int* __restrict__ deg, const int* __restrict__ row_ptr,
+                                                         long long cap, int* __restrict__ src, int* __restrict__ dst,
+                                                         float* __restrict__ attr) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (r >= R) return;
@@ -30,48 +59,57 @@ __global__ __launch_bounds__(256) void radius_count_kernel(const float* __restri
     const int m = r / N;
     const float* pm = pos + (size_t)m * N * 3;
     const float* pi = pos + (size_t)r * 3;
-    const double xi = pi[0], yi = pi[1], zi = pi[2];
+    const float fxi = pi[0], fyi = pi[1], fzi = pi[2];
+    const double xi = fxi, yi = fyi, zi = fzi;
+    long long base = FILL ? row_ptr[r] : 0;
     int cnt = 0;
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     for (int j0 = 0; j0 < N; j0 += 64) {
         const int j = j0 + lane;
-        const bool in = (j < N) && within(xi, yi, zi, pm + (size_t)j * 3, cutoff);
-        cnt += __popcll(__ballot(in));
+        double sh[3];
+        const float* pj = pm + (size_t)(j < N ? j : 0) * 3;
+        const bool in = (j < N) && pair(xi, yi, zi, pj, sh);
+        const unsigned long long mask = __ballot(in);
+        if (!FILL) {
+            cnt += __popcll(mask);
+        } else {
+            if (in) {
+                const long long p = base + __popcll(mask & lt);
+                if (p < cap) {
+                    src[p] = m * N + j;
+                    if (dst) dst[p] = r;
+                    if constexpr (Pair::has_image) {
+                        if (attr) {
+                            float2* a = reinterpret_cast<float2*>(attr + (size_t)p * 6);      // rows of 24 B: 8-B aligned
+                            a[0] = make_float2((float)((double)pj[0] - sh[0]), (float)((double)pj[1] - sh[1]));
+                            a[1] = make_float2((float)((double)pj[2] - sh[2]), fxi);
+                            a[2] = make_float2(fyi, fzi);
+                        }
+                    }
+                }
+            }
+            base += __popcll(mask);
+        }
     }
-    if (lane == 0) deg[r] = cnt;
+    if (!FILL && lane == 0) deg[r] = cnt;
 }
 
-}  // namespace
-
 // Pass 2: exclusive scan of deg -> row_ptr, clipped at edge_cap (single workgroup; R is small
-// next to the per-edge work that follows).  External linkage (kernels.h): the periodic graph (pbc.hip) launches it too.
+// next to the per-edge work that follows).
 __global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__ deg, int R, long long cap,
                                                          int* __restrict__ row_ptr, int* __restrict__ num_edges,
                                                          int* __restrict__ status, int* __restrict__ zero_words,
                                                          int n_zero) {
     __shared__ long long wsum[16];
     __shared__ long long carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < n_zero) zero_words[tid] = 0;
     if (tid == 0) carry_s = 0;
     __syncthreads();
     for (int base = 0; base < R; base += 1024) {
         const int i = base + tid;
-        long long v = (i < R) ? deg[i] : 0;
-        long long incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            long long t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        long long woff = 0;
-        for (int k = 0; k < w; ++k) woff += wsum[k];
-        const long long carry = carry_s;
-        const long long excl = carry + woff + incl - v;
+        const long long excl = scan_chunk<long long>((i < R) ? deg[i] : 0, wsum, &carry_s);
         if (i < R) row_ptr[i] = (int)(excl < cap ? excl : cap);
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + woff + incl;
-        __syncthreads();
     }
     if (tid == 0) {
         const long long total = carry_s;
@@ -79,40 +117,6 @@ __global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__
         row_ptr[R] = (int)e;
         *num_edges = (int)e;
         if (total > cap && status) atomicOr(status, MDNO_STATUS_EDGE_OVERFLOW);
-    }
-}
-
-namespace {
-
-// Pass 3: write each row's sources in ascending order (ballot + prefix popcount keeps the order
-// deterministic) and, optionally, the destination of every edge.
-__global__ __launch_bounds__(256) void radius_fill_kernel(const float* __restrict__ frames, int frame,
-                                                          const int* __restrict__ t_dev, int N, int R,
-                                                          double cutoff, const int* __restrict__ row_ptr,
-                                                          long long cap, int* __restrict__ src,
-                                                          int* __restrict__ dst) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const float* pos = frames + (size_t)(frame + (t_dev ? *t_dev : 0)) * R * 3;
-    const int m = r / N;
-    const float* pm = pos + (size_t)m * N * 3;
-    const float* pi = pos + (size_t)r * 3;
-    const double xi = pi[0], yi = pi[1], zi = pi[2];
-    long long base = row_ptr[r];
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int j0 = 0; j0 < N; j0 += 64) {
-        const int j = j0 + lane;
-        const bool in = (j < N) && within(xi, yi, zi, pm + (size_t)j * 3, cutoff);
-        const unsigned long long mask = __ballot(in);
-        if (in) {
-            const long long p = base + __popcll(mask & lt);
-            if (p < cap) {
-                src[p] = m * N + j;
-                if (dst) dst[p] = r;
-            }
-        }
-        base += __popcll(mask);
     }
 }
 
@@ -237,28 +241,15 @@ __global__ __launch_bounds__(256) void cell_count_kernel(const float* __restrict
 __global__ __launch_bounds__(1024) void cell_scan_kernel(const float* __restrict__ box, int* __restrict__ start) {
     __shared__ int wsum[16];
     __shared__ int carry_s;
-    const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int m = blockIdx.x, tid = threadIdx.x;
     const int ncell = reinterpret_cast<const int*>(box + (size_t)m * 8 + 4)[3];
     int* st = start + (size_t)m * (kCellMax + 1);
     if (tid == 0) carry_s = 0;
     __syncthreads();
     for (int base = 0; base < ncell + 1; base += 1024) {
         const int i = base + tid;
-        const int v = i < ncell ? st[i] : 0;
-        int incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int woff = 0;
-        for (int k = 0; k < w; ++k) woff += wsum[k];
-        const int carry = carry_s;
-        if (i <= ncell) st[i] = carry + woff + incl - v;
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + woff + incl;
-        __syncthreads();
+        const int excl = scan_chunk<int>(i < ncell ? st[i] : 0, wsum, &carry_s);
+        if (i <= ncell) st[i] = excl;
     }
 }
 
@@ -476,6 +467,21 @@ CooWs carve_coo(void* ws, long long E, int num_nodes) {
     return c;
 }
 
+// the brute-force form under one pair rule: count (in-degrees staged in src[0..R)), scan, fill
+template <class Pair>
+int radius_rows(const Pair pair, const float* frames, int frame, const int* t_dev, int N, int R, int* row_ptr, int* src,
+                int* dst, float* attr, long long cap, int* num_edges, int* status, hipStream_t s, int* zero_words,
+                int n_zero) {
+    const int blocks = (R + kRowsPerBlock - 1) / kRowsPerBlock;
+    hipLaunchKernelGGL((radius_row_kernel<Pair, false>), dim3(blocks), dim3(256), 0, s, frames, frame, t_dev, N, R, pair, src,
+                       (const int*)nullptr, cap, (int*)nullptr, (int*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, s, (const int*)src, R, cap, row_ptr, num_edges, status,
+                       zero_words, n_zero);
+    hipLaunchKernelGGL((radius_row_kernel<Pair, true>), dim3(blocks), dim3(256), 0, s, frames, frame, t_dev, N, R, pair,
+                       (int*)nullptr, (const int*)row_ptr, cap, src, dst, attr);
+    return check_launch("radius_graph");
+}
+
 }  // namespace
 }  // namespace mdno
 
@@ -483,20 +489,24 @@ size_t mdno::radius_graph_scratch_bytes(int M, int N) {
     return (M > 0 && N >= kCellMinAtoms) ? carve_cells(nullptr, M, N).total : 0;
 }
 
-int mdno::radius_graph(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, int* row_ptr,
-                       int* src, int* dst, long long edge_cap, int* num_edges, int* status, hipStream_t s,
-                       int* zero_words, int n_zero, void* scratch, size_t scratch_bytes) {
+int mdno::radius_graph(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, const PbcBox* box,
+                       float* edge_attr, int* row_ptr, int* src, int* dst, long long edge_cap, int* num_edges, int* status,
+                       hipStream_t s, int* zero_words, int n_zero, void* scratch, size_t scratch_bytes) {
     MDNO_REQUIRE(frames && row_ptr && src && num_edges, MDNO_EINVAL, "radius_graph: null pointer");
     MDNO_REQUIRE(M > 0 && N > 0 && edge_cap > 0 && frame >= 0, MDNO_EINVAL, "radius_graph: M=%d N=%d cap=%lld", M, N,
                  edge_cap);
     MDNO_REQUIRE((long long)M * N < (1ll << 31) - 1 && edge_cap < (1ll << 31) - 1, MDNO_EUNSUPPORTED,
                  "radius_graph: row or edge count exceeds int32 indexing");
     const int R = M * N;
-    const int blocks = (R + kRowsPerBlock - 1) / kRowsPerBlock;
     // The in-degrees are staged in src[0..R) (needs edge_cap >= R); the fill pass overwrites them.
     MDNO_REQUIRE(edge_cap >= R, MDNO_EINVAL, "radius_graph: edge_cap (%lld) < rows (%d)", edge_cap, R);
     MDNO_REQUIRE(n_zero >= 0 && n_zero <= 64 && (n_zero == 0 || zero_words), MDNO_EINVAL, "radius_graph: n_zero=%d", n_zero);
+    MDNO_REQUIRE(!box || !edge_attr || (reinterpret_cast<uintptr_t>(edge_attr) & 7) == 0, MDNO_EINVAL,
+                 "radius_graph: edge_attr not 8-B aligned");
     TimedSection ts(KID_GRAPH, s);
+    // a box (an all-open one included): the minimum-image rule, brute force at every size
+    if (box) return radius_rows(PbcPair{cutoff, *box}, frames, frame, t_dev, N, R, row_ptr, src, dst, edge_attr, edge_cap,
+                                num_edges, status, s, zero_words, n_zero);
     if (small_graph_supported(M, N)) {
         hipLaunchKernelGGL(radius_graph_small_kernel, dim3(1), dim3(1024), 0, s,
                            SmallGraphArgs{frames, frame, t_dev, N, R, cutoff, edge_cap, row_ptr, src, dst, num_edges,
@@ -507,6 +517,7 @@ int mdno::radius_graph(const float* frames, int frame, const int* t_dev, int M, 
         // cell list: bounding box + grid, populations, scan, scatter, then the two passes over 27 cells per row
         const CellWs c = carve_cells(scratch, M, N);
         const unsigned rb = (unsigned)((R + 255) / 256);
+        const int blocks = (R + kRowsPerBlock - 1) / kRowsPerBlock;
         hipLaunchKernelGGL(cell_box_kernel, dim3(M), dim3(1024), 0, s, frames, frame, t_dev, N, R, cutoff, c.box, c.start, c.cursor);
         hipLaunchKernelGGL(cell_count_kernel, dim3(rb), dim3(256), 0, s, frames, frame, t_dev, N, R, (const float*)c.box,
                            c.cell_of, c.start);
@@ -523,12 +534,8 @@ int mdno::radius_graph(const float* frames, int frame, const int* t_dev, int M, 
                            edge_cap, src, dst);
         return check_launch("radius_graph (cell list)");
     }
-    hipLaunchKernelGGL(radius_count_kernel, dim3(blocks), dim3(256), 0, s, frames, frame, t_dev, N, R, cutoff, src);
-    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, s, (const int*)src, R, edge_cap, row_ptr,
-                       num_edges, status, zero_words, n_zero);
-    hipLaunchKernelGGL(radius_fill_kernel, dim3(blocks), dim3(256), 0, s, frames, frame, t_dev, N, R, cutoff,
-                       (const int*)row_ptr, edge_cap, src, dst);
-    return check_launch("radius_graph");
+    return radius_rows(OpenPair{cutoff}, frames, frame, t_dev, N, R, row_ptr, src, dst, nullptr, edge_cap, num_edges, status,
+                       s, zero_words, n_zero);
 }
 
 using namespace mdno;
@@ -536,8 +543,8 @@ using namespace mdno;
 extern "C" int mdno_radius_graph_csr(const float* pos, int M, int N, double cutoff, int32_t* row_ptr,
                                      int32_t* src, int32_t* dst, int64_t edge_cap, int32_t* num_edges,
                                      int32_t* status, void* stream) {
-    return radius_graph(pos, 0, nullptr, M, N, cutoff, row_ptr, src, dst, (long long)edge_cap, num_edges, status,
-                        static_cast<hipStream_t>(stream));
+    return radius_graph(pos, 0, nullptr, M, N, cutoff, nullptr, nullptr, row_ptr, src, dst, (long long)edge_cap, num_edges,
+                        status, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t mdno_radius_graph_workspace_bytes(int M, int N) { return radius_graph_scratch_bytes(M, N); }
@@ -545,8 +552,8 @@ extern "C" size_t mdno_radius_graph_workspace_bytes(int M, int N) { return radiu
 extern "C" int mdno_radius_graph_csr_ws(const float* pos, int M, int N, double cutoff, int32_t* row_ptr, int32_t* src,
                                         int32_t* dst, int64_t edge_cap, int32_t* num_edges, int32_t* status,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    return radius_graph(pos, 0, nullptr, M, N, cutoff, row_ptr, src, dst, (long long)edge_cap, num_edges, status,
-                        static_cast<hipStream_t>(stream), nullptr, 0, workspace, workspace_bytes);
+    return radius_graph(pos, 0, nullptr, M, N, cutoff, nullptr, nullptr, row_ptr, src, dst, (long long)edge_cap, num_edges,
+                        status, static_cast<hipStream_t>(stream), nullptr, 0, workspace, workspace_bytes);
 }
 
 extern "C" size_t mdno_coo_to_csr_workspace_bytes(int64_t E, int num_nodes) {

@@ -25,17 +25,13 @@ struct TimedSection {
 // activation flags here instead of with a launch of its own
 // scratch (radius_graph_scratch_bytes; 0 below 8,192 atoms per member): with it a large member's graph is built
 // through a cell list instead of N^2 pair tests — the same edges in the same order
+// box (pbc.h; NULL: the open graph): the minimum-image graph, brute force at every size, with edge_attr f32
+// [edge_cap, 6] (8-B aligned; NULL: topology only) = [image of the source next to the destination, destination] per edge
+struct PbcBox;
 size_t radius_graph_scratch_bytes(int M, int N);
-int radius_graph(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, int* row_ptr,
-                 int* src, int* dst, long long edge_cap, int* num_edges, int* status, hipStream_t s,
-                 int* zero_words = nullptr, int n_zero = 0, void* scratch = nullptr, size_t scratch_bytes = 0);
-
-// exclusive scan of deg [R] -> row_ptr [R + 1] clipped at cap, *num_edges, the overflow bit of *status, and n_zero
-// (<= 64) words of zero_words reset: one 1,024-thread workgroup (graph.hip; shared by the open and the periodic graph)
-__global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__ deg, int R, long long cap,
-                                                         int* __restrict__ row_ptr, int* __restrict__ num_edges,
-                                                         int* __restrict__ status, int* __restrict__ zero_words,
-                                                         int n_zero);
+int radius_graph(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, const PbcBox* box,
+                 float* edge_attr, int* row_ptr, int* src, int* dst, long long edge_cap, int* num_edges, int* status,
+                 hipStream_t s, int* zero_words = nullptr, int n_zero = 0, void* scratch = nullptr, size_t scratch_bytes = 0);
 
 struct EdgeMlpWeights {
     const float *w0, *b0, *w1, *b1, *w2, *b2;

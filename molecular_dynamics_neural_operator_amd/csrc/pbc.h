@@ -1,6 +1,6 @@
 // Orthorhombic periodic boundary conditions: THE minimum-image rule (include/mdno_pbc.h), used by the
-// periodic radius graph (pbc.hip), by a rollout step with a box (engine.hip) and by the periodic scoring kernels
-// (forecast.hip).  One definition: every kernel that tests a pair under a box calls within_pbc below.
+// radius graph under a box (graph.hip: radius_graph, which a periodic rollout step calls) and by the periodic scoring
+// kernels (forecast.hip).  One definition: every kernel that tests a pair under a box calls within_pbc below.
 #pragma once
 #include "graph_small.h"
 
@@ -37,26 +37,33 @@ __device__ __forceinline__ bool within_pbc(double xi, double yi, double zi, cons
     return sqrt(s) < cutoff;
 }
 
-// Pair tests as kernel arguments (forecast.hip is templated on one of them): the open test is within() itself
+// Pair tests as kernel arguments (graph.hip's brute-force form and forecast.hip are templated on one of them): the open
+// test is within() itself.  The second call operator also yields sh[a] = the shift that was tested (zeros for the open
+// rule); has_image says whether a source can have an image other than itself.
 struct OpenPair {
+    static constexpr bool has_image = false;
     double cutoff;
     __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj) const {
         return within(xi, yi, zi, pj, cutoff);
     }
+    __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj,
+                                               double sh[3]) const {
+        sh[0] = sh[1] = sh[2] = 0.0;
+        return within(xi, yi, zi, pj, cutoff);
+    }
 };
 struct PbcPair {
+    static constexpr bool has_image = true;
     double cutoff;
     PbcBox box;
     __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj) const {
         double sh[3];
         return within_pbc(xi, yi, zi, pj, cutoff, box, sh);
     }
+    __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj,
+                                               double sh[3]) const {
+        return within_pbc(xi, yi, zi, pj, cutoff, box, sh);
+    }
 };
-
-// Periodic radius graph of frame (frame + *t_dev) of frames f32 [T, M*N, 3]: the arguments of radius_graph (kernels.h)
-// plus the box and edge_attr f32 [edge_cap, 6] (NULL: topology only).  Brute force, one wave per destination row.
-int radius_graph_pbc(const float* frames, int frame, const int* t_dev, int M, int N, double cutoff, const PbcBox& box,
-                     int* row_ptr, int* src, int* dst, float* edge_attr, long long edge_cap, int* num_edges, int* status,
-                     hipStream_t s, int* zero_words = nullptr, int n_zero = 0);
 
 }  // namespace mdno

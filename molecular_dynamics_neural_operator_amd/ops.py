@@ -35,6 +35,13 @@ class CSRGraph:
         return torch.stack([self.dst[:e], self.src[:e]]).to(torch.long)
 
 
+def _empty_csr(R: int, cap: int, dev) -> CSRGraph:
+    """The buffers a radius graph of R rows and at most `cap` edges is built into (count and status zeroed)."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    return CSRGraph(torch.empty(R + 1, **i32), torch.empty(cap, **i32), torch.empty(cap, **i32), torch.zeros(1, **i32),
+                    cap, None, torch.zeros(1, **i32))
+
+
 def radius_graph(pos: torch.Tensor, n_atoms: int, cutoff: float = 8.0, edge_cap: Optional[int] = None,
                  cell_list: bool = True) -> CSRGraph:
     """pos f32 [M*N,3] (or [M,N,3]) -> CSRGraph.  Replaces graph_kernel.py:363-368.  Members of >= 8,192 atoms go
@@ -48,16 +55,13 @@ def radius_graph(pos: torch.Tensor, n_atoms: int, cutoff: float = 8.0, edge_cap:
     cap = int(edge_cap) if edge_cap is not None else M * n_atoms * n_atoms
     cap = max(cap, R)
     dev = pos.device
-    row_ptr = torch.empty(R + 1, dtype=torch.int32, device=dev)
-    src = torch.empty(cap, dtype=torch.int32, device=dev)
-    dst = torch.empty(cap, dtype=torch.int32, device=dev)
-    ne = torch.zeros(1, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    g = _empty_csr(R, cap, dev)
     nbytes = lib.mdno_radius_graph_workspace_bytes(M, n_atoms) if cell_list else 0      # > 0: large members, cell list
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    check(lib.mdno_radius_graph_csr_ws(ptr(pos), M, n_atoms, float(cutoff), ptr(row_ptr), ptr(src), ptr(dst), cap,
-                                       ptr(ne), ptr(status), ptr(ws), nbytes, stream_ptr(dev)), "mdno_radius_graph_csr_ws")
-    return CSRGraph(row_ptr, src, dst, ne, cap, None, status)
+    check(lib.mdno_radius_graph_csr_ws(ptr(pos), M, n_atoms, float(cutoff), ptr(g.row_ptr), ptr(g.src), ptr(g.dst), cap,
+                                       ptr(g.num_edges), ptr(g.status), ptr(ws), nbytes, stream_ptr(dev)),
+          "mdno_radius_graph_csr_ws")
+    return g
 
 
 def check_box(box, cutoff: float, what: str = "box"):
@@ -111,16 +115,12 @@ def radius_graph_pbc(pos: torch.Tensor, n_atoms: int, cutoff: float, box, edge_c
     cap = int(edge_cap) if edge_cap is not None else M * n_atoms * n_atoms
     cap = max(cap, R)
     dev = pos.device
-    row_ptr = torch.empty(R + 1, dtype=torch.int32, device=dev)
-    src = torch.empty(cap, dtype=torch.int32, device=dev)
-    dst = torch.empty(cap, dtype=torch.int32, device=dev)
-    ne = torch.zeros(1, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    g = _empty_csr(R, cap, dev)
     attr = torch.empty((cap, 6), dtype=torch.float32, device=dev) if with_attr else None
     b = box_arg(vals)
-    check(lib.mdno_radius_graph_pbc(ptr(pos), M, n_atoms, float(cutoff), b, ptr(row_ptr), ptr(src), ptr(dst), ptr(attr), cap,
-                                    ptr(ne), ptr(status), stream_ptr(dev)), "mdno_radius_graph_pbc")
-    return CSRGraph(row_ptr, src, dst, ne, cap, None, status), attr
+    check(lib.mdno_radius_graph_pbc(ptr(pos), M, n_atoms, float(cutoff), b, ptr(g.row_ptr), ptr(g.src), ptr(g.dst), ptr(attr),
+                                    cap, ptr(g.num_edges), ptr(g.status), stream_ptr(dev)), "mdno_radius_graph_pbc")
+    return g, attr
 
 
 def coo_to_csr(edge_index: torch.Tensor, num_nodes: int, validate: bool = True,

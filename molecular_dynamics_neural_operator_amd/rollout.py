@@ -60,6 +60,19 @@ def check_rollout_box(model, box, threshold: float):
     return box
 
 
+def probe_edges(last: torch.Tensor, M: int, N: int, threshold: float, box) -> Tuple[int, bool]:
+    """Edges of the radius graph (the periodic one under `box`) of a window's last frame [M,N,3], counted up to the
+    bounds the "auto" and capacity decisions look at; (count, True) when there are more."""
+    R = M * N
+    probe_cap = max(AUTO_FACTORED_MIN_DEGREE * R, M * AUTO_FACTORED_MIN_EDGES) + R
+    last = last.reshape(R, 3)
+    if box is not None:
+        g, _ = ops.radius_graph_pbc(last, N, threshold, box, edge_cap=probe_cap, with_attr=False)
+    else:
+        g = ops.radius_graph(last, N, threshold, edge_cap=probe_cap)
+    return int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
+
+
 class RolloutEngine:
     """Owns the trajectory buffer [W+max_steps, M, N, 3], the workspace and the captured step.
 
@@ -140,18 +153,6 @@ class RolloutEngine:
         return ops.ParamPack({v: p.tensors[k] for k, v in ops.ParamPack.KEYS.items() if k in p.tensors},
                              p.struct.depth, self.device, p.gemm_mode, conv_mode)
 
-    def _probe_edges(self) -> Tuple[int, bool]:
-        """Edges of the radius graph of the window's last frame, counted up to the bounds the decisions below look
-        at; (count, True) when there are more."""
-        R = self.M * self.N
-        probe_cap = max(AUTO_FACTORED_MIN_DEGREE * R, self.M * AUTO_FACTORED_MIN_EDGES) + R
-        last = self.traj[self.W - 1].reshape(R, 3)
-        if self.box is not None:
-            g, _ = ops.radius_graph_pbc(last, self.N, self.threshold, self.box, edge_cap=probe_cap, with_attr=False)
-        else:
-            g = ops.radius_graph(last, self.N, self.threshold, edge_cap=probe_cap)
-        return int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
-
     def _fit_capacity(self, e: int, over: bool) -> bool:
         R = self.M * self.N
         cap = self.M * self.N * self.N if over else min(self.M * self.N * self.N, max(4 * e, e + 16 * R) + R)
@@ -205,14 +206,18 @@ class RolloutEngine:
                 self._member_ids_dev = torch.tensor(self.member_ids, dtype=torch.int32, device=self.device)
             check(self.lib.mdno_rollout_plan_set_noise(self.plan, self.noise_sigma, self.noise_seed,
                                                        ptr(self._member_ids_dev)), "mdno_rollout_plan_set_noise")
-        self._box_attr = None
         if self.box is not None:         # (a rebuilt plan has a new capacity: a new attribute buffer)
-            self._box_attr = torch.empty((self.edge_cap, 6), dtype=torch.float32, device=self.device)
-            self._box_arg = ops.box_arg(self.box)
-            check(self.lib.mdno_rollout_plan_set_box(self.plan, self._box_arg, ptr(self._box_attr)),
-                  "mdno_rollout_plan_set_box")
+            self._attach_box()
+        else:
+            self._box_attr = None
         if self._timer_records:          # the timer lived in the plan just destroyed: its records are gone, the attachment is not
             check(self.lib.mdno_rollout_plan_timer_attach(self.plan, self._timer_records), "timer_attach")
+
+    def _attach_box(self) -> None:
+        """A fresh attribute buffer at the current capacity, and self.box, given to the plan."""
+        self._box_attr = torch.empty((self.edge_cap, 6), dtype=torch.float32, device=self.device)
+        self._box_arg = ops.box_arg(self.box)
+        check(self.lib.mdno_rollout_plan_set_box(self.plan, self._box_arg, ptr(self._box_attr)), "mdno_rollout_plan_set_box")
 
     def set_box(self, box) -> None:
         """Give the engine another periodic cell, or None for the open step (mdno_rollout_plan_set_box: with None the
@@ -224,13 +229,11 @@ class RolloutEngine:
         self.box = box
         if not self.plan:
             return
-        self._box_attr = None
         if box is None:
+            self._box_attr = None
             check(self.lib.mdno_rollout_plan_set_box(self.plan, None, None), "mdno_rollout_plan_set_box")
-            return
-        self._box_attr = torch.empty((self.edge_cap, 6), dtype=torch.float32, device=self.device)
-        self._box_arg = ops.box_arg(box)
-        check(self.lib.mdno_rollout_plan_set_box(self.plan, self._box_arg, ptr(self._box_attr)), "mdno_rollout_plan_set_box")
+        else:
+            self._attach_box()
 
     @property
     def steps_per_launch(self) -> int:
@@ -261,7 +264,7 @@ class RolloutEngine:
         changed = False
         e, over = 0, False
         if self._fit_cap or (self._auto and not _conv_mode):
-            e, over = self._probe_edges()
+            e, over = probe_edges(self.traj[self.W - 1], self.M, self.N, self.threshold, self.box)
         if self._fit_cap:
             changed |= self._fit_capacity(e, over)
         if self._auto:
@@ -501,14 +504,7 @@ class GroupedRolloutEngine:
         want = None
         if any(e._auto for e in self.engines):      # the rule one engine holding every member would apply
             e0 = self.engines[0]
-            R = self.M * self.N
-            probe_cap = max(AUTO_FACTORED_MIN_DEGREE * R, self.M * AUTO_FACTORED_MIN_EDGES) + R
-            last = f32(window[self.W - 1].to(self.device)).reshape(R, 3)
-            if self.box is not None:
-                g, _ = ops.radius_graph_pbc(last, self.N, e0.threshold, self.box, edge_cap=probe_cap, with_attr=False)
-            else:
-                g = ops.radius_graph(last, self.N, e0.threshold, edge_cap=probe_cap)
-            n_e, over = int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
+            n_e, over = probe_edges(f32(window[self.W - 1].to(self.device)), self.M, self.N, e0.threshold, self.box)
             if over:
                 n_e = max(n_e, self.M * max(AUTO_FACTORED_MIN_DEGREE * self.N, AUTO_FACTORED_MIN_EDGES))
             want = {v: k for k, v in _lib.CONV_MODES.items()}[

@@ -193,6 +193,15 @@ PBC_SIGNATURES = {
     "mdno_contact_maps_pbc": (_I, [_P, _L, _I, _D, _P, _P, _P]),
 }
 
+# include/mdno_observe.h (pair-distance histograms and the radius of gyration of frames on the device; additive, no
+# version number of its own): name -> (restype, argtypes), kept in step with that header (tests/test_observe_host.py
+# checks both ways).  `box` is a HOST pointer to three doubles or NULL.
+OBSERVE_SIGNATURES = {
+    "mdno_pair_histogram_workspace_bytes": (_SZ, [_L, _I, _I, _I]),
+    "mdno_pair_histogram": (_I, [_P, _L, _I, _D, _I, _P, _P, _I, _P, _SZ, _P]),
+    "mdno_radius_of_gyration": (_I, [_P, _L, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -224,7 +233,7 @@ def load() -> C.CDLL:
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
-            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()):
+            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

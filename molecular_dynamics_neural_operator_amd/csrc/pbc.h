@@ -37,9 +37,24 @@ __device__ __forceinline__ bool within_pbc(double xi, double yi, double zi, cons
     return sqrt(s) < cutoff;
 }
 
+// the squared distance that within() / within_pbc test, for kernels that need the distance itself (observe.hip): the
+// same differences, the same shifts and the same summation order, so sqrt(dist2) < cutoff IS the pair test
+__device__ __forceinline__ double dist2_open(double xi, double yi, double zi, const float* __restrict__ pj) {
+    const double dx = (double)pj[0] - xi, dy = (double)pj[1] - yi, dz = (double)pj[2] - zi;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+__device__ __forceinline__ double dist2_pbc(double xi, double yi, double zi, const float* __restrict__ pj, const PbcBox& b) {
+    const double xj = pj[0], yj = pj[1], zj = pj[2];
+    const double dx = (xj - xi) - pbc_shift(xi, xj, b.L[0], b.inv[0]);
+    const double dy = (yj - yi) - pbc_shift(yi, yj, b.L[1], b.inv[1]);
+    const double dz = (zj - zi) - pbc_shift(zi, zj, b.L[2], b.inv[2]);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
 // Pair tests as kernel arguments (graph.hip's brute-force form and forecast.hip are templated on one of them): the open
 // test is within() itself.  The second call operator also yields sh[a] = the shift that was tested (zeros for the open
-// rule); has_image says whether a source can have an image other than itself.
+// rule); has_image says whether a source can have an image other than itself; dist2 is the squared distance the test takes
+// the root of.
 struct OpenPair {
     static constexpr bool has_image = false;
     double cutoff;
@@ -50,6 +65,9 @@ struct OpenPair {
                                                double sh[3]) const {
         sh[0] = sh[1] = sh[2] = 0.0;
         return within(xi, yi, zi, pj, cutoff);
+    }
+    __device__ __forceinline__ double dist2(double xi, double yi, double zi, const float* __restrict__ pj) const {
+        return dist2_open(xi, yi, zi, pj);
     }
 };
 struct PbcPair {
@@ -63,6 +81,9 @@ struct PbcPair {
     __device__ __forceinline__ bool operator()(double xi, double yi, double zi, const float* __restrict__ pj,
                                                double sh[3]) const {
         return within_pbc(xi, yi, zi, pj, cutoff, box, sh);
+    }
+    __device__ __forceinline__ double dist2(double xi, double yi, double zi, const float* __restrict__ pj) const {
+        return dist2_pbc(xi, yi, zi, pj, box);
     }
 };
 

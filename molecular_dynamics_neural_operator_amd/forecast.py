@@ -21,15 +21,28 @@ Definitions, per (step s, member m):
 One reference quirk is documented, not copied: the movie compares forecast step i with the STORED contact map of
 `dataset[i + 1]`, which is that window's FIRST frame (dataset.py:189); here the truth is the frame the forecast
 predicts (`DeviceTrajectory.truth_frames`).  The two coincide at window 1.
+
+Distributional scoring.  Past the decorrelation time a forecast and the truth are two different trajectories, and the
+numbers above only say so; what can still be asked is whether the forecast samples the right STRUCTURES.  For that the
+pair distances of every frame are binned on the device (csrc/observe.hip, include/mdno_observe.h has the rule) and the
+per-frame radius of gyration is taken beside them:
+
+    h = eng.pair_histogram(r_max=8.5, n_bins=200).sum((0,))    # PairHistogram: counts i64 [M, 200], summed over the steps
+    t = pair_histogram(truth, 8.5, 200, box=eng.box).sum((0,)) # the truth's, from frames [S, N, 3]
+    h.total_variation(t)                                        # f64 [M]: 0 = the same distribution of distances, 1 = disjoint
+    h.rdf()                                                     # g(r) per member (a box with three periodic axes)
+    eng.radius_of_gyration()                                    # f64 [S, M]
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
+from ._lib import MdnoError
 
 
 @dataclass
@@ -86,6 +99,95 @@ def contact_maps(frames: torch.Tensor, threshold: float = 8.0, box=None) -> torc
     """u8 [..., N, N] for frames [..., N, 3]: the reference's `get_contact_map`, for the movie.  `box`: a periodic cell
     (Lx, Ly, Lz), contacts by the minimum image."""
     return ops.contact_maps(frames, threshold, box)
+
+
+@dataclass
+class PairHistogram:
+    """Histograms of pair distances (ops.pair_histogram): `counts` i64 [..., n_bins] of UNORDERED pairs i < j per bin of
+    width r_max / n_bins over [0, r_max), under `box` (None: open).  `n_frames`: how many frames were summed into every
+    row (1 as computed; `sum` multiplies it).  Every method runs in fp64 on the device of `counts` and reads nothing
+    back."""
+    counts: torch.Tensor
+    r_max: float
+    n_bins: int
+    n_atoms: int
+    box: Optional[Tuple[float, float, float]] = None
+    n_frames: int = 1
+
+    def edges(self) -> torch.Tensor:
+        """Bin edges r_0 = 0 .. r_n = r_max: f64 [n_bins + 1], edge b = b * r_max / n_bins."""
+        k = torch.arange(self.n_bins + 1, dtype=torch.float64, device=self.counts.device)
+        return k * self.r_max / self.n_bins
+
+    def centers(self) -> torch.Tensor:
+        """Bin midpoints: f64 [n_bins]."""
+        e = self.edges()
+        return 0.5 * (e[:-1] + e[1:])
+
+    def sum(self, dims) -> "PairHistogram":
+        """Counts summed over the given LEADING dimensions (steps, members, windows): the histogram of all those frames."""
+        dims = (dims,) if isinstance(dims, int) else tuple(int(d) for d in dims)
+        lead = self.counts.dim() - 1
+        norm = sorted({d + lead if d < 0 else d for d in dims})
+        if len(norm) != len(dims) or any(not 0 <= d < lead for d in norm):
+            raise MdnoError(f"PairHistogram.sum: dims {dims} are not distinct leading dimensions of counts "
+                            f"{tuple(self.counts.shape)}")
+        frames = self.n_frames
+        for d in norm:
+            frames *= self.counts.shape[d]
+        counts = self.counts.sum(norm) if norm else self.counts
+        return PairHistogram(counts, self.r_max, self.n_bins, self.n_atoms, self.box, frames)
+
+    def distribution(self) -> torch.Tensor:
+        """counts / their total per row: f64 [..., n_bins], the distribution p(r) of the pair distances below r_max;
+        NaN where the total is 0."""
+        c = self.counts.to(torch.float64)
+        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+
+    def rdf(self) -> torch.Tensor:
+        """The radial distribution function g(r) per bin: f64 [..., n_bins], counts over what an ideal gas of the same
+        density would put into the bin's shell, n_frames * N (N - 1) / 2 * (4 pi / 3) (r_{b+1}^3 - r_b^3) / (Lx Ly Lz).
+        Defined for a box with three periodic axes only (r_max <= L / 2 holds by construction, so a shell never meets
+        its own image); an open or slab box has no density to normalise by: use `distribution()`."""
+        if self.box is None or not all(L > 0.0 for L in self.box):
+            raise MdnoError(f"rdf: box={self.box} is not periodic in all three axes, so there is no bulk density to "
+                            f"normalise by; use distribution() for an open or slab system")
+        e = self.edges()
+        shell = (4.0 * math.pi / 3.0) * (e[1:] ** 3 - e[:-1] ** 3)
+        pairs = self.n_frames * (self.n_atoms * (self.n_atoms - 1) / 2.0)
+        ideal = shell * (pairs / (self.box[0] * self.box[1] * self.box[2]))
+        return self.counts.to(torch.float64) / ideal
+
+    def total_variation(self, other: "PairHistogram") -> torch.Tensor:
+        """0.5 * sum_b |p_b - q_b| of the two `distribution()`s (leading shapes broadcast): 0 for equal distributions,
+        1 for disjoint ones.  Both histograms must have the same r_max and n_bins."""
+        if not isinstance(other, PairHistogram) or other.r_max != self.r_max or other.n_bins != self.n_bins:
+            raise MdnoError("total_variation: the two histograms must have the same r_max and n_bins")
+        return 0.5 * (self.distribution() - other.distribution()).abs().sum(-1)
+
+    def cpu(self) -> "PairHistogram":
+        return PairHistogram(self.counts.cpu(), self.r_max, self.n_bins, self.n_atoms, self.box, self.n_frames)
+
+    @staticmethod
+    def cat(parts: Sequence["PairHistogram"], dim: int = 1) -> "PairHistogram":
+        """Histograms of disjoint member ranges of the same steps, members in order."""
+        p = parts[0]
+        return PairHistogram(torch.cat([q.counts for q in parts], dim), p.r_max, p.n_bins, p.n_atoms, p.box, p.n_frames)
+
+
+def pair_histogram(frames: torch.Tensor, r_max: float, n_bins: int = 200, box=None, form: str = "auto") -> PairHistogram:
+    """frames f32 [..., N, 3] (device) -> `PairHistogram` with counts i64 [..., n_bins], one row per frame (sum over steps
+    or members with `.sum`).  `box` = (Lx, Ly, Lz), 0 for an open axis: distances by the minimum image
+    (include/mdno_observe.h); every periodic axis must be >= 2 * r_max.  Asynchronous on the current stream; CPU tensors
+    and bad arguments raise `MdnoError` before any device work."""
+    r_max, n_bins, box = ops.check_histogram_args(r_max, n_bins, box)
+    counts = ops.pair_histogram(frames, r_max, n_bins, box, form)
+    return PairHistogram(counts, r_max, n_bins, int(frames.shape[-2]), box)
+
+
+def radius_of_gyration(frames: torch.Tensor) -> torch.Tensor:
+    """f64 [...] for frames f32 [..., N, 3] (device): sqrt(mean_i |x_i - centroid|^2), NaN for a non-finite frame."""
+    return ops.radius_of_gyration(frames)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

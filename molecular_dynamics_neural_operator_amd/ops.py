@@ -1322,3 +1322,65 @@ def contact_maps(frames: torch.Tensor, cutoff: float = 8.0, box=None) -> torch.T
         check(lib.mdno_contact_maps_pbc(None if empty else ptr(frames), F, N, float(cutoff), box_arg(box),
                                         None if empty else ptr(maps), stream_ptr(frames.device)), "mdno_contact_maps_pbc")
     return maps
+
+
+# ------------------------------------------------------------------------------------------------
+# Structural observables (include/mdno_observe.h, csrc/observe.hip)
+MAX_HISTOGRAM_BINS = 4096
+
+
+def check_histogram_args(r_max, n_bins, box=None):
+    """(r_max as float, n_bins as int, box as check_box returns it) for a pair histogram, or MdnoError: r_max finite and
+    > 0, n_bins in 1 .. 4096, every periodic axis of the box >= 2 * r_max (include/mdno_observe.h).  Host only."""
+    import math
+    try:
+        r, nb = float(r_max), int(n_bins)
+    except (TypeError, ValueError):
+        raise MdnoError(f"pair_histogram: r_max={r_max!r}, n_bins={n_bins!r}: expected a number and an integer") from None
+    if not (math.isfinite(r) and r > 0.0):
+        raise MdnoError(f"pair_histogram: r_max {r} is not a finite positive number")
+    if nb != n_bins or not 1 <= nb <= MAX_HISTOGRAM_BINS:
+        raise MdnoError(f"pair_histogram: n_bins={n_bins!r} is outside 1 .. {MAX_HISTOGRAM_BINS}")
+    return r, nb, check_box(box, r)
+
+
+def _flat_frames(frames):
+    """(frames as contiguous f32 [..., N, 3] on the device, its leading shape, F, N), or MdnoError."""
+    frames = _device_frames(frames, "frames", tuple(range(2, 9)))
+    lead = tuple(frames.shape[:-2])
+    F = 1
+    for d in lead:
+        F *= d
+    return frames, lead, F, frames.shape[-2]
+
+
+def pair_histogram(frames: torch.Tensor, r_max: float, n_bins: int, box=None, form: str = "auto") -> torch.Tensor:
+    """frames f32 [..., N, 3] -> i64 [..., n_bins]: per frame, the number of unordered pairs i < j whose distance lies
+    in bin b of [0, r_max) (include/mdno_observe.h has the rule; mdno_pair_histogram).  `box` = (Lx, Ly, Lz), 0 for an
+    open axis: distances by the minimum image, every periodic axis >= 2 * r_max.  Asynchronous on the current stream,
+    nothing is read back.  `form`: "auto" (one workgroup per frame up to 2,048 atoms, pair tiles above), "lds" or
+    "tiled" to force one (the same counts)."""
+    r_max, n_bins, box = check_histogram_args(r_max, n_bins, box)
+    if form not in FORECAST_FORMS:
+        raise MdnoError(f"form {form!r}: expected one of {sorted(FORECAST_FORMS)}")
+    frames, lead, F, N = _flat_frames(frames)
+    lib = _lib.load()
+    dev = frames.device
+    counts = torch.empty(lead + (n_bins,), dtype=torch.int64, device=dev)
+    nbytes = lib.mdno_pair_histogram_workspace_bytes(F, N, n_bins, FORECAST_FORMS[form])
+    ws = _ws(nbytes, dev) if nbytes else None
+    check(lib.mdno_pair_histogram(ptr(frames) if F * N else None, F, N, r_max, n_bins, box_arg(box) if box else None,
+                                  ptr(counts) if F else None, FORECAST_FORMS[form], ptr(ws), nbytes, stream_ptr(dev)),
+          "mdno_pair_histogram")
+    return counts
+
+
+def radius_of_gyration(frames: torch.Tensor) -> torch.Tensor:
+    """frames f32 [..., N, 3] -> f64 [...]: sqrt(mean_i |x_i - centroid|^2) per frame, two fixed-order fp64 passes
+    (mdno_radius_of_gyration); NaN for a frame with a non-finite coordinate or without atoms."""
+    frames, lead, F, N = _flat_frames(frames)
+    lib = _lib.load()
+    rg = torch.empty(lead, dtype=torch.float64, device=frames.device)
+    check(lib.mdno_radius_of_gyration(ptr(frames) if F * N else None, F, N, ptr(rg) if F else None,
+                                      stream_ptr(frames.device)), "mdno_radius_of_gyration")
+    return rg

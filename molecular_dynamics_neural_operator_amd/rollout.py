@@ -425,6 +425,23 @@ class RolloutEngine:
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return score_forecast(self.produced(first_step, steps), truth, threshold, box=box)
 
+    def _observed(self, first_step: int, steps: Optional[int]) -> torch.Tensor:
+        first_step, steps = self._score_range(first_step, steps)
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return self.produced(first_step, steps)
+
+    def pair_histogram(self, r_max: float, n_bins: int = 200, first_step: int = 0, steps: Optional[int] = None):
+        """Pair-distance histograms of the produced frames of steps first_step .. first_step + steps - 1 (default: all)
+        in the engine's own box -> `forecast.PairHistogram`, counts i64 [steps, M, n_bins]; the frames are read where
+        they are, on the current stream after the engine's enqueued steps (as `score`)."""
+        from .forecast import pair_histogram
+        ops.check_histogram_args(r_max, n_bins, self.box)
+        return pair_histogram(self._observed(first_step, steps), r_max, n_bins, box=self.box)
+
+    def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
+        """Radius of gyration of the produced frames (same range arguments as `score`): f64 [steps, M]."""
+        return ops.radius_of_gyration(self._observed(first_step, steps))
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -562,6 +579,15 @@ class GroupedRolloutEngine:
         per_member = torch.is_tensor(truth) and truth.dim() == 4
         return ForecastScore.cat([e.score(truth[:, lo:hi].contiguous() if per_member else truth, first_step, steps, threshold, box)
                                   for e, (lo, hi) in zip(self.engines, self.bounds)])
+
+    def pair_histogram(self, r_max: float, n_bins: int = 200, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.pair_histogram` for every group on its own frames, members in order."""
+        from .forecast import PairHistogram
+        return PairHistogram.cat([e.pair_histogram(r_max, n_bins, first_step, steps) for e in self.engines])
+
+    def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
+        """`RolloutEngine.radius_of_gyration` for every group, members in order: f64 [steps, M]."""
+        return torch.cat([e.radius_of_gyration(first_step, steps) for e in self.engines], dim=1)
 
     @property
     def edges_per_step(self) -> torch.Tensor:

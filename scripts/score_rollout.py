@@ -1,9 +1,12 @@
 """Roll an ensemble out and score it on the device: 64 members of a 504-atom box start from perturbed copies of the first
 window of a synthetic Ornstein-Uhlenbeck trajectory (synthetic.ou_trajectory) and are scored, step by step, against the
 frames of that trajectory they forecast (forecast.py).  Prints ONE JSON line: per-step ensemble means, the first
-non-finite step per member, and the cost of the scoring call (HIP events) beside the time the rollout took.
+non-finite step per member, and the cost of the scoring call (HIP events) beside the time the rollout took.  With
+`--rdf R_MAX N_BINS` also the distributional score (forecast.PairHistogram): per member the total-variation distance
+between the forecast's and the truth's pair-distance distributions summed over the steps, and the radius of gyration at
+the first and the last step.
 
-    python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5]
+    python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
 """
 import argparse
 import json
@@ -27,6 +30,8 @@ def main() -> None:
     ap.add_argument("--kernel-width", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=5, help="timed repetitions of the scoring call (after one warm-up)")
     ap.add_argument("--every", type=int, default=50, help="print every n-th step of the per-step series")
+    ap.add_argument("--rdf", nargs=2, metavar=("R_MAX", "N_BINS"), default=None,
+                    help="also score the distribution of pair distances below R_MAX in N_BINS bins, and the radius of gyration")
     a = ap.parse_args()
 
     from molecular_dynamics_neural_operator_amd import synthetic as syn
@@ -69,6 +74,21 @@ def main() -> None:
     def series(x):
         return [None if not np.isfinite(v) else float(v) for v in x[::a.every].tolist()]
 
+    def finite(x):
+        return [None if not np.isfinite(v) else float(v) for v in x.tolist()]
+
+    dist = {}
+    if a.rdf is not None and S > 0:
+        from molecular_dynamics_neural_operator_amd.forecast import pair_histogram, radius_of_gyration
+        r_max, n_bins = float(a.rdf[0]), int(a.rdf[1])
+        fh = eng.pair_histogram(r_max, n_bins).sum((0,))                             # counts [M, n_bins] over the steps
+        th = pair_histogram(truth, r_max, n_bins, box=eng.box).sum((0,))             # counts [n_bins]
+        rg, rg_truth = eng.radius_of_gyration(), radius_of_gyration(truth)
+        dist = {"rdf_r_max": r_max, "rdf_bins": n_bins,
+                "pair_distance_total_variation": finite(fh.total_variation(th).cpu()),
+                "rg_first_step": finite(rg[0].cpu()), "rg_last_step": finite(rg[-1].cpu()),
+                "rg_truth_first_last": finite(rg_truth[[0, -1]].cpu())}
+
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,
         "first_nonfinite_step": c.first_nonfinite.tolist(),
@@ -79,7 +99,7 @@ def main() -> None:
         "score_ms": best, "score_ms_all": ms, "score_us_per_member_step": best * 1e3 / max(S * M, 1),
         "produce_s": produce_s, "produce_ms_per_member_step": produce_s * 1e3 / max(S * M, 1),
         "score_over_produce": best * 1e-3 / produce_s,
-        "pair_tests": pair_tests, "pair_tests_per_s": pair_tests / (best * 1e-3),
+        "pair_tests": pair_tests, "pair_tests_per_s": pair_tests / (best * 1e-3), **dist,
     }))
     eng.close()
 

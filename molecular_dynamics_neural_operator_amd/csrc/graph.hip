@@ -129,8 +129,9 @@ __global__ __launch_bounds__(1024) void scan_rows_kernel(const int* __restrict__
 // neighbouring cells (the cell edge is the cutoff times 1 + 1e-6, so rounding in the cell index cannot separate them),
 // so the result is the same set of edges.  ORDER: hits are recorded as bits of an atom mask kept in LDS (one wave per
 // destination, 65,536 atoms per pass over the mask) and read back in ascending order — the sources of a row come out
-// sorted whatever order the cells delivered them in, and the graph is bit-identical to the brute-force one (tested on
-// the whole 50k-atom box).
+// sorted whatever order the cells delivered them in, and the graph is bit-identical to the brute-force one.  Tested
+// against a sparse fp64 restatement of the pair rule (tests/graph_ref.py) up to one member of 65,728 atoms — two passes
+// over the mask, rows with sources in both — and against the brute-force form on the whole 50k-atom box.
 constexpr int kCellMinAtoms = 8192;
 constexpr int kCellMax = 32768;          // cells per member (<= 32 per axis)
 constexpr int kMaskBits = 65536;         // atoms per pass over a wave's LDS mask (8 KiB)

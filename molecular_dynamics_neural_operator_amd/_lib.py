@@ -202,6 +202,18 @@ OBSERVE_SIGNATURES = {
     "mdno_radius_of_gyration": (_I, [_P, _L, _I, _P, _P]),
 }
 
+# include/mdno_dynamics.h (displacement statistics, velocity autocorrelation and unwrapping of a trajectory on the
+# device; additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
+# (tests/test_dynamics_host.py checks both ways).  `lags` is a HOST pointer to n_lags int32, `box` a HOST pointer to three
+# doubles.
+DYNAMICS_SIGNATURES = {
+    "mdno_displacement_stats_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "mdno_displacement_stats": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _D, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mdno_velocity_autocorrelation_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "mdno_velocity_autocorrelation": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "mdno_unwrap_frames": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -233,7 +245,8 @@ def load() -> C.CDLL:
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
-            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()):
+            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
+            list(DYNAMICS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -32,6 +32,18 @@ per-frame radius of gyration is taken beside them:
     h.total_variation(t)                                        # f64 [M]: 0 = the same distribution of distances, 1 = disjoint
     h.rdf()                                                     # g(r) per member (a box with three periodic axes)
     eng.radius_of_gyration()                                    # f64 [S, M]
+
+Dynamical scoring.  A forecast can sample the right structures and still freeze, or heat up: whether it has the right
+DYNAMICS is asked of the displacements over a time lag, averaged over all time origins (csrc/dynamics.hip,
+include/mdno_dynamics.h has the rule):
+
+    d = eng.displacement_stats(r_max=4.0, n_bins=64)            # DisplacementStats over ~33 log-spaced lags
+    t = displacement_stats(truth, d.lags.tolist(), r_max=4.0, n_bins=64)
+    d.msd(), d.non_gaussian()                                   # f64 [M, L]: MSD(tau) and alpha_2(tau)
+    d.total_variation(t)                                        # f64 [M, L]: the self van Hove functions compared per lag
+    d.diffusion_coefficient(dt)                                 # f64 [M]: slope of MSD / 6
+    c, lags = eng.velocity_autocorrelation()                    # f64 [M, L]: <v(t) . v(t + tau)>, finite differences
+    unwrap(frames, box)                                         # for truth data that arrives wrapped into its cell
 """
 from __future__ import annotations
 
@@ -188,6 +200,148 @@ def pair_histogram(frames: torch.Tensor, r_max: float, n_bins: int = 200, box=No
 def radius_of_gyration(frames: torch.Tensor) -> torch.Tensor:
     """f64 [...] for frames f32 [..., N, 3] (device): sqrt(mean_i |x_i - centroid|^2), NaN for a non-finite frame."""
     return ops.radius_of_gyration(frames)
+
+
+@dataclass
+class DisplacementStats:
+    """Displacement statistics per member and lag (ops.displacement_stats): `sum2`, `sum4` f64 [M, L], the sums of
+    |x_i(t + lag) - x_i(t)|^2 and of its square over origins and atoms; `counts` i64 [M, L, n_bins] (None without a
+    histogram) of the displacements per bin of width r_max / n_bins over [0, r_max); `lags` i64 [L]; `n_samples` i64 [L],
+    origins times atoms of every lag.  Every method runs in fp64 on the device of the sums and reads nothing back."""
+    sum2: torch.Tensor
+    sum4: torch.Tensor
+    counts: Optional[torch.Tensor]
+    lags: torch.Tensor
+    n_samples: torch.Tensor
+    r_max: Optional[float] = None
+    n_bins: int = 0
+
+    def _n(self) -> torch.Tensor:
+        return self.n_samples.to(torch.float64).expand_as(self.sum2)
+
+    def msd(self) -> torch.Tensor:
+        """Mean squared displacement <r^2>(lag): f64 [M, L]; NaN for a lag without samples."""
+        return ForecastScore._ratio(self.sum2, self._n())
+
+    def non_gaussian(self) -> torch.Tensor:
+        """alpha_2(lag) = 3 <r^4> / (5 <r^2>^2) - 1: f64 [M, L], 0 for Gaussian displacements in three dimensions; NaN
+        where <r^2> is 0 (lag 0) or there is no sample."""
+        r2 = self.msd()
+        r4 = ForecastScore._ratio(self.sum4, self._n())
+        return 3.0 * r4 / (5.0 * r2 * r2) - 1.0
+
+    def _need_counts(self, what: str) -> torch.Tensor:
+        if self.counts is None or self.n_bins <= 0 or self.r_max is None:
+            raise MdnoError(f"{what}: no histogram was taken (n_bins=0); pass r_max and n_bins to displacement_stats")
+        return self.counts.to(torch.float64)
+
+    def edges(self) -> torch.Tensor:
+        """Bin edges 0 .. r_max: f64 [n_bins + 1]."""
+        self._need_counts("edges")
+        k = torch.arange(self.n_bins + 1, dtype=torch.float64, device=self.sum2.device)
+        return k * self.r_max / self.n_bins
+
+    def van_hove(self) -> torch.Tensor:
+        """The self part of the van Hove function as a density in r: counts / (n_samples * dr), f64 [M, L, n_bins]; its
+        integral over [0, r_max) is the fraction of the displacements below r_max."""
+        c = self._need_counts("van_hove")
+        den = (self.n_samples.to(torch.float64)[None, :, None] * (self.r_max / self.n_bins)).expand_as(c)
+        return torch.where(den == 0, torch.full_like(c, float("nan")), c / den)
+
+    def distribution(self) -> torch.Tensor:
+        """counts / their total per (member, lag): f64 [M, L, n_bins]; NaN where the total is 0."""
+        c = self._need_counts("distribution")
+        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+
+    def total_variation(self, other: "DisplacementStats") -> torch.Tensor:
+        """0.5 * sum_b |p_b - q_b| of the two `distribution()`s per lag: f64 [M, L] (members broadcast, so a truth with
+        M = 1 serves every member); 0 for equal distributions, 1 for disjoint ones.  Both must have the same lags, r_max
+        and n_bins."""
+        if not isinstance(other, DisplacementStats) or other.r_max != self.r_max or other.n_bins != self.n_bins or \
+                tuple(other.lags.shape) != tuple(self.lags.shape):
+            raise MdnoError("total_variation: the two statistics must have the same lags, r_max and n_bins")
+        return 0.5 * (self.distribution() - other.distribution()).abs().sum(-1)
+
+    def diffusion_coefficient(self, dt: float = 1.0, first: int = 0, last: Optional[int] = None) -> torch.Tensor:
+        """The least-squares slope (with intercept) of MSD over lags * dt, divided by 6: f64 [M].  `first`, `last`: the
+        slice lags[first:last] that is fitted (leave the ballistic short lags out); needs two distinct lags."""
+        x = self.lags[first:last].to(torch.float64) * float(dt)
+        y = self.msd()[:, first:last]
+        if x.numel() < 2:
+            raise MdnoError(f"diffusion_coefficient: lags[{first}:{last}] holds {x.numel()} lag(s), a slope needs two")
+        xc = x - x.mean()
+        return (xc * (y - y.mean(1, keepdim=True))).sum(1) / (xc * xc).sum() / 6.0
+
+    def cpu(self) -> "DisplacementStats":
+        return DisplacementStats(self.sum2.cpu(), self.sum4.cpu(), None if self.counts is None else self.counts.cpu(),
+                                 self.lags.cpu(), self.n_samples.cpu(), self.r_max, self.n_bins)
+
+    @staticmethod
+    def cat(parts: Sequence["DisplacementStats"]) -> "DisplacementStats":
+        """Statistics of disjoint member ranges of the same steps and lags, members in order."""
+        p = parts[0]
+        counts = None if p.counts is None else torch.cat([q.counts for q in parts], 0)
+        return DisplacementStats(torch.cat([q.sum2 for q in parts], 0), torch.cat([q.sum4 for q in parts], 0), counts,
+                                 p.lags, p.n_samples, p.r_max, p.n_bins)
+
+
+def default_lags(S: int, span: int = 0):
+    """0 and about 32 log-spaced distinct integers from 1 up to (S - 1 - span) // 2 (half the trajectory: every lag keeps
+    at least as many origins as it is long), ascending; [0] for a trajectory too short for a lag."""
+    top = (int(S) - 1 - span) // 2
+    if top < 1:
+        return [0]
+    lags = {0, top}
+    for k in range(32):
+        lags.add(int(round(top ** (k / 31.0))))
+    return sorted(lags)
+
+
+def _lag_tensors(lags, S: int, N: int, stride: int, span: int, device):
+    n = [ops.n_origins(S, tau, stride, span) * N for tau in lags]
+    return (torch.tensor(lags, dtype=torch.int64, device=device), torch.tensor(n, dtype=torch.int64, device=device))
+
+
+def displacement_stats(frames: torch.Tensor, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None,
+                       n_bins: int = 0) -> DisplacementStats:
+    """frames f32 [S, M, N, 3] (device; [S, N, 3] is M = 1) -> `DisplacementStats` over `lags` (default: `default_lags`),
+    every lag averaged over the origins t = 0, origin_stride, ... (include/mdno_dynamics.h).  `remove_com`: the centroid's
+    motion is subtracted.  `r_max`, `n_bins` > 0: also the histogram of the displacements (the self van Hove function).
+    Asynchronous on the current stream; CPU tensors and bad arguments raise `MdnoError` before any device work."""
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
+        ops._trajectory(frames)           # raises with the shape message
+    S, N = int(frames.shape[0]), int(frames.shape[-2])
+    lags = default_lags(S) if lags is None else ops.check_lags(lags, max(S, 1))
+    stride = ops.check_origin_stride(origin_stride)
+    sum2, sum4, counts = ops.displacement_stats(frames, lags, stride, remove_com, r_max, n_bins)
+    lt, nt = _lag_tensors(lags, S, N, stride, 0, sum2.device)
+    return DisplacementStats(sum2, sum4, counts, lt, nt, float(r_max) if counts is not None else None, int(n_bins))
+
+
+def velocity_autocorrelation(frames: torch.Tensor, lags=None, origin_stride: int = 1, remove_com: bool = False,
+                             normalized: bool = False):
+    """frames f32 [S, M, N, 3] (device) -> (C f64 [M, L], lags i64 [L]): C(lag) = the mean over origins and atoms of
+    v_i(t) . v_i(t + lag), v(t) = x(t + 1) - x(t) (divide by dt^2 for physical units).  `normalized`: C(lag) / C(0), which
+    needs lag 0 among the lags (the default set has it).  Lags in 0 .. S - 2."""
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
+        ops._trajectory(frames)
+    S, N = int(frames.shape[0]), int(frames.shape[-2])
+    lags = default_lags(S, 1) if lags is None else ops.check_lags(lags, max(S, 2), 1, "velocity_autocorrelation")
+    stride = ops.check_origin_stride(origin_stride, "velocity_autocorrelation")
+    corr = ops.velocity_autocorrelation(frames, lags, stride, remove_com)
+    lt, nt = _lag_tensors(lags, S, N, stride, 1, corr.device)
+    c = ForecastScore._ratio(corr, nt.to(torch.float64).expand_as(corr))
+    if normalized:
+        if 0 not in lags:
+            raise MdnoError("velocity_autocorrelation: normalized=True needs lag 0 among the lags")
+        c = c / c[:, lags.index(0)][:, None]
+    return c, lt
+
+
+def unwrap(frames: torch.Tensor, box) -> torch.Tensor:
+    """Frames wrapped into the periodic cell `box` = (Lx, Ly, Lz), 0 for an open axis -> the unwrapped trajectory
+    (ops.unwrap_frames), so that displacements mean something for data that arrives wrapped."""
+    return ops.unwrap_frames(frames, box)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -1384,3 +1384,142 @@ def radius_of_gyration(frames: torch.Tensor) -> torch.Tensor:
     check(lib.mdno_radius_of_gyration(ptr(frames) if F * N else None, F, N, ptr(rg) if F else None,
                                       stream_ptr(frames.device)), "mdno_radius_of_gyration")
     return rg
+
+
+# ------------------------------------------------------------------------------------------------
+# Time-correlation statistics (include/mdno_dynamics.h, csrc/dynamics.hip)
+DYNAMICS_ORIGIN_CHUNK = 64          # MDNO_DYN_ORIGIN_CHUNK: origins per workgroup (fixes the order of the sums)
+DYNAMICS_ATOM_TILE = 256            # MDNO_DYN_ATOM_TILE
+MAX_LAGS = 1024
+
+
+def _trajectory(frames, what: str = "frames"):
+    """(frames as contiguous f32 [S, M, N, 3] on the device, S, M, N); [S, N, 3] is M = 1.  MdnoError otherwise."""
+    frames = _device_frames(frames, what, (3, 4))
+    if frames.dim() == 3:
+        frames = frames[:, None]
+    S, M, N = frames.shape[:3]
+    if max(S, M, N) >= 2 ** 31:
+        raise MdnoError(f"{what} has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
+    return frames, S, M, N
+
+
+def check_lags(lags, S: int, span: int = 0, what: str = "displacement_stats"):
+    """`lags` as a list of Python ints: 1 .. 1024 integers in 0 .. S - 1 - span (include/mdno_dynamics.h), or MdnoError.
+    Host only."""
+    if torch.is_tensor(lags):
+        lags = lags.detach().cpu().reshape(-1).tolist()
+    try:
+        lags = list(lags)
+        vals = [int(v) for v in lags]
+        same = all(v == w for v, w in zip(vals, lags))
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
+    if not same:
+        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
+    if not 1 <= len(vals) <= MAX_LAGS:
+        raise MdnoError(f"{what}: {len(vals)} lags, expected 1 .. {MAX_LAGS}")
+    for v in vals:
+        if not 0 <= v <= S - 1 - span:
+            raise MdnoError(f"{what}: lag {v} is outside 0 .. {S - 1 - span} (S={S})")
+    return vals
+
+
+def check_origin_stride(origin_stride, what: str = "displacement_stats") -> int:
+    try:
+        st = int(origin_stride)
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}: origin_stride={origin_stride!r}: expected an integer >= 1") from None
+    if st != origin_stride or not 1 <= st < 2 ** 31:
+        raise MdnoError(f"{what}: origin_stride={origin_stride!r}: expected an integer >= 1")
+    return st
+
+
+def n_origins(S: int, lag: int, origin_stride: int = 1, span: int = 0) -> int:
+    """How many origins t = 0, stride, ... satisfy t + lag + span <= S - 1."""
+    last = S - 1 - span - lag
+    return 0 if last < 0 else last // origin_stride + 1
+
+
+def _lag_arg(vals):
+    return (C.c_int32 * len(vals))(*vals)
+
+
+def displacement_stats(frames: torch.Tensor, lags, origin_stride: int = 1, remove_com: bool = False, r_max=None,
+                       n_bins: int = 0):
+    """frames f32 [S, M, N, 3] (or [S, N, 3]: M = 1) -> (sum2 f64 [M, L], sum4 f64 [M, L], counts i64 [M, L, n_bins] or
+    None): per member and lag, the sums of |x_i(t + lag) - x_i(t)|^2 and of its square over all origins t = 0, stride, ...
+    and atoms, and (n_bins > 0) the histogram of the displacements below r_max (include/mdno_dynamics.h has the rule;
+    mdno_displacement_stats).  `remove_com`: the centroid's displacement is subtracted.  Fixed summation order: the same
+    bits on every run.  Asynchronous on the current stream, nothing is read back."""
+    import math
+    frames, S, M, N = _trajectory(frames)
+    stride = check_origin_stride(origin_stride)
+    try:
+        nb = int(n_bins)
+    except (TypeError, ValueError):
+        raise MdnoError(f"displacement_stats: n_bins={n_bins!r}: expected an integer") from None
+    if nb != n_bins or not 0 <= nb <= MAX_HISTOGRAM_BINS:
+        raise MdnoError(f"displacement_stats: n_bins={n_bins!r} is outside 0 .. {MAX_HISTOGRAM_BINS}")
+    r = 0.0
+    if nb > 0:
+        try:
+            r = float(r_max)
+        except (TypeError, ValueError):
+            raise MdnoError(f"displacement_stats: r_max={r_max!r}: expected a number (n_bins={nb})") from None
+        if not (math.isfinite(r) and r > 0.0):
+            raise MdnoError(f"displacement_stats: r_max {r} is not a finite positive number")
+    vals = check_lags(lags, S) if S > 0 else check_lags(lags, 1 << 30)
+    L = len(vals)
+    lib = _lib.load()
+    dev = frames.device
+    sum2 = torch.empty((M, L), dtype=torch.float64, device=dev)
+    sum4 = torch.empty((M, L), dtype=torch.float64, device=dev)
+    counts = torch.empty((M, L, nb), dtype=torch.int64, device=dev) if nb > 0 else None
+    if S == 0 or M == 0:
+        return sum2.zero_(), sum4.zero_(), None if counts is None else counts.zero_()
+    nbytes = lib.mdno_displacement_stats_workspace_bytes(S, M, N, L, nb)
+    ws = _ws(nbytes, dev)
+    check(lib.mdno_displacement_stats(ptr(frames) if N else None, S, M, N, _lag_arg(vals), L, stride, int(bool(remove_com)),
+                                      r, nb, ptr(sum2), ptr(sum4), ptr(counts), ptr(ws), nbytes, stream_ptr(dev)),
+          "mdno_displacement_stats")
+    return sum2, sum4, counts
+
+
+def velocity_autocorrelation(frames: torch.Tensor, lags, origin_stride: int = 1, remove_com: bool = False) -> torch.Tensor:
+    """frames f32 [S, M, N, 3] (or [S, N, 3]) -> corr f64 [M, L]: the sum over origins and atoms of v_i(t) . v_i(t + lag)
+    with the finite-difference velocities v(t) = x(t + 1) - x(t) (mdno_velocity_autocorrelation; lags in 0 .. S - 2).
+    Same fixed order and stream behaviour as `displacement_stats`."""
+    what = "velocity_autocorrelation"
+    frames, S, M, N = _trajectory(frames)
+    stride = check_origin_stride(origin_stride, what)
+    vals = check_lags(lags, S, 1, what) if S > 0 else check_lags(lags, 1 << 30, 1, what)
+    L = len(vals)
+    lib = _lib.load()
+    dev = frames.device
+    corr = torch.empty((M, L), dtype=torch.float64, device=dev)
+    if S == 0 or M == 0:
+        return corr.zero_()
+    nbytes = lib.mdno_velocity_autocorrelation_workspace_bytes(S, M, N, L)
+    ws = _ws(nbytes, dev)
+    check(lib.mdno_velocity_autocorrelation(ptr(frames) if N else None, S, M, N, _lag_arg(vals), L, stride,
+                                            int(bool(remove_com)), ptr(corr), ptr(ws), nbytes, stream_ptr(dev)),
+          "mdno_velocity_autocorrelation")
+    return corr
+
+
+def unwrap_frames(frames: torch.Tensor, box) -> torch.Tensor:
+    """frames f32 [S, M, N, 3] or [S, N, 3] wrapped into the periodic cell `box` = (Lx, Ly, Lz) (0 = open axis) -> the
+    unwrapped trajectory, a new tensor of the same shape: every atom follows the image nearest to where it was one frame
+    before (mdno_unwrap_frames; integer image counts, no accumulated rounding).  A trajectory that never wrapped comes back
+    bit for bit."""
+    if box is None:
+        raise MdnoError("unwrap_frames: box is None: expected three lengths (Lx, Ly, Lz), 0 for an open axis")
+    vals = check_box(box, 0.0) or (0.0, 0.0, 0.0)
+    shape = tuple(frames.shape) if torch.is_tensor(frames) else None
+    frames, S, M, N = _trajectory(frames)
+    out = torch.empty((S, M, N, 3), dtype=torch.float32, device=frames.device)
+    if S * M * N:
+        check(_lib.load().mdno_unwrap_frames(ptr(frames), S, M, N, box_arg(vals), ptr(out), stream_ptr(frames.device)),
+              "mdno_unwrap_frames")
+    return out.reshape(shape)

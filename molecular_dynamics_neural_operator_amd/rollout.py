@@ -442,6 +442,21 @@ class RolloutEngine:
         """Radius of gyration of the produced frames (same range arguments as `score`): f64 [steps, M]."""
         return ops.radius_of_gyration(self._observed(first_step, steps))
 
+    def displacement_stats(self, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None, n_bins: int = 0,
+                           first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.displacement_stats` (MSD, non-Gaussian parameter, self van Hove histogram per member and lag) of the
+        produced frames of steps first_step .. first_step + steps - 1 (default: all), read where they are on the current
+        stream after the engine's enqueued steps (as `score`)."""
+        from .forecast import displacement_stats
+        return displacement_stats(self._observed(first_step, steps), lags, origin_stride, remove_com, r_max, n_bins)
+
+    def velocity_autocorrelation(self, lags=None, origin_stride: int = 1, remove_com: bool = False,
+                                 normalized: bool = False, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.velocity_autocorrelation` of the produced frames (same range arguments as `score`):
+        (C f64 [M, L], lags i64 [L])."""
+        from .forecast import velocity_autocorrelation
+        return velocity_autocorrelation(self._observed(first_step, steps), lags, origin_stride, remove_com, normalized)
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -588,6 +603,20 @@ class GroupedRolloutEngine:
     def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
         """`RolloutEngine.radius_of_gyration` for every group, members in order: f64 [steps, M]."""
         return torch.cat([e.radius_of_gyration(first_step, steps) for e in self.engines], dim=1)
+
+    def displacement_stats(self, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None, n_bins: int = 0,
+                           first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.displacement_stats` for every group on its own frames, members in order."""
+        from .forecast import DisplacementStats
+        return DisplacementStats.cat([e.displacement_stats(lags, origin_stride, remove_com, r_max, n_bins, first_step, steps)
+                                      for e in self.engines])
+
+    def velocity_autocorrelation(self, lags=None, origin_stride: int = 1, remove_com: bool = False,
+                                 normalized: bool = False, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.velocity_autocorrelation` for every group, members in order: (C f64 [M, L], lags)."""
+        parts = [e.velocity_autocorrelation(lags, origin_stride, remove_com, normalized, first_step, steps)
+                 for e in self.engines]
+        return torch.cat([c for c, _ in parts], dim=0), parts[0][1]
 
     @property
     def edges_per_step(self) -> torch.Tensor:

@@ -214,6 +214,16 @@ DYNAMICS_SIGNATURES = {
     "mdno_unwrap_frames": (_I, [_P, _I, _I, _I, _P, _P, _P]),
 }
 
+# include/mdno_ensemble.h (ensemble verification: error of the mean, spread, CRPS sums and the rank histogram per step;
+# additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
+# (tests/test_ensemble_host.py checks both ways).  The names start with mdnoens_, not mdno_: the tests of the seven tables
+# above hold every mdno_ export to THEIR tables (the header says so too).
+ENSEMBLE_FORMS = {"auto": 0, "registers": 1, "lds": 2}
+ENSEMBLE_SIGNATURES = {
+    "mdnoens_score_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "mdnoens_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+}
+
 _lib = None
 
 
@@ -246,7 +256,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
-            list(DYNAMICS_SIGNATURES.items()):
+            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -44,6 +44,15 @@ include/mdno_dynamics.h has the rule):
     d.diffusion_coefficient(dt)                                 # f64 [M]: slope of MSD / 6
     c, lags = eng.velocity_autocorrelation()                    # f64 [M, L]: <v(t) . v(t + tau)>, finite differences
     unwrap(frames, box)                                         # for truth data that arrives wrapped into its cell
+
+Ensemble verification.  Everything above scores each member on its own.  Whether a stochastic ensemble (`noise_sigma`) is
+CALIBRATED — its spread as large as the error of its mean, the truth indistinguishable from one more member — is asked of
+the members together, per step over every atom and component (csrc/ensemble.hip, include/mdno_ensemble.h has the rule):
+
+    e = eng.ensemble_score(truth)                               # EnsembleScore, one row per step
+    e.rmse(), e.spread(), e.spread_skill()                      # f64 [S]: spread-skill 1 = calibrated, < 1 under-dispersed
+    e.crps(), e.crps(fair=True)                                 # f64 [S]
+    e.sum().rank_flatness()                                     # the pooled rank histogram's distance from uniform
 """
 from __future__ import annotations
 
@@ -342,6 +351,92 @@ def unwrap(frames: torch.Tensor, box) -> torch.Tensor:
     """Frames wrapped into the periodic cell `box` = (Lx, Ly, Lz), 0 for an open axis -> the unwrapped trajectory
     (ops.unwrap_frames), so that displacements mean something for data that arrives wrapped."""
     return ops.unwrap_frames(frames, box)
+
+
+@dataclass
+class EnsembleScore:
+    """The verification sums of an ensemble per step (ops.ensemble_score; include/mdno_ensemble.h has the rule): `sums`
+    f64 [S, 4] over the step's samples (atom, component) of the squared error of the ensemble mean, the unbiased ensemble
+    variance, sum_m |x_m - y| and sum_{m<k} |x_m - x_k|; `rank_hist` i64 [S, M + 1], the truth's rank among the sorted
+    members; `n_invalid` i64 [S], samples left out because a value is not finite (their row of `sums` is NaN); `n_ties`
+    i64 [S], samples where a member equals the truth; `members` = M; `samples_per_step` = 3 N; `n_steps`: how many steps
+    were pooled into every row (1 as computed; `sum` raises it).  Every method runs in fp64 on the device of the sums and
+    reads nothing back; a row without samples gives NaN."""
+    sums: torch.Tensor
+    rank_hist: torch.Tensor
+    n_invalid: torch.Tensor
+    n_ties: torch.Tensor
+    members: int
+    samples_per_step: int
+    n_steps: int = 1
+
+    def _mean(self, c: int) -> torch.Tensor:
+        n = torch.full_like(self.sums[:, c], float(self.samples_per_step * self.n_steps))
+        return ForecastScore._ratio(self.sums[:, c], n)
+
+    def rmse(self) -> torch.Tensor:
+        """Root mean squared error of the ensemble mean: f64 [S]."""
+        return self._mean(0).sqrt()
+
+    def spread(self) -> torch.Tensor:
+        """Root of the mean unbiased ensemble variance: f64 [S]; 0 for one member."""
+        return self._mean(1).sqrt()
+
+    def spread_skill(self) -> torch.Tensor:
+        """sqrt((M + 1) / M) * spread / rmse: f64 [S]; 1 for a calibrated ensemble (the truth one more draw from the
+        members' distribution), below 1 under-dispersed, above 1 over-dispersed."""
+        M = self.members
+        return math.sqrt((M + 1) / M) * self.spread() / self.rmse()
+
+    def crps(self, fair: bool = False) -> torch.Tensor:
+        """The continuous ranked probability score of the empirical distribution of the members, averaged over the
+        samples: mean_m |x_m - y| - sum_{m<k} |x_m - x_k| / M^2, f64 [S].  `fair`: M (M - 1) in place of M^2, the
+        estimator whose expectation does not depend on M (NaN for one member)."""
+        M = self.members
+        first = self._mean(2) / M
+        if fair and M < 2:
+            return torch.full_like(first, float("nan"))
+        return first - self._mean(3) / (M * (M - 1) if fair else M * M)
+
+    def rank_histogram(self) -> torch.Tensor:
+        """rank_hist / its total per row (the valid samples): f64 [S, M + 1]; NaN where there is none."""
+        c = self.rank_hist.to(torch.float64)
+        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+
+    def rank_flatness(self) -> torch.Tensor:
+        """Total variation distance of `rank_histogram()` from the uniform 1 / (M + 1): f64 [S], 0 = flat."""
+        return 0.5 * (self.rank_histogram() - 1.0 / (self.members + 1)).abs().sum(-1)
+
+    def sum(self, steps=None) -> "EnsembleScore":
+        """The given steps (an index, slice, list or index tensor; default: all) pooled into ONE row, before any ratio is
+        taken."""
+        pick = (lambda t: t) if steps is None else (lambda t: t[steps].reshape((-1,) + tuple(t.shape[1:])))
+        parts = [pick(t) for t in (self.sums, self.rank_hist, self.n_invalid, self.n_ties)]
+        rows = parts[0].shape[0]
+        return EnsembleScore(*(t.sum(0, keepdim=True) for t in parts), self.members, self.samples_per_step, self.n_steps * rows)
+
+    def cpu(self) -> "EnsembleScore":
+        return EnsembleScore(self.sums.cpu(), self.rank_hist.cpu(), self.n_invalid.cpu(), self.n_ties.cpu(), self.members,
+                             self.samples_per_step, self.n_steps)
+
+    @staticmethod
+    def cat(parts: Sequence["EnsembleScore"]) -> "EnsembleScore":
+        """Scores of consecutive step ranges of the same ensemble, steps in order."""
+        p = parts[0]
+        if any((q.members, q.samples_per_step, q.n_steps) != (p.members, p.samples_per_step, p.n_steps) for q in parts):
+            raise MdnoError("EnsembleScore.cat: the parts must have the same members, samples per step and pooling")
+        return EnsembleScore(torch.cat([q.sums for q in parts], 0), torch.cat([q.rank_hist for q in parts], 0),
+                             torch.cat([q.n_invalid for q in parts], 0), torch.cat([q.n_ties for q in parts], 0), p.members,
+                             p.samples_per_step, p.n_steps)
+
+
+def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto") -> EnsembleScore:
+    """frames f32 [S, M, N, 3] (device), the M members of ONE ensemble, against truth [S, N, 3] -> `EnsembleScore`, one row
+    per step.  The result does not depend on the order of the members (so not on how they were sharded, grouped or
+    gathered), and is the same bits on every run.  Asynchronous on the current stream; CPU tensors and bad arguments raise
+    `MdnoError` before any device work.  `form` forces one of the two kernel forms (ops.ensemble_score)."""
+    sums, rank_hist, n_invalid, n_ties = ops.ensemble_score(frames, truth, form)
+    return EnsembleScore(sums, rank_hist, n_invalid, n_ties, int(frames.shape[1]), 3 * int(frames.shape[2]))
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

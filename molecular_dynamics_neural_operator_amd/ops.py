@@ -1523,3 +1523,51 @@ def unwrap_frames(frames: torch.Tensor, box) -> torch.Tensor:
         check(_lib.load().mdno_unwrap_frames(ptr(frames), S, M, N, box_arg(vals), ptr(out), stream_ptr(frames.device)),
               "mdno_unwrap_frames")
     return out.reshape(shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# Ensemble verification (include/mdno_ensemble.h, csrc/ensemble.hip)
+ENSEMBLE_SAMPLE_TILE = 256          # MDNO_ENS_SAMPLE_TILE: samples per workgroup (fixes the order of the sums)
+MAX_ENSEMBLE_MEMBERS = 1024         # MDNO_ENS_MAX_MEMBERS
+MAX_REGISTER_MEMBERS = 64           # MDNO_ENS_MAX_REGISTER_MEMBERS
+ENSEMBLE_FORMS = _lib.ENSEMBLE_FORMS
+
+
+def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto"):
+    """frames f32 [S, M, N, 3] (the M members of one ensemble) against truth f32 [S, N, 3] -> (sums f64 [S, 4],
+    rank_hist i64 [S, M + 1], n_invalid i64 [S], n_ties i64 [S]): per step, over its 3 N samples (atom, component), the
+    sums of the squared error of the ensemble mean, of the unbiased ensemble variance, of sum_m |x_m - y| and of
+    sum_{m<k} |x_m - x_k|, the histogram of the truth's rank among the sorted members, the samples left out because a
+    value is not finite (their step's sums are NaN) and the samples where a member equals the truth (include/mdno_ensemble.h
+    has the rule; mdnoens_score).  No output depends on the order of the members; fixed summation order: the same bits on
+    every run.  `form`: "auto" (registers up to 64 members, LDS up to 1,024), "registers" or "lds" to force one (the same
+    bits).  Asynchronous on the current stream, nothing is read back."""
+    frames = _device_frames(frames, "frames", (4,))
+    truth = _device_frames(truth, "truth", (3,))
+    if truth.device != frames.device:
+        raise MdnoError(f"truth is on {truth.device}, frames on {frames.device}")
+    S, M, N, _ = frames.shape
+    if tuple(truth.shape) != (S, N, 3):
+        raise MdnoError(f"truth shape {tuple(truth.shape)} does not match frames {tuple(frames.shape)}: expected {(S, N, 3)}")
+    if form not in ENSEMBLE_FORMS:
+        raise MdnoError(f"form {form!r}: expected one of {sorted(ENSEMBLE_FORMS)}")
+    if not 1 <= M <= MAX_ENSEMBLE_MEMBERS:
+        raise MdnoError(f"ensemble_score: {M} members, expected 1 .. {MAX_ENSEMBLE_MEMBERS}")
+    if form == "registers" and M > MAX_REGISTER_MEMBERS:
+        raise MdnoError(f"ensemble_score: form 'registers' holds at most {MAX_REGISTER_MEMBERS} members, got {M}")
+    if max(S, N) >= 2 ** 31:
+        raise MdnoError(f"frames has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
+    lib = _lib.load()
+    dev = frames.device
+    sums = torch.empty((S, 4), dtype=torch.float64, device=dev)
+    rank_hist = torch.empty((S, M + 1), dtype=torch.int64, device=dev)
+    n_invalid = torch.empty((S,), dtype=torch.int64, device=dev)
+    n_ties = torch.empty((S,), dtype=torch.int64, device=dev)
+    if S == 0:
+        return sums, rank_hist, n_invalid, n_ties
+    nbytes = lib.mdnoens_score_workspace_bytes(S, M, N)
+    ws = _ws(nbytes, dev)
+    check(lib.mdnoens_score(ptr(frames) if N else None, ptr(truth) if N else None, S, M, N, ptr(sums), ptr(rank_hist),
+                            ptr(n_invalid), ptr(n_ties), ENSEMBLE_FORMS[form], ptr(ws), nbytes, stream_ptr(dev)),
+          "mdnoens_score")
+    return sums, rank_hist, n_invalid, n_ties

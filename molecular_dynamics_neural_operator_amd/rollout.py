@@ -457,6 +457,14 @@ class RolloutEngine:
         from .forecast import velocity_autocorrelation
         return velocity_autocorrelation(self._observed(first_step, steps), lags, origin_stride, remove_com, normalized)
 
+    def ensemble_score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.ensemble_score` (error of the ensemble mean, spread, CRPS sums and rank histogram per step) of the
+        produced frames of steps first_step .. first_step + steps - 1 (default: all), taken as ONE ensemble of the engine's
+        M members, against truth f32 [steps, N, 3]; the frames are read where they are, on the current stream after the
+        engine's enqueued steps (as `score`)."""
+        from .forecast import ensemble_score
+        return ensemble_score(self._observed(first_step, steps), truth)
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -617,6 +625,14 @@ class GroupedRolloutEngine:
         parts = [e.velocity_autocorrelation(lags, origin_stride, remove_com, normalized, first_step, steps)
                  for e in self.engines]
         return torch.cat([c for c, _ in parts], dim=0), parts[0][1]
+
+    def ensemble_score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.ensemble_score` of ALL groups' members as one ensemble.  Unlike the per-member statistics above this
+        cannot be merged from per-group results — the pair term sum_{m<k} |x_m - x_k| and the ranks run across the
+        groups — so the groups' frames of the asked steps are concatenated along the member axis (one copy) and scored
+        once: the bits of `forecast.ensemble_score(self.produced(first_step, steps), truth)`."""
+        from .forecast import ensemble_score
+        return ensemble_score(torch.cat([e._observed(first_step, steps) for e in self.engines], dim=1), truth)
 
     @property
     def edges_per_step(self) -> torch.Tensor:

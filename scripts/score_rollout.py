@@ -6,10 +6,14 @@ non-finite step per member, and the cost of the scoring call (HIP events) beside
 between the forecast's and the truth's pair-distance distributions summed over the steps, and the radius of gyration at
 the first and the last step.  With `--msd [R_MAX N_BINS]` also the dynamical score (forecast.DisplacementStats): per lag the
 ensemble mean of MSD(tau) and of the non-Gaussian parameter alpha_2(tau) beside the truth's, and (with R_MAX N_BINS) the
-total-variation distance between the forecast's and the truth's displacement distributions per lag.
+total-variation distance between the forecast's and the truth's displacement distributions per lag.  With `--ensemble` also
+the verification of the members AS AN ENSEMBLE (forecast.EnsembleScore): every `--every`-th step the RMSE of the ensemble mean,
+the spread, the spread-skill ratio, the CRPS and the fair CRPS, and the flatness of the rank histogram pooled over the steps
+(INTEGRATION.md "Is the ensemble calibrated?" reads them).  `--noise-sigma` gives the members their per-step kicks; without
+it they differ only by their starting windows.
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
-                                    [--msd 4.0 64]
+                                    [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05]
 """
 import argparse
 import json
@@ -38,6 +42,10 @@ def main() -> None:
     ap.add_argument("--msd", nargs="*", metavar="R_MAX N_BINS", default=None,
                     help="also score the dynamics: MSD and alpha_2 per lag against the truth's; with R_MAX N_BINS the total "
                          "variation of the displacement histograms per lag as well")
+    ap.add_argument("--ensemble", action="store_true",
+                    help="also verify the members as one ensemble: RMSE of the mean, spread, spread-skill, CRPS, rank histogram")
+    ap.add_argument("--noise-sigma", type=float, default=0.0, help="per-step Gaussian kick of every member (0: none)")
+    ap.add_argument("--noise-seed", type=int, default=0)
     a = ap.parse_args()
     if a.msd is not None and len(a.msd) not in (0, 2):
         ap.error("--msd takes no values or R_MAX N_BINS")
@@ -57,7 +65,8 @@ def main() -> None:
     model = KernelNN(64, a.kernel_width, 6, 6, 7, 3, 20, 4)
     model.load_state_dict(near_identity_state_dict(64, a.kernel_width, seed=0, kernel_gain=1e-3, feature_gain=0.1))
     model.eval().to(dev)
-    eng = RolloutEngine(model, M, N, W, a.threshold, max_steps=S, device=dev)
+    eng = RolloutEngine(model, M, N, W, a.threshold, max_steps=S, device=dev, noise_sigma=a.noise_sigma,
+                        noise_seed=a.noise_seed)
     truth = torch.from_numpy(traj[W:]).to(dev)                                       # [S, N, 3]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -109,6 +118,24 @@ def main() -> None:
         if n_bins:
             dist.update({"msd_r_max": r_max, "msd_bins": n_bins,
                          "displacement_total_variation_mean": finite(fd.total_variation(td).nanmean(0).cpu())})
+
+    if a.ensemble and S > 0:
+        es = eng.ensemble_score(truth)                                               # one row per step
+        pooled = es.sum()
+        spread = es.spread().cpu()
+        dist.update({"ensemble_rmse_of_mean": series(es.rmse().cpu()), "ensemble_spread": series(spread),
+                     "ensemble_spread_skill": series(es.spread_skill().cpu()), "ensemble_crps": series(es.crps().cpu()),
+                     "ensemble_crps_fair": series(es.crps(fair=True).cpu()),
+                     "ensemble_spread_skill_pooled": finite(pooled.spread_skill().cpu())[0],
+                     "ensemble_rank_flatness_pooled": finite(pooled.rank_flatness().cpu())[0],
+                     "ensemble_invalid_samples": int(es.n_invalid.sum()), "noise_sigma": a.noise_sigma})
+        if not bool(spread.nan_to_num(1.0).any()):
+            dist["ensemble_note"] = ("spread 0: the members coincide bit for bit (noise_sigma = 0 and one starting window), so "
+                                     "they carry no uncertainty, the spread-skill ratio is 0 and the CRPS is the mean absolute "
+                                     "error; run with --noise-sigma")
+        elif a.noise_sigma == 0.0:
+            dist["ensemble_note"] = ("noise_sigma = 0: the members differ only by their perturbed starting windows, the spread "
+                                     "is what the model keeps of that; run with --noise-sigma for a stochastic ensemble")
 
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,

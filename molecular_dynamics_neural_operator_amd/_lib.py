@@ -224,6 +224,15 @@ ENSEMBLE_SIGNATURES = {
     "mdnoens_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _SZ, _P]),
 }
 
+# include/mdno_conformations.h (structural coverage: the superposed RMSD of every frame against every reference frame, its
+# row and per-member column minima; additive, no version number of its own): name -> (restype, argtypes), kept in step
+# with that header (tests/test_conformations_host.py checks both ways).  The names start with mdnoconf_, for the reason
+# mdnoens_ has (the header says so too).
+CONFORMATIONS_SIGNATURES = {
+    "mdnoconf_cross_rmsd_workspace_bytes": (_SZ, [_I, _I, _I, _L, _I]),
+    "mdnoconf_cross_rmsd": (_I, [_P, _I, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+
 _lib = None
 
 
@@ -256,7 +265,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
-            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()):
+            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -32,6 +32,7 @@
 // in its two atoms bit for bit as well (rint is odd), so the i <= j counting holds for both.
 #include "pbc.h"
 #include "reduce.h"
+#include "superpose.h"
 #include "../../include/mdno_pbc.h"
 
 #include <cmath>
@@ -43,52 +44,6 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kLdsAtoms = 2048;        // 2 frames x 2,048 atoms x 12 B = 48 KiB of LDS
 constexpr int kSumTile = 1024;         // atoms per workgroup in the tiled sums
 constexpr int kPairTile = 256;         // atoms per side of a pair-test tile
-constexpr int kJacobiSweeps = 12;      // a 4 x 4 symmetric matrix is diagonal to fp64 after 5-6 (quadratic convergence)
-
-// rmsd^2 from the cross-covariance s[3*r+c] = sum a_r b_c and G (file header); n = N as a double
-__device__ double rmsd2_from_moments(const double* s, double G, double n) {
-    double a[4][4];
-    a[0][0] = (s[0] + s[4]) + s[8];
-    a[1][1] = (s[0] - s[4]) - s[8];
-    a[2][2] = (s[4] - s[0]) - s[8];
-    a[3][3] = (s[8] - s[0]) - s[4];
-    a[0][1] = a[1][0] = s[5] - s[7];
-    a[0][2] = a[2][0] = s[6] - s[2];
-    a[0][3] = a[3][0] = s[1] - s[3];
-    a[1][2] = a[2][1] = s[1] + s[3];
-    a[1][3] = a[3][1] = s[6] + s[2];
-    a[2][3] = a[3][2] = s[5] + s[7];
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                a[p][p] -= t * apq;
-                a[q][q] += t * apq;
-                a[p][q] = a[q][p] = 0.0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (r == p || r == q) continue;
-                    const double arp = a[r][p], arq = a[r][q];
-                    a[r][p] = a[p][r] = c * arp - sn * arq;
-                    a[r][q] = a[q][r] = sn * arp + c * arq;
-                }
-            }
-        }
-    }
-    double lam = a[0][0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) lam = a[k][k] > lam ? a[k][k] : lam;
-    const double trace = (a[0][0] + a[1][1]) + (a[2][2] + a[3][3]);
-    if (trace != trace) lam = trace;      // a non-finite truth frame: NaN, whatever the comparisons above made of it
-    const double r2 = (G - 2.0 * lam) / n;
-    return r2 < 0.0 ? 0.0 : r2;           // rounding only (a NaN stays a NaN)
-}
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }   // false for NaN and Inf
 

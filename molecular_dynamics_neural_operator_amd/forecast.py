@@ -53,6 +53,14 @@ the members together, per step over every atom and component (csrc/ensemble.hip,
     e.rmse(), e.spread(), e.spread_skill()                      # f64 [S]: spread-skill 1 = calibrated, < 1 under-dispersed
     e.crps(), e.crps(fair=True)                                 # f64 [S]
     e.sum().rank_flatness()                                     # the pooled rank histogram's distance from uniform
+
+Structural coverage.  Past the decorrelation time a free run and the truth are different trajectories and a same-step RMSD
+only says so.  Whether the run visits the RIGHT STRUCTURES is asked of every produced frame against every true frame
+(csrc/conformations.hip on the fp64 matrix pipe, include/mdno_conformations.h has the rule):
+
+    c = eng.cross_rmsd(truth, matrix=False)                     # CrossRmsd: nearest [S, M], cover [M, Fb] and their indices
+    c.precision(2.0), c.coverage(2.0)                           # f64 [M]: frames near some true frame / true frames visited
+    cross_rmsd(frames, folded[None]).to_reference(0)            # f64 [S, M]: the RMSD time series to one structure
 """
 from __future__ import annotations
 
@@ -437,6 +445,64 @@ def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto"
     `MdnoError` before any device work.  `form` forces one of the two kernel forms (ops.ensemble_score)."""
     sums, rank_hist, n_invalid, n_ties = ops.ensemble_score(frames, truth, form)
     return EnsembleScore(sums, rank_hist, n_invalid, n_ties, int(frames.shape[1]), 3 * int(frames.shape[2]))
+
+
+@dataclass
+class CrossRmsd:
+    """Every produced frame against every reference frame (ops.cross_rmsd; include/mdno_conformations.h has the rule):
+    `matrix` f64 [S, M, Fb], the RMSD after the optimal rigid superposition (None when it was not asked for); `nearest` f64
+    [S, M] and `nearest_index` i64 [S, M], the smallest of a frame's row and the lowest reference index that attains it;
+    `cover` f64 [M, Fb] and `cover_step` i64 [M, Fb], per member the smallest of a reference frame's column and the lowest
+    step that attains it.  A frame with a NaN or Inf coordinate is NaN in its row (column) and never chosen; NaN and -1 where
+    nothing valid is left.  Every method runs in fp64 on the device of the fields and reads nothing back."""
+    matrix: Optional[torch.Tensor]
+    nearest: torch.Tensor
+    nearest_index: torch.Tensor
+    cover: torch.Tensor
+    cover_step: torch.Tensor
+
+    def precision(self, radius: float) -> torch.Tensor:
+        """Is every produced frame close to SOME reference frame: per member the share of its valid frames with
+        nearest <= radius, f64 [M]; NaN for a member without a valid frame (or without a valid reference)."""
+        valid = self.nearest_index >= 0
+        return ForecastScore._ratio(((self.nearest <= radius) & valid).sum(0), valid.sum(0))
+
+    def coverage(self, radius: float) -> torch.Tensor:
+        """Is every reference frame visited by the run: per member the share of the valid reference frames with
+        cover <= radius, f64 [M]; NaN for a member without a valid step (or without a valid reference)."""
+        valid = self.cover_step >= 0
+        return ForecastScore._ratio(((self.cover <= radius) & valid).sum(1), valid.sum(1))
+
+    def to_reference(self, j: int) -> torch.Tensor:
+        """Column j of the matrix, f64 [S, M]: the RMSD time series of every member to ONE structure (a folded state)."""
+        if self.matrix is None:
+            raise MdnoError("CrossRmsd.to_reference needs the matrix: ask for it (matrix=True)")
+        return self.matrix[:, :, j]
+
+    def cpu(self) -> "CrossRmsd":
+        return CrossRmsd(None if self.matrix is None else self.matrix.cpu(), self.nearest.cpu(), self.nearest_index.cpu(),
+                         self.cover.cpu(), self.cover_step.cpu())
+
+    @staticmethod
+    def cat(parts: Sequence["CrossRmsd"]) -> "CrossRmsd":
+        """Results of disjoint member ranges of the same steps against the same reference, members in order.  Rows and
+        per-member columns never cross members, so this is the result of scoring all members at once, bit for bit."""
+        if any((q.matrix is None) != (parts[0].matrix is None) for q in parts):
+            raise MdnoError("CrossRmsd.cat: either every part holds the matrix or none does")
+        return CrossRmsd(None if parts[0].matrix is None else torch.cat([q.matrix for q in parts], 1),
+                         torch.cat([q.nearest for q in parts], 1), torch.cat([q.nearest_index for q in parts], 1),
+                         torch.cat([q.cover for q in parts], 0), torch.cat([q.cover_step for q in parts], 0))
+
+
+def cross_rmsd(frames: torch.Tensor, reference: torch.Tensor, matrix: bool = True) -> CrossRmsd:
+    """frames f32 [S, M, N, 3] (device; [F, N, 3] is one member) against reference f32 [Fb, N, 3] -> `CrossRmsd`: the nearest
+    reference frame of every produced frame, the nearest produced frame of every reference frame per member, and with
+    `matrix` the full [S, M, Fb] RMSD map (8 S M Fb bytes: 512 MB for 64 members x 1,000 steps x 1,000 reference frames —
+    pass matrix=False where only precision and coverage are wanted).  `reference` may be `frames` itself (one member): the
+    run's own 2-D RMSD map.  The bits of an element depend on its two frames alone, never on the batch.  No periodic box:
+    a superposition needs whole molecules (ops.cross_rmsd).  Asynchronous on the current stream; CPU tensors and bad
+    arguments raise `MdnoError` before any device work."""
+    return CrossRmsd(*ops.cross_rmsd(frames, reference, matrix=matrix, nearest=True, cover=True))
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -1571,3 +1571,51 @@ def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto"
                             ptr(n_invalid), ptr(n_ties), ENSEMBLE_FORMS[form], ptr(ws), nbytes, stream_ptr(dev)),
           "mdnoens_score")
     return sums, rank_hist, n_invalid, n_ties
+
+
+# ------------------------------------------------------------------------------------------------
+# Structural coverage (include/mdno_conformations.h, csrc/conformations.hip)
+CONF_FRAME_TILE = 32                # MDNO_CONF_FRAME_TILE: frames per side of a workgroup's tile of pairs
+CONF_ATOM_CHUNK = 32                # MDNO_CONF_ATOM_CHUNK: atoms staged per pass (fixes the order of the pair sums)
+
+
+def cross_rmsd(frames: torch.Tensor, reference: torch.Tensor, matrix: bool = True, nearest: bool = True, cover: bool = True):
+    """frames f32 [S, M, N, 3] (or a plain stack [F, N, 3]: M = 1) against reference f32 [Fb, N, 3] -> (matrix f64
+    [S, M, Fb], nearest f64 [S, M], nearest_index i64 [S, M], cover f64 [M, Fb], cover_step i64 [M, Fb]), None for what was
+    not asked for: the RMSD after the optimal rigid superposition of EVERY frame with EVERY reference frame, per frame the
+    smallest of its row and the LOWEST reference index that attains it, per member and reference frame the smallest of the
+    member's column and the lowest step that attains it (include/mdno_conformations.h has the rule; mdnoconf_cross_rmsd).
+    A frame with a NaN or Inf coordinate gives NaN in its row (column) and is never chosen by an index; NaN and -1 where
+    nothing valid is left.  The bits of matrix[s, m, j] depend on the two frames and N alone: fixed summation order, no
+    float atomics, the same on every run and inside any batch.  `frames` and `reference` may be the same tensor (the self
+    matrix, computed in full).  A periodic `box` is not an argument: a superposition under the minimum image needs whole
+    molecules — unwrap first (ops.unwrap_frames) and make them whole.  Asynchronous on the current stream, nothing is read
+    back."""
+    frames, S, M, N = _trajectory(frames)
+    reference = _device_frames(reference, "reference", (3,))
+    if reference.device != frames.device:
+        raise MdnoError(f"reference is on {reference.device}, frames on {frames.device}")
+    Fb = reference.shape[0]
+    if reference.shape[1] != N:
+        raise MdnoError(f"reference shape {tuple(reference.shape)} does not match frames {tuple(frames.shape)}: expected "
+                        f"[Fb, {N}, 3]")
+    if not (matrix or nearest or cover):
+        raise MdnoError("cross_rmsd: no output was asked for (matrix, nearest and cover are all False)")
+    if Fb >= 2 ** 31 * CONF_FRAME_TILE:
+        raise MdnoError(f"reference has shape {tuple(reference.shape)}: too many frames for one launch")
+    lib = _lib.load()
+    dev = frames.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    out_m = torch.empty((S, M, Fb), **f64) if matrix else None
+    out_n, out_ni = (torch.empty((S, M), **f64), torch.empty((S, M), **i64)) if nearest else (None, None)
+    out_c, out_cs = (torch.empty((M, Fb), **f64), torch.empty((M, Fb), **i64)) if cover else (None, None)
+    if not any(t is not None and t.numel() for t in (out_m, out_n, out_c)):
+        return out_m, out_n, out_ni, out_c, out_cs          # every output asked for is empty: nothing to write
+    work = S * M > 0 and Fb > 0
+    nbytes = lib.mdnoconf_cross_rmsd_workspace_bytes(S, M, N, Fb, int(cover)) if work else 0
+    ws = _ws(nbytes, dev) if work else None
+    check(lib.mdnoconf_cross_rmsd(ptr(frames) if work and N else None, S, M, ptr(reference) if work and N else None, Fb, N,
+                                  ptr(out_m), ptr(out_n), ptr(out_ni), ptr(out_c), ptr(out_cs), ptr(ws), nbytes,
+                                  stream_ptr(dev)), "mdnoconf_cross_rmsd")
+    return out_m, out_n, out_ni, out_c, out_cs

@@ -465,6 +465,14 @@ class RolloutEngine:
         from .forecast import ensemble_score
         return ensemble_score(self._observed(first_step, steps), truth)
 
+    def cross_rmsd(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None, matrix: bool = True):
+        """`forecast.cross_rmsd` (superposed RMSD of every produced frame against every reference frame, the nearest
+        reference frame per frame and the nearest produced frame per member and reference frame) of the produced frames of
+        steps first_step .. first_step + steps - 1 (default: all) against reference f32 [Fb, N, 3]; the frames are read where
+        they are, on the current stream after the engine's enqueued steps (as `score`)."""
+        from .forecast import cross_rmsd
+        return cross_rmsd(self._observed(first_step, steps), reference, matrix)
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -633,6 +641,13 @@ class GroupedRolloutEngine:
         once: the bits of `forecast.ensemble_score(self.produced(first_step, steps), truth)`."""
         from .forecast import ensemble_score
         return ensemble_score(torch.cat([e._observed(first_step, steps) for e in self.engines], dim=1), truth)
+
+    def cross_rmsd(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None, matrix: bool = True):
+        """`forecast.cross_rmsd` per group, joined along the member axis: a row and a per-member column never cross members
+        and an element's bits depend on its two frames alone, so unlike `ensemble_score` no copy of the frames is needed
+        and the result is that of all members scored at once."""
+        from .forecast import CrossRmsd
+        return CrossRmsd.cat([e.cross_rmsd(reference, first_step, steps, matrix) for e in self.engines])
 
     @property
     def edges_per_step(self) -> torch.Tensor:

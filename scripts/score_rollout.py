@@ -10,10 +10,13 @@ total-variation distance between the forecast's and the truth's displacement dis
 the verification of the members AS AN ENSEMBLE (forecast.EnsembleScore): every `--every`-th step the RMSE of the ensemble mean,
 the spread, the spread-skill ratio, the CRPS and the fair CRPS, and the flatness of the rank histogram pooled over the steps
 (INTEGRATION.md "Is the ensemble calibrated?" reads them).  `--noise-sigma` gives the members their per-step kicks; without
-it they differ only by their starting windows.
+it they differ only by their starting windows.  With `--coverage RADIUS` also the structural coverage
+(forecast.CrossRmsd): every produced frame against every frame of the truth, per member the precision (the share of its
+frames within RADIUS of some true frame), the coverage (the share of the true frames it comes within RADIUS of) and the
+median nearest-frame RMSD (INTEGRATION.md "Does the run visit the right structures?" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
-                                    [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05]
+                                    [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
 """
 import argparse
 import json
@@ -46,6 +49,9 @@ def main() -> None:
                     help="also verify the members as one ensemble: RMSE of the mean, spread, spread-skill, CRPS, rank histogram")
     ap.add_argument("--noise-sigma", type=float, default=0.0, help="per-step Gaussian kick of every member (0: none)")
     ap.add_argument("--noise-seed", type=int, default=0)
+    ap.add_argument("--coverage", type=float, metavar="RADIUS", default=None,
+                    help="also score the structural coverage: per member the precision, the coverage and the median "
+                         "nearest-frame RMSD against the truth, at this radius")
     a = ap.parse_args()
     if a.msd is not None and len(a.msd) not in (0, 2):
         ap.error("--msd takes no values or R_MAX N_BINS")
@@ -136,6 +142,12 @@ def main() -> None:
         elif a.noise_sigma == 0.0:
             dist["ensemble_note"] = ("noise_sigma = 0: the members differ only by their perturbed starting windows, the spread "
                                      "is what the model keeps of that; run with --noise-sigma for a stochastic ensemble")
+
+    if a.coverage is not None and S > 0:
+        cr = eng.cross_rmsd(truth, matrix=False)                                     # nearest [S, M], cover [M, S]
+        dist.update({"coverage_radius": a.coverage, "coverage_precision": finite(cr.precision(a.coverage).cpu()),
+                     "coverage": finite(cr.coverage(a.coverage).cpu()),
+                     "nearest_true_frame_rmsd_median": finite(cr.nearest.nanmedian(0).values.cpu())})
 
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,

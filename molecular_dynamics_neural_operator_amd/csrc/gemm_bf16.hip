@@ -330,7 +330,15 @@ tile_loop:      // (PERSIST: one pass per tile of this workgroup; otherwise a si
         // it but the epilogue, which waves 0-3 then start while waves 4-7 are still multiplying)
         if (grp == 0 || t + 1 < T) { MDNO_PP_BARRIER() }
     }
-    if (T == 0 && grp == 0) { MDNO_PP_BARRIER() }   // (an empty slice: pair the stagger barrier)
+    // An empty K slice (TN: k0 >= rows; nothing was sent — both prologue DMAs and the loop need T > 0 — and both
+    // descriptors have size 0).  T == 0 (the slice starts 0 .. 31 rows past the end: C division rounds
+    // (k1 - k0 + 31) / 32 toward zero): waves 0-3 pair the stagger barrier of waves 4-7 here, so both groups have
+    // executed two barriers when they reach the epilogue.  T < 0 (it starts 32 or more rows past the end) is NOT
+    // paired: waves 0-3 go on with one barrier fewer, store their zeros and END, and a wave that has ended no longer
+    // counts towards s_barrier — that is what releases waves 4-7 from their stagger barrier.  Nothing is shared
+    // between the groups after it (the epilogue's patches are per wave), so either way the workgroup writes its
+    // 256 x 256 zeros into its slab and every wave terminates.
+    if (T == 0 && grp == 0) { MDNO_PP_BARRIER() }
 
     // ---- PERSIST: this wave's share of the next tile's stages 0 and 1, now (every fragment read of the tile just
     // multiplied completed before the last barrier this wave passed: any slot may be overwritten; slot 2 is left to

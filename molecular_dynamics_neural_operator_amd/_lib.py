@@ -233,6 +233,18 @@ CONFORMATIONS_SIGNATURES = {
     "mdnoconf_cross_rmsd": (_I, [_P, _I, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# include/mdno_essential.h (essential dynamics: superposition onto one reference with the rotated frames handed back,
+# column sums, the feature x feature second-moment matrix at a time lag, projection; additive, no version number of its
+# own): name -> (restype, argtypes), kept in step with that header (tests/test_essential_host.py checks both ways).  The
+# names start with mdnopca_, for the reason mdnoens_ has (the header says so too).
+ESSENTIAL_SIGNATURES = {
+    "mdnopca_superpose": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "mdnopca_feature_sums": (_I, [_P, _L, _I, _P, _P, _P]),
+    "mdnopca_covariance_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "mdnopca_covariance": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
+    "mdnopca_project": (_I, [_P, _L, _I, _P, _P, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -265,7 +277,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
-            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()):
+            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
+            list(ESSENTIAL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

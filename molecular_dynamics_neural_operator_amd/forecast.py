@@ -61,6 +61,16 @@ only says so.  Whether the run visits the RIGHT STRUCTURES is asked of every pro
     c = eng.cross_rmsd(truth, matrix=False)                     # CrossRmsd: nearest [S, M], cover [M, Fb] and their indices
     c.precision(2.0), c.coverage(2.0)                           # f64 [M]: frames near some true frame / true frames visited
     cross_rmsd(frames, folded[None]).to_reference(0)            # f64 [S, M]: the RMSD time series to one structure
+
+Essential dynamics.  Whether the run moves along the right collective coordinates, with the right amplitudes and the right
+slow timescales, is asked of the principal components of the superposed trajectory and of their time-lagged version
+(csrc/essential.hip: the covariance is one fp64 GEMM over the rows on the matrix pipe; include/mdno_essential.h has the rule):
+
+    aligned, rmsd = eng.superpose(reference)                    # every frame in the reference's frame of reference
+    pc = pca(covariance(superpose(truth, reference)[0]), 10)    # Components of the truth: values, vectors [3 N, 10]
+    pca(covariance(aligned[:, m].contiguous()), 10).rmsip(pc)   # member m's subspace against the truth's
+    free_energy(project(aligned, pc), 0, 1)                     # F [bins, bins] in kT over PC1/PC2, counts, edges
+    tica(c0, covariance(x, c0.mean, lag=10), 5).timescales()    # implied timescales in steps
 """
 from __future__ import annotations
 
@@ -503,6 +513,221 @@ def cross_rmsd(frames: torch.Tensor, reference: torch.Tensor, matrix: bool = Tru
     a superposition needs whole molecules (ops.cross_rmsd).  Asynchronous on the current stream; CPU tensors and bad
     arguments raise `MdnoError` before any device work."""
     return CrossRmsd(*ops.cross_rmsd(frames, reference, matrix=matrix, nearest=True, cover=True))
+
+
+# ------------------------------------------------------------------------------------------------
+# Essential dynamics (csrc/essential.hip, include/mdno_essential.h has the rules)
+def superpose(frames: torch.Tensor, reference: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """frames f32 [S, M, N, 3] (device; [F, N, 3] is one member) onto reference f32 [N, 3] -> (aligned f32 [S, M, N, 3],
+    rmsd f64 [S, M]): every frame in the reference's frame of reference (optimal proper rotation, centroid on the
+    reference's) and its RMSD to it.  A frame with a non-finite coordinate comes back as NaN.  Asynchronous on the current
+    stream; CPU tensors and bad arguments raise `MdnoError` before any device work."""
+    return ops.superpose_frames(frames, reference, aligned=True, rmsd=True)
+
+
+def _feature_rows(X: torch.Tensor, what: str = "X") -> Tuple[torch.Tensor, Tuple[int, ...]]:
+    """(X as [S, M, D], its leading shape): [S, M, N, 3] -> D = 3 N; [F, N, 3] -> one member, D = 3 N; [S, M, D]; [F, D] -> one
+    member.  A rank-3 tensor whose last dimension is 3 is taken as FRAMES [F, N, 3]: pass three features of M members as
+    [S, M, 1, 3]."""
+    if not torch.is_tensor(X):
+        raise MdnoError(f"{what} must be a torch tensor, got {type(X).__name__}")
+    if X.dim() == 4 and X.shape[-1] == 3:
+        return X.reshape(X.shape[0], X.shape[1], -1), tuple(X.shape[:2])
+    if X.dim() == 3 and X.shape[-1] == 3:
+        return X.reshape(X.shape[0], 1, -1), tuple(X.shape[:1])
+    if X.dim() == 3:
+        return X, tuple(X.shape[:2])
+    if X.dim() == 2:
+        return X[:, None], tuple(X.shape[:1])
+    raise MdnoError(f"{what} has shape {tuple(X.shape)}: expected [S, M, N, 3], [F, N, 3], [S, M, D] or [F, D]")
+
+
+@dataclass
+class Covariance:
+    """The pooled second-moment SUMS of `covariance`: sums[a, b] = sum over the n pairs of rows (t, t + lag) of the same member
+    of (x[t, a] - mean[a]) (x[t + lag, b] - mean[b])."""
+    mean: torch.Tensor               # f64 [D]
+    sums: torch.Tensor               # f64 [D, D]
+    n: int                           # M (S - lag) pairs
+    lag: int
+
+    def matrix(self) -> torch.Tensor:
+        """sums / (n - 1) at lag 0 (the unbiased covariance), sums / n at a lag; NaN where that divides by zero."""
+        return self.sums / float(self.n - 1 if self.lag == 0 else self.n)
+
+    def symmetrized(self) -> torch.Tensor:
+        """(matrix + matrix^T) / 2: the estimate TICA uses for a reversible process."""
+        m = self.matrix()
+        return 0.5 * (m + m.transpose(0, 1))
+
+    def rmsf(self) -> torch.Tensor:
+        """f64 [N] for D = 3 N coordinates: sqrt of the summed diagonal variances of each atom's x, y, z."""
+        D = self.sums.shape[0]
+        if D % 3:
+            raise MdnoError(f"Covariance.rmsf needs D = 3 N coordinates, D = {D}")
+        return torch.sqrt(torch.diagonal(self.matrix()).reshape(-1, 3).sum(1))
+
+    def cpu(self) -> "Covariance":
+        return Covariance(self.mean.cpu(), self.sums.cpu(), self.n, self.lag)
+
+
+def covariance(X: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0) -> Covariance:
+    """X f32 [S, M, N, 3], [F, N, 3] (superposed frames: `superpose` first) or any feature matrix [S, M, D] / [F, D] (a latent
+    matrix from forward(..., return_latent=True)) -> `Covariance`, pooled over the members, time lag `lag` along the first
+    axis.  `mean` f64 [D]: the centre, by default the mean over all S M rows (ops.feature_sums; computed on the device, not
+    read back).  One fp64 GEMM on the matrix pipe without an fp64 copy of X (ops.feature_covariance).  Asynchronous on the
+    current stream."""
+    x, _ = _feature_rows(X)
+    x, S, M, D = ops._features(x, "X")
+    if mean is None:
+        total, _ = ops.feature_sums(x.reshape(S * M, D))
+        mean = total / float(S * M)
+    sums = ops.feature_covariance(x, mean, lag)
+    return Covariance(mean if mean.dtype == torch.float64 else mean.to(torch.float64), sums, M * max(S - int(lag), 0), int(lag))
+
+
+def _fix_signs(v: torch.Tensor) -> torch.Tensor:
+    """Every column's largest-magnitude entry positive (the lowest index on a tie)."""
+    if v.numel() == 0:
+        return v
+    big = v.abs()
+    idx = (big == big.max(0, keepdim=True).values).to(torch.int8).argmax(0)          # the first maximal entry
+    sign = torch.where(v.gather(0, idx[None]) < 0, -1.0, 1.0).to(v.dtype)
+    return v * sign
+
+
+@dataclass
+class Components:
+    """k directions of feature space (`pca`, `tica`): values descending, vectors[:, c] the c-th direction."""
+    values: torch.Tensor             # f64 [k]
+    vectors: torch.Tensor            # f64 [D, k]
+    mean: torch.Tensor               # f64 [D]
+    total: float                     # pca: the trace of the covariance; tica: the number of whitened dimensions kept
+    lag: int = 0                     # tica: the lag of the time-lagged matrix
+
+    def explained_ratio(self) -> torch.Tensor:
+        """pca: values / trace of the covariance, f64 [k]."""
+        return self.values / self.total
+
+    def rmsip(self, other: "Components") -> float:
+        """The root-mean-square inner product of the two k-subspaces, sqrt(sum_ij (v_i . w_j)^2 / k): 1 = the same
+        subspace, 0 = orthogonal ones (orthonormal vectors: pca's)."""
+        k = self.vectors.shape[1]
+        if other.vectors.shape != self.vectors.shape:
+            raise MdnoError(f"rmsip: {tuple(self.vectors.shape)} against {tuple(other.vectors.shape)}")
+        g = self.vectors.cpu().transpose(0, 1) @ other.vectors.cpu()
+        return math.sqrt(float((g * g).sum()) / k)
+
+    def timescales(self) -> torch.Tensor:
+        """tica: the implied timescales -lag / ln |value| in steps, f64 [k] (inf at |value| = 1, 0 at value 0)."""
+        if self.lag <= 0:
+            raise MdnoError("timescales: these components have no lag (tica's have)")
+        return -float(self.lag) / torch.log(self.values.abs())
+
+    def cpu(self) -> "Components":
+        return Components(self.values.cpu(), self.vectors.cpu(), self.mean.cpu(), self.total, self.lag)
+
+
+def _check_k(k, limit: int, what: str) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= limit:
+        raise MdnoError(f"{what}: k = {k!r}, expected an integer in 1 .. {limit}")
+    return k
+
+
+def pca(cov: Covariance, k: int) -> Components:
+    """The k leading principal components of a lag-0 `Covariance`: fp64 torch.linalg.eigh of cov.matrix() on the HOST copy
+    (one read-back of D^2 doubles), eigenvalues descending, every vector's largest-magnitude entry positive (the lowest
+    index on a tie).  The result lives on cov's device."""
+    if cov.lag != 0:
+        raise MdnoError(f"pca needs a lag-0 covariance, got lag {cov.lag}")
+    D = cov.sums.shape[0]
+    k = _check_k(k, D, "pca")
+    m = cov.matrix().cpu()
+    w, v = torch.linalg.eigh(0.5 * (m + m.transpose(0, 1)))
+    w, v = w.flip(0)[:k], _fix_signs(v.flip(1)[:, :k].contiguous())
+    dev = cov.sums.device
+    return Components(w.to(dev), v.to(dev), cov.mean, float(torch.diagonal(m).sum()))
+
+
+def tica(cov0: Covariance, cov_lag: Covariance, k: int, eps: float = 1e-10) -> Components:
+    """Time-lagged independent components: whiten with the eigenpairs of C(0) above eps * lambda_max (superposition makes
+    C(0) rank-deficient by six, so the truncation is required), eigh of the whitened symmetrised C(lag) -> the k slowest
+    directions, values = their autocorrelations at the lag (descending), vectors [D, k] in the original features
+    (C(0)-orthonormal), signs as in `pca`.  `.timescales()` gives -lag / ln |value|.  On the host copy, fp64."""
+    if cov0.lag != 0 or cov_lag.lag <= 0:
+        raise MdnoError(f"tica needs C(0) and C(lag > 0), got lags {cov0.lag} and {cov_lag.lag}")
+    if cov0.sums.shape != cov_lag.sums.shape:
+        raise MdnoError(f"tica: C(0) is {tuple(cov0.sums.shape)}, C(lag) {tuple(cov_lag.sums.shape)}")
+    c0, ct = cov0.symmetrized().cpu(), cov_lag.symmetrized().cpu()
+    w, u = torch.linalg.eigh(c0)
+    keep = w > eps * w[-1] if w.numel() and w[-1] > 0 else torch.zeros_like(w, dtype=torch.bool)
+    r = int(keep.sum())
+    k = _check_k(k, r, f"tica ({r} of {w.numel()} dimensions above eps)") if r else _check_k(k, 0, "tica (C(0) has no positive eigenvalue)")
+    white = u[:, keep] / torch.sqrt(w[keep])
+    lam, q = torch.linalg.eigh(white.transpose(0, 1) @ ct @ white)
+    lam, q = lam.flip(0)[:k], q.flip(1)[:, :k]
+    dev = cov0.sums.device
+    return Components(lam.to(dev), _fix_signs((white @ q).contiguous()).to(dev), cov0.mean, float(r), cov_lag.lag)
+
+
+def project(X: torch.Tensor, components: Components) -> torch.Tensor:
+    """X (any form `covariance` takes) onto `components` -> P f64 [S, M, k] ([F, k] for a plain stack):
+    P[..., c] = (x - components.mean) . components.vectors[:, c], in fp64 on the device (ops.project_features)."""
+    x, lead = _feature_rows(X)
+    x, S, M, D = ops._features(x, "X")
+    return ops.project_features(x.reshape(S * M, D), components.mean, components.vectors).reshape(lead + (components.vectors.shape[1],))
+
+
+def free_energy(P: torch.Tensor, i: int = 0, j: int = 1, bins: int = 50, range=None):
+    """The free-energy surface over components i and j of the projections P f64 [..., k] -> (F f64 [bins, bins] in kT,
+    minimum at 0, +inf where a bin is empty; counts i64 [bins, bins]; edges f64 [2, bins + 1]).  `range` = ((lo_i, hi_i),
+    (lo_j, hi_j)), by default the data's own extent (one read-back); a point is counted in bin b when
+    edges[b] <= p < edges[b + 1], the last bin closed, and dropped outside the range or where it is NaN — comparisons
+    against the edges and integer counts on P's device, nothing rounded."""
+    if not torch.is_tensor(P) or P.dim() < 1:
+        raise MdnoError("free_energy: P must be a tensor [..., k]")
+    k = P.shape[-1]
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 1:
+        raise MdnoError(f"free_energy: bins = {bins!r}, expected a positive integer")
+    if not (0 <= i < k and 0 <= j < k):
+        raise MdnoError(f"free_energy: components {i} and {j} of {k}")
+    pts = [P[..., c].reshape(-1).to(torch.float64).contiguous() for c in (i, j)]
+    if range is None:
+        if pts[0].numel() == 0:
+            raise MdnoError("free_energy: no points and no range")
+        range = tuple((float(torch.nan_to_num(p, nan=float("inf")).min()), float(torch.nan_to_num(p, nan=float("-inf")).max())) for p in pts)
+    edges, idx, ok = [], [], None
+    for p, (lo, hi) in zip(pts, range):
+        lo, hi = float(lo), float(hi)
+        if not (math.isfinite(lo) and math.isfinite(hi)) or hi < lo:
+            raise MdnoError(f"free_energy: range ({lo}, {hi})")
+        if hi == lo:
+            lo, hi = lo - 0.5, hi + 0.5
+        e = torch.linspace(lo, hi, bins + 1, dtype=torch.float64)                      # (on the host: the same edges for any device)
+        e[0], e[-1] = lo, hi
+        e = e.to(P.device)
+        b = torch.bucketize(p, e, right=True) - 1
+        b = torch.where(p == hi, torch.full_like(b, bins - 1), b)
+        inside = (p >= lo) & (p <= hi)
+        ok = inside if ok is None else ok & inside
+        edges.append(e)
+        idx.append(b)
+    flat = (idx[0] * bins + idx[1])[ok]
+    counts = torch.bincount(flat, minlength=bins * bins).reshape(bins, bins)
+    total = counts.sum()
+    F = -torch.log(counts.to(torch.float64) / total.to(torch.float64))
+    F = F - F.min() if int(total) else torch.full_like(F, float("inf"))
+    return F, counts, torch.stack(edges)
+
+
+def histogram_total_variation(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Total variation distance of two count arrays of the same binning, [..., bins, bins] -> f64 [...]:
+    0.5 sum |a / sum a - b / sum b| (0 = the same distribution, 1 = disjoint; NaN where one is empty)."""
+    if a.shape[-2:] != b.shape[-2:]:
+        raise MdnoError(f"histogram_total_variation: {tuple(a.shape)} against {tuple(b.shape)}")
+    a, b = a.to(torch.float64), b.to(torch.float64)
+    pa, pb = a / a.sum((-2, -1), keepdim=True), b / b.sum((-2, -1), keepdim=True)
+    return 0.5 * (pa - pb).abs().sum((-2, -1))
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

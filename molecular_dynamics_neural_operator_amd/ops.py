@@ -1619,3 +1619,142 @@ def cross_rmsd(frames: torch.Tensor, reference: torch.Tensor, matrix: bool = Tru
                                   ptr(out_m), ptr(out_n), ptr(out_ni), ptr(out_c), ptr(out_cs), ptr(ws), nbytes,
                                   stream_ptr(dev)), "mdnoconf_cross_rmsd")
     return out_m, out_n, out_ni, out_c, out_cs
+
+
+# ------------------------------------------------------------------------------------------------
+# Essential dynamics (include/mdno_essential.h, csrc/essential.hip)
+PCA_TILE = 32                       # MDNO_PCA_TILE: features per side of a workgroup's tile of C
+PCA_ROW_PASS = 32                   # MDNO_PCA_ROW_PASS
+PCA_ROW_CHUNK = 64                  # MDNO_PCA_ROW_CHUNK: a split's length is a multiple of it
+PCA_TARGET_WORKGROUPS = 2048        # MDNO_PCA_TARGET_WORKGROUPS
+PCA_MAX_SPLITS = 256                # MDNO_PCA_MAX_SPLITS
+PCA_SUM_PARTIALS = 16               # MDNO_PCA_SUM_PARTIALS
+PCA_MAX_COMPONENTS = 32             # MDNO_PCA_MAX_COMPONENTS
+
+
+def covariance_row_split(K: int, D: int, lag: int):
+    """(rows per split L, splits) of mdnopca_covariance for K terms of D features: the ROW SPLIT rule of the header."""
+    T = -(-D // PCA_TILE)
+    tiles = T * (T + 1) // 2 if lag == 0 else T * T
+    if K <= 0 or tiles == 0:
+        return 0, 0
+    want = min(PCA_MAX_SPLITS, max(1, -(-PCA_TARGET_WORKGROUPS // tiles)))
+    L = PCA_ROW_CHUNK * -(-K // (want * PCA_ROW_CHUNK))
+    return L, -(-K // L)
+
+
+def _device_matrix(t, what: str, ranks, dtype=torch.float32) -> torch.Tensor:
+    """`t` as a contiguous device tensor of `dtype` and one of the given ranks, or MdnoError (no device work)."""
+    if not torch.is_tensor(t):
+        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise MdnoError(f"{what} is a CPU tensor: essential dynamics runs on the GPU only (no CPU fallback exists)")
+    if t.dim() not in ranks:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected rank {' or '.join(str(r) for r in ranks)}")
+    return (t if t.dtype == dtype else t.to(dtype)).contiguous()
+
+
+def _vector_f64(t, what: str, D: int, dev) -> torch.Tensor:
+    t = _device_matrix(t, what, (1,), torch.float64)
+    if t.shape[0] != D or t.device != dev:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)} on {t.device}: expected [{D}] on {dev}")
+    return t
+
+
+def superpose_frames(frames: torch.Tensor, reference: torch.Tensor, aligned: bool = True, rmsd: bool = True):
+    """frames f32 [S, M, N, 3] (or a plain stack [F, N, 3]: M = 1) onto reference f32 [N, 3] -> (aligned f32 like frames,
+    rmsd f64 [S, M]), None for what was not asked for: every frame after its optimal rigid superposition onto the
+    reference — centroid on the reference's centroid, proper rotations only (include/mdno_essential.h has the rule;
+    mdnopca_superpose).  A frame with a NaN or Inf coordinate comes back as NaN, with a NaN rmsd.  Fixed summation order:
+    the bits of a frame's outputs depend on that frame, the reference and N alone.  Asynchronous on the current stream."""
+    frames, S, M, N = _trajectory(frames)
+    reference = _device_frames(reference, "reference", (2,))
+    if reference.device != frames.device:
+        raise MdnoError(f"reference is on {reference.device}, frames on {frames.device}")
+    if reference.shape[0] != N:
+        raise MdnoError(f"reference shape {tuple(reference.shape)} does not match frames {tuple(frames.shape)}: expected [{N}, 3]")
+    if not (aligned or rmsd):
+        raise MdnoError("superpose_frames: no output was asked for (aligned and rmsd are both False)")
+    lib = _lib.load()
+    dev = frames.device
+    out_a = torch.empty_like(frames) if aligned else None
+    out_r = torch.empty((S, M), dtype=torch.float64, device=dev) if rmsd else None
+    if S * M:
+        check(lib.mdnopca_superpose(ptr(frames) if N else None, S, M, N, ptr(reference) if N else None, ptr(out_a), ptr(out_r),
+                                    stream_ptr(dev)), "mdnopca_superpose")
+    return out_a, out_r
+
+
+def feature_sums(x: torch.Tensor):
+    """x f32 [R, D] (device) -> (sum f64 [D], n_invalid i64 [1]): the column sums over the rows in a fixed order and the
+    number of rows that hold a NaN or Inf (such a row makes the columns it touches NaN); mdnopca_feature_sums.  The mean
+    is sum / R.  Asynchronous on the current stream, nothing is read back."""
+    x = _device_matrix(x, "x", (2,))
+    R, D = x.shape
+    if D >= 2 ** 31:
+        raise MdnoError(f"x has shape {tuple(x.shape)}: D exceeds 2^31 - 1")
+    lib = _lib.load()
+    dev = x.device
+    total = torch.empty(D, dtype=torch.float64, device=dev)
+    bad = torch.empty(1, dtype=torch.int64, device=dev)
+    check(lib.mdnopca_feature_sums(ptr(x) if R * D else None, R, D, ptr(total) if D else None, ptr(bad), stream_ptr(dev)),
+          "mdnopca_feature_sums")
+    return total, bad
+
+
+def _features(x, what: str = "x"):
+    """(x as contiguous f32 [S, M, D] on the device, S, M, D); [F, D] is M = 1."""
+    x = _device_matrix(x, what, (2, 3))
+    if x.dim() == 2:
+        x = x[:, None]
+    S, M, D = x.shape
+    if max(S, M, D) >= 2 ** 31:
+        raise MdnoError(f"{what} has shape {tuple(x.shape)}: a dimension exceeds 2^31 - 1")
+    return x, S, M, D
+
+
+def feature_covariance(x: torch.Tensor, mean: torch.Tensor, lag: int = 0) -> torch.Tensor:
+    """x f32 [S, M, D] (or [F, D]: M = 1), mean f64 [D], lag >= 0 -> C f64 [D, D], the SUMS
+    C[a, b] = sum_m sum_t (x[t, m, a] - mean[a]) (x[t + lag, m, b] - mean[b]) over the M (S - lag) pairs, pooled over the
+    members (include/mdno_essential.h has the rule; mdnopca_covariance): one fp64 GEMM on the matrix pipe, the rows
+    centred in fp64 on the way in, no fp64 copy of x.  lag 0 is bitwise symmetric; lag >= S gives zeros.  Fixed summation
+    order: the same bits on every run.  Asynchronous on the current stream."""
+    x, S, M, D = _features(x)
+    if isinstance(lag, bool) or not isinstance(lag, int) or lag < 0 or lag >= 2 ** 31:
+        raise MdnoError(f"lag {lag!r}: expected an integer >= 0")
+    mean = _vector_f64(mean, "mean", D, x.device)
+    lib = _lib.load()
+    dev = x.device
+    out = torch.empty((D, D), dtype=torch.float64, device=dev)
+    if D == 0:
+        return out
+    work = M * max(S - lag, 0) > 0
+    nbytes = lib.mdnopca_covariance_workspace_bytes(S, M, D, lag) if work else 0
+    ws = _ws(nbytes, dev) if work else None
+    check(lib.mdnopca_covariance(ptr(x) if work else None, S, M, D, ptr(mean), lag, ptr(out), ptr(ws), nbytes, stream_ptr(dev)),
+          "mdnopca_covariance")
+    return out
+
+
+def project_features(x: torch.Tensor, mean: torch.Tensor, vectors: torch.Tensor) -> torch.Tensor:
+    """x f32 [R, D], mean f64 [D], vectors f64 [D, k] (1 <= k <= PCA_MAX_COMPONENTS) -> P f64 [R, k],
+    P[r, c] = sum_a (x[r, a] - mean[a]) vectors[a, c], one running fp64 sum in ascending a (mdnopca_project).
+    Asynchronous on the current stream."""
+    x = _device_matrix(x, "x", (2,))
+    R, D = x.shape
+    if D >= 2 ** 31:
+        raise MdnoError(f"x has shape {tuple(x.shape)}: D exceeds 2^31 - 1")
+    mean = _vector_f64(mean, "mean", D, x.device)
+    vectors = _device_matrix(vectors, "vectors", (2,), torch.float64)
+    if vectors.shape[0] != D or vectors.device != x.device:
+        raise MdnoError(f"vectors has shape {tuple(vectors.shape)} on {vectors.device}: expected [{D}, k] on {x.device}")
+    k = vectors.shape[1]
+    if not 1 <= k <= PCA_MAX_COMPONENTS:
+        raise MdnoError(f"vectors has k = {k} columns: expected 1 .. {PCA_MAX_COMPONENTS}")
+    lib = _lib.load()
+    dev = x.device
+    out = torch.empty((R, k), dtype=torch.float64, device=dev)
+    if R:
+        check(lib.mdnopca_project(ptr(x) if D else None, R, D, ptr(mean) if D else None, ptr(vectors) if D else None, k, ptr(out),
+                                  stream_ptr(dev)), "mdnopca_project")
+    return out

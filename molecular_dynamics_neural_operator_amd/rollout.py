@@ -473,6 +473,21 @@ class RolloutEngine:
         from .forecast import cross_rmsd
         return cross_rmsd(self._observed(first_step, steps), reference, matrix)
 
+    def superpose(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.superpose` of the produced frames of steps first_step .. first_step + steps - 1 (default: all) onto
+        reference f32 [N, 3] -> (aligned f32 [steps, M, N, 3], rmsd f64 [steps, M]); the frames are read where they are, on
+        the current stream after the engine's enqueued steps (as `score`)."""
+        from .forecast import superpose
+        return superpose(self._observed(first_step, steps), reference)
+
+    def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
+                   steps: Optional[int] = None):
+        """`forecast.covariance` of the produced frames (same range arguments as `score`) after their superposition onto
+        reference f32 [N, 3], pooled over the members -> `forecast.Covariance` over the 3 N coordinates: the bits of
+        `forecast.covariance(forecast.superpose(self.produced(...), reference)[0], mean, lag)`."""
+        from .forecast import covariance
+        return covariance(self.superpose(reference, first_step, steps)[0], mean, lag)
+
     def close(self) -> None:
         if self.plan:
             self.stream.synchronize()
@@ -648,6 +663,22 @@ class GroupedRolloutEngine:
         and the result is that of all members scored at once."""
         from .forecast import CrossRmsd
         return CrossRmsd.cat([e.cross_rmsd(reference, first_step, steps, matrix) for e in self.engines])
+
+    def superpose(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.superpose` for every group on its own frames, joined along the member axis: a frame's outputs
+        depend on that frame and the reference alone, so these are the bits of
+        `forecast.superpose(self.produced(first_step, steps), reference)`."""
+        parts = [e.superpose(reference, first_step, steps) for e in self.engines]
+        return torch.cat([a for a, _ in parts], dim=1), torch.cat([r for _, r in parts], dim=1)
+
+    def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
+                   steps: Optional[int] = None):
+        """`forecast.covariance` of ALL groups' members pooled: the covariance sums run across the members, so each group
+        is superposed on its own, the aligned frames are concatenated along the member axis and ONE covariance call
+        follows: the bits of `forecast.covariance(forecast.superpose(self.produced(first_step, steps), reference)[0], mean,
+        lag)`."""
+        from .forecast import covariance
+        return covariance(self.superpose(reference, first_step, steps)[0], mean, lag)
 
     @property
     def edges_per_step(self) -> torch.Tensor:

@@ -13,10 +13,16 @@ the spread, the spread-skill ratio, the CRPS and the fair CRPS, and the flatness
 it they differ only by their starting windows.  With `--coverage RADIUS` also the structural coverage
 (forecast.CrossRmsd): every produced frame against every frame of the truth, per member the precision (the share of its
 frames within RADIUS of some true frame), the coverage (the share of the true frames it comes within RADIUS of) and the
-median nearest-frame RMSD (INTEGRATION.md "Does the run visit the right structures?" reads them).
+median nearest-frame RMSD (INTEGRATION.md "Does the run visit the right structures?" reads them).  With `--pca K` also the
+essential dynamics (forecast.pca): the truth, superposed on its first frame, gives K principal components; printed are its
+explained-variance ratios, per member the RMSIP of the member's own top-K subspace with the truth's and the total variation
+between the member's and the truth's PC1/PC2 histograms, both projected on the TRUTH's components; with `--tica LAG` also
+the leading implied timescales of the truth and of the pooled members (INTEGRATION.md "Does the run move along the right
+coordinates?" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
+                                    [--pca 10] [--tica 10]
 """
 import argparse
 import json
@@ -52,7 +58,14 @@ def main() -> None:
     ap.add_argument("--coverage", type=float, metavar="RADIUS", default=None,
                     help="also score the structural coverage: per member the precision, the coverage and the median "
                          "nearest-frame RMSD against the truth, at this radius")
+    ap.add_argument("--pca", type=int, metavar="K", default=None,
+                    help="also score the essential dynamics: K principal components of the superposed truth, per member the "
+                         "RMSIP with them and the total variation of the PC1/PC2 histograms")
+    ap.add_argument("--tica", type=int, metavar="LAG", default=None,
+                    help="with --pca: also the K leading implied timescales at this lag, of the truth and of the pooled members")
     a = ap.parse_args()
+    if a.tica is not None and a.pca is None:
+        ap.error("--tica needs --pca K")
     if a.msd is not None and len(a.msd) not in (0, 2):
         ap.error("--msd takes no values or R_MAX N_BINS")
 
@@ -148,6 +161,37 @@ def main() -> None:
         dist.update({"coverage_radius": a.coverage, "coverage_precision": finite(cr.precision(a.coverage).cpu()),
                      "coverage": finite(cr.coverage(a.coverage).cpu()),
                      "nearest_true_frame_rmsd_median": finite(cr.nearest.nanmedian(0).values.cpu())})
+
+    if a.pca is not None and S > 2:
+        from molecular_dynamics_neural_operator_amd import forecast as fc
+        K, bins = a.pca, 32
+        reference = truth[0].contiguous()
+        t_al = fc.superpose(truth, reference)[0]                                     # [S, 1, N, 3]
+        t_cov = fc.covariance(t_al)
+        t_pc = fc.pca(t_cov, K)
+        f_al = eng.superpose(reference)[0]                                           # [S, M, N, 3]
+        t_proj, f_proj = fc.project(t_al, t_pc), fc.project(f_al, t_pc)              # [S, 1, K], [S, M, K]
+        lo = torch.minimum(t_proj.amin((0, 1)), f_proj.nan_to_num(posinf=0.0, neginf=0.0).amin((0, 1))).cpu()
+        hi = torch.maximum(t_proj.amax((0, 1)), f_proj.nan_to_num(posinf=0.0, neginf=0.0).amax((0, 1))).cpu()
+        j = 1 if K > 1 else 0
+        rng = ((float(lo[0]), float(hi[0])), (float(lo[j]), float(hi[j])))
+        t_hist = fc.free_energy(t_proj, 0, j, bins, rng)[1]
+        rmsip, tv = [], []
+        for m in range(M):                                                           # per member: slice and copy (forecast.covariance pools)
+            own = f_al[:, m].contiguous()
+            ok = bool(torch.isfinite(own).all())
+            rmsip.append(fc.pca(fc.covariance(own), K).rmsip(t_pc) if ok else float("nan"))
+            tv.append(float(fc.histogram_total_variation(fc.free_energy(f_proj[:, m], 0, j, bins, rng)[1], t_hist)))
+        dist.update({"pca_k": K, "pca_truth_explained_ratio": finite(t_pc.explained_ratio().cpu()),
+                     "pca_rmsip_with_truth": finite(np.asarray(rmsip)), "pca_pc12_total_variation": finite(np.asarray(tv)),
+                     "pca_truth_rmsf_mean": float(t_cov.rmsf().mean())})
+        if a.tica is not None and 0 < a.tica < S - 1:
+            t_tica = fc.tica(t_cov, fc.covariance(t_al, t_cov.mean, a.tica), K)
+            f_cov = eng.covariance(reference)
+            dist.update({"tica_lag": a.tica, "tica_truth_timescales": finite(t_tica.timescales().cpu())})
+            if bool(torch.isfinite(f_cov.sums).all()):
+                f_tica = fc.tica(f_cov, eng.covariance(reference, f_cov.mean, a.tica), K)
+                dist["tica_forecast_timescales"] = finite(f_tica.timescales().cpu())
 
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,

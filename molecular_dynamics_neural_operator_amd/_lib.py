@@ -245,6 +245,20 @@ ESSENTIAL_SIGNATURES = {
     "mdnopca_project": (_I, [_P, _L, _I, _P, _P, _I, _P, _P]),
 }
 
+# include/mdno_markov.h (Markov state models: nearest-centre assignment, k-centres seeding, per-state row sums, transition
+# counts at a set of lags; additive, no version number of its own): name -> (restype, argtypes), kept in step with that
+# header (tests/test_markov_host.py checks both ways).  The names start with mdnomsm_, for the reason mdnoens_ has (the
+# header says so too).  `lags` is a HOST pointer to n_lags int32.
+MARKOV_DTYPES = {"float32": 0, "float64": 1}
+MARKOV_SIGNATURES = {
+    "mdnomsm_assign_workspace_bytes": (_SZ, [_L, _I, _I]),
+    "mdnomsm_assign": (_I, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mdnomsm_kcenters_workspace_bytes": (_SZ, [_L, _I]),
+    "mdnomsm_kcenters": (_I, [_P, _L, _I, _I, _I, _L, _P, _P, _P, _SZ, _P]),
+    "mdnomsm_centroid_sums": (_I, [_P, _L, _I, _I, _P, _I, _P, _P, _P]),
+    "mdnomsm_transition_counts": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -278,7 +292,7 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
             list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
-            list(ESSENTIAL_SIGNATURES.items()):
+            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

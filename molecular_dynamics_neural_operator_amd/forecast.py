@@ -71,6 +71,19 @@ slow timescales, is asked of the principal components of the superposed trajecto
     pca(covariance(aligned[:, m].contiguous()), 10).rmsip(pc)   # member m's subspace against the truth's
     free_energy(project(aligned, pc), 0, 1)                     # F [bins, bins] in kT over PC1/PC2, counts, edges
     tica(c0, covariance(x, c0.mean, lag=10), 5).timescales()    # implied timescales in steps
+
+Markov state models.  Whether the run populates the truth's STATES with the right weights and hops between them at the right
+rates is asked of a partition of the projected (or superposed) space: cluster the truth, assign every frame of truth and run
+to the nearest centre (csrc/markov.hip: the inner products on the fp64 matrix pipe; include/mdno_markov.h has the rule), count
+the transitions at a lag on the device and estimate the model on the host:
+
+    disc = discretize(truth, 100, components=tc)                # Discretization: k-centres (or k-means) in the truth's TICA space
+    a = eng.assign(disc)                                        # Assignment: labels i32, dist2 f64 [S, M]
+    a.outside(disc.radius)                                      # f64 [M]: the share of the run off the truth's manifold
+    counts = transition_counts(a.labels, 100, [10, 20, 40])     # TransitionCounts: i64 [L, M, n, n], exact
+    msm = markov_model(counts)                                  # MarkovModel: active set, T, spectrum, stationary distribution
+    msm.timescales(5), msm.chapman_kolmogorov(counts, 1)        # implied timescales in steps; T^2 against the lag-20 estimate
+    msm.population_total_variation(markov_model(truth_counts))  # 0 = the truth's state weights, 1 = disjoint
 """
 from __future__ import annotations
 
@@ -728,6 +741,328 @@ def histogram_total_variation(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     a, b = a.to(torch.float64), b.to(torch.float64)
     pa, pb = a / a.sum((-2, -1), keepdim=True), b / b.sum((-2, -1), keepdim=True)
     return 0.5 * (pa - pb).abs().sum((-2, -1))
+
+
+# ------------------------------------------------------------------------------------------------
+# Markov state models (csrc/markov.hip, include/mdno_markov.h has the rules)
+@dataclass
+class Assignment:
+    """Every frame's state (`assign`): `labels` i32 and `dist2` f64, shaped like the input's leading dimensions ([S, M], or
+    [F] for a plain stack): the index of the nearest centre and the squared distance to it; -1 and NaN for a frame that
+    holds a non-finite value (or where no centre could be chosen).  Methods run on the device of the fields."""
+    labels: torch.Tensor
+    dist2: torch.Tensor
+
+    def outside(self, radius) -> torch.Tensor:
+        """The share of the frames, per member (f64 [M]; a scalar for [F]), that lie farther than `radius` from EVERY centre
+        — with the truth's covering radius, how much of a run is off the truth's manifold.  A frame without a label counts
+        as outside; NaN without frames."""
+        r = radius.to(self.dist2.device, torch.float64) if torch.is_tensor(radius) else float(radius)
+        inside = torch.sqrt(self.dist2) <= r                                        # (NaN: not inside; sqrt is monotone, so a
+        #                                                                             frame AT the covering radius is inside)
+        return ForecastScore._ratio((~inside).sum(0), torch.full_like(inside.sum(0), self.dist2.shape[0] if self.dist2.dim() else 1))
+
+    def populations(self, n_states: int) -> torch.Tensor:
+        """The share of the labelled frames in each state, per member: f64 [M, n_states] ([n_states] for [F]); NaN for a
+        member without a labelled frame.  Labels outside 0 .. n_states - 1 are left out."""
+        lab = self.labels.reshape(self.labels.shape[0], -1).to(torch.int64)
+        M = lab.shape[1]
+        ok = (lab >= 0) & (lab < n_states)
+        flat = (torch.arange(M, device=lab.device)[None] * n_states + lab)[ok]
+        counts = torch.bincount(flat, minlength=M * n_states).reshape(M, n_states)
+        pops = ForecastScore._ratio(counts, counts.sum(1, keepdim=True).expand_as(counts))
+        return pops.reshape(self.labels.shape[1:] + (n_states,))
+
+    def cpu(self) -> "Assignment":
+        return Assignment(self.labels.cpu(), self.dist2.cpu())
+
+    @staticmethod
+    def cat(parts: Sequence["Assignment"]) -> "Assignment":
+        """Results of disjoint member ranges of the same steps against the same centres, members in order."""
+        return Assignment(torch.cat([q.labels for q in parts], 1), torch.cat([q.dist2 for q in parts], 1))
+
+
+def _state_rows(X: torch.Tensor, what: str = "X"):
+    """(X as a matrix of rows [R, D] — f64 stays f64, anything else becomes f32 —, its leading shape), forms as in
+    `_feature_rows`."""
+    x, lead = _feature_rows(X, what)
+    return x.reshape(-1, x.shape[-1]), lead
+
+
+def _centre_rows(centres: torch.Tensor) -> torch.Tensor:
+    if not torch.is_tensor(centres) or centres.dim() not in (2, 3):
+        raise MdnoError("centres: expected a tensor [k, D] or frames [k, N, 3]")
+    return centres.reshape(centres.shape[0], -1)
+
+
+def _assign_rows(rows: torch.Tensor, lead, centres: torch.Tensor, origin) -> Assignment:
+    centres = _centre_rows(centres)
+    if torch.is_tensor(rows) and torch.is_tensor(centres) and rows.dtype != centres.dtype and rows.is_cuda and centres.is_cuda:
+        centres = centres.to(torch.float64 if rows.dtype == torch.float64 else torch.float32)
+    if origin is None and centres.is_cuda and centres.shape[0] > 0:
+        origin = centres.to(torch.float64).mean(0)
+    labels, dist2 = ops.assign_features(rows, centres, origin)
+    return Assignment(labels.reshape(lead), dist2.reshape(lead))
+
+
+def assign(X: torch.Tensor, centres: torch.Tensor, origin: Optional[torch.Tensor] = None) -> Assignment:
+    """X — any form `covariance` takes, or the f64 projections of `project` ([S, M, k] / [F, k]; like there, a rank-3 tensor
+    whose last dimension is 3 is taken as frames) — against centres [k, D] (or frames [k, N, 3]) -> `Assignment`: the nearest
+    centre of every frame in fp64, the inner products on the matrix pipe (ops.assign_features).  `origin` f64 [D]: the point
+    the expansion |x|^2 + |c|^2 - 2 x.c is taken about, by default the centres' mean in fp64 — it keeps the cancellation
+    small where the coordinates carry a large common offset; the labels do not depend on it beyond rounding.  Asynchronous
+    on the current stream; CPU tensors and bad arguments raise `MdnoError` before any device work."""
+    rows, lead = _state_rows(X)
+    return _assign_rows(rows, lead, centres, origin)
+
+
+def kcenters(X: torch.Tensor, k: int, first: int = 0):
+    """Deterministic farthest-point seeding of k centres among the frames of X (forms as in `assign`), starting from row
+    `first` of the flat [S M, D] matrix -> (centres [k, D] in X's element type, index i64 [k], radius f64 [k]); radius[i]
+    is the covering radius before centre i was added (radius[0] = +inf).  All on the device, nothing read back
+    (ops.kcenters)."""
+    rows, _ = _state_rows(X)
+    index, radius = ops.kcenters(rows, k, first)
+    rows = rows if rows.dtype == torch.float64 else rows.to(torch.float32)
+    return rows.index_select(0, index.clamp(min=0)), index, radius
+
+
+def kmeans(X: torch.Tensor, k: int, iters: int = 10, init: Optional[torch.Tensor] = None):
+    """k-means on the device: k-centres seeding (or `init` [k, D]), then `iters` Lloyd rounds of `assign` + ops.centroid_sums
+    -> (centres [k, D] in X's element type, `Assignment` of X against them, moved i64 [iters]).  A state without frames keeps
+    its centre; new centres are sums / counts in fp64, rounded once to X's element type.  moved[i] is the number of frames
+    whose label round i changed (0: converged); it stays on the device, like everything inside the loop — nothing is read
+    back."""
+    rows, lead = _state_rows(X)
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise MdnoError(f"kmeans: iters = {iters!r}, expected an integer >= 0")
+    if init is None:
+        centres = kcenters(rows, k)[0]
+    else:
+        centres = _centre_rows(init)
+        if centres.shape[0] != k:
+            raise MdnoError(f"kmeans: init has {centres.shape[0]} rows, k = {k}")
+    dtype = torch.float64 if rows.dtype == torch.float64 else torch.float32
+    centres = centres.to(dtype)
+    flat = (rows.shape[0],)
+    current = _assign_rows(rows, flat, centres, None)
+    moved = []
+    for _ in range(iters):
+        sums, counts = ops.centroid_sums(rows, current.labels, k)
+        mean = sums / counts.to(torch.float64)[:, None]
+        centres = torch.where((counts > 0)[:, None], mean, centres.to(torch.float64)).to(dtype)
+        nxt = _assign_rows(rows, flat, centres, None)
+        moved.append((nxt.labels != current.labels).sum())
+        current = nxt
+    moved = torch.stack(moved) if moved else torch.zeros(0, dtype=torch.int64, device=rows.device)
+    return centres, Assignment(current.labels.reshape(lead), current.dist2.reshape(lead)), moved
+
+
+@dataclass
+class Discretization:
+    """A partition of conformation space into states (`discretize`): frames are superposed onto `reference` f32 [N, 3],
+    projected onto `components` (if any) and assigned to the nearest of `centres` [k, D]; `radius` (an f64 scalar on the
+    device) is the covering radius of the frames it was built from: the largest distance of one of them to its centre."""
+    reference: torch.Tensor
+    components: Optional[Components]
+    centres: torch.Tensor
+    radius: torch.Tensor
+
+    @property
+    def n_states(self) -> int:
+        return int(self.centres.shape[0])
+
+    def features(self, frames: torch.Tensor):
+        """(rows [S M, D], leading shape) of frames f32 [S, M, N, 3] or [F, N, 3]: superposed, then projected."""
+        aligned, _ = superpose(frames, self.reference)
+        lead = tuple(frames.shape[:-2])
+        if self.components is None:
+            return aligned.reshape(-1, aligned.shape[-2] * 3), lead
+        P = project(aligned, self.components)
+        return P.reshape(-1, P.shape[-1]), lead
+
+    def assign(self, frames: torch.Tensor) -> Assignment:
+        """superpose -> project (if components) -> assign; labels and dist2 shaped like the frames' leading dimensions.  A
+        frame's result depends on that frame alone."""
+        rows, lead = self.features(frames)
+        return _assign_rows(rows, lead, self.centres, None)
+
+
+def discretize(truth: torch.Tensor, n_states: int, components: Optional[Components] = None, method: str = "kcenters",
+               iters: int = 10, reference: Optional[torch.Tensor] = None) -> Discretization:
+    """Cut the space the frames of `truth` (f32 [S, M, N, 3] or [F, N, 3]) visit into `n_states` states: superposed onto
+    `reference` (by default the first frame), projected onto `components` if given (pca / tica of the same superposed
+    frames), then clustered by "kcenters" (farthest-point: even coverage, the covering radius is minimised greedily) or
+    "kmeans" (`iters` Lloyd rounds from that seeding)."""
+    if method not in ("kcenters", "kmeans"):
+        raise MdnoError(f"discretize: method = {method!r}, expected 'kcenters' or 'kmeans'")
+    if not torch.is_tensor(truth) or truth.dim() not in (3, 4) or truth.shape[-1] != 3:
+        raise MdnoError("discretize: truth must be frames [S, M, N, 3] or [F, N, 3]")
+    if reference is None:
+        reference = truth.reshape(-1, truth.shape[-2], 3)[0].contiguous() if truth.numel() else truth.new_zeros(truth.shape[-2], 3)
+    d = Discretization(reference, components, truth.new_zeros(0, 0), torch.zeros((), dtype=torch.float64))
+    rows, _ = d.features(truth)
+    if method == "kcenters":
+        centres = kcenters(rows, n_states)[0]
+        fit = _assign_rows(rows, (rows.shape[0],), centres, None)
+    else:
+        centres, fit, _ = kmeans(rows, n_states, iters)
+    worst = torch.nan_to_num(fit.dist2.reshape(-1), nan=0.0).max() if rows.shape[0] else torch.zeros((), dtype=torch.float64, device=rows.device)
+    return Discretization(reference, components, centres, torch.sqrt(worst))
+
+
+@dataclass
+class TransitionCounts:
+    """`transition_counts`: counts i64 [L, M (or 1 when pooled), n, n], counts[l, m, i, j] = the number of origins t with
+    label[t, m] = i and label[t + lags[l], m] = j; n_skipped i64 [L], the pairs with a label outside 0 .. n - 1."""
+    counts: torch.Tensor
+    n_skipped: torch.Tensor
+    lags: Tuple[int, ...]
+
+    def sum_members(self) -> "TransitionCounts":
+        return TransitionCounts(self.counts.sum(1, keepdim=True), self.n_skipped, self.lags)
+
+    def cpu(self) -> "TransitionCounts":
+        return TransitionCounts(self.counts.cpu(), self.n_skipped.cpu(), self.lags)
+
+    @staticmethod
+    def cat(parts: Sequence["TransitionCounts"]) -> "TransitionCounts":
+        """Per-member counts of disjoint member ranges at the same lags, members in order."""
+        if any(q.lags != parts[0].lags for q in parts):
+            raise MdnoError("TransitionCounts.cat: the parts were counted at different lags")
+        return TransitionCounts(torch.cat([q.counts for q in parts], 1), torch.stack([q.n_skipped for q in parts]).sum(0), parts[0].lags)
+
+
+def transition_counts(labels: torch.Tensor, n_states: int, lags, pooled: bool = False) -> TransitionCounts:
+    """labels i32 [S, M] (`Assignment.labels`; [S] is one member) -> `TransitionCounts` at the given lags, sliding window,
+    per member or pooled; exact integer counts on the device (ops.transition_counts)."""
+    counts, skipped = ops.transition_counts(labels, n_states, lags, pooled)
+    return TransitionCounts(counts, skipped, tuple(ops.check_msm_lags(lags)))
+
+
+def _largest_connected_set(c: torch.Tensor):
+    """The largest strongly connected set of the graph with an edge i -> j where c[i, j] > 0, among the visited states (a
+    state with a count in its row or column); of equally large sets the one that holds the lowest state.  A sorted list."""
+    n = c.shape[0]
+    pos = c > 0
+    visited = (pos.any(0) | pos.any(1)).tolist()
+    fwd = [torch.nonzero(pos[i]).reshape(-1).tolist() for i in range(n)]
+    bwd = [torch.nonzero(pos[:, i]).reshape(-1).tolist() for i in range(n)]
+
+    def reach(start, adj):
+        seen, stack = {start}, [start]
+        while stack:
+            for j in adj[stack.pop()]:
+                if j not in seen:
+                    seen.add(j)
+                    stack.append(j)
+        return seen
+    best, done = [], set()
+    for s in range(n):
+        if not visited[s] or s in done:
+            continue
+        comp = reach(s, fwd) & reach(s, bwd)
+        done |= comp
+        if len(comp) > len(best):                                                  # (ascending s: the first of equals stays)
+            best = sorted(comp)
+    return best
+
+
+def _transition_matrix(c: torch.Tensor, reversible: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(T, the matrix whose rows were normalised): c + c^T for the reversible estimate, c otherwise; a row without counts
+    becomes NaN."""
+    m = c + c.transpose(0, 1) if reversible else c
+    return m / m.sum(1, keepdim=True), m
+
+
+@dataclass
+class MarkovModel:
+    """`markov_model`: the transition matrix `T` f64 [a, a] among the `active` states (i64 [a], ascending), its
+    `eigenvalues` (descending in magnitude; real f64 for the reversible estimate, complex otherwise) and the stationary
+    distribution `pi` f64 [a], all on the host."""
+    lag: int
+    n_states: int
+    active: torch.Tensor
+    T: torch.Tensor
+    eigenvalues: torch.Tensor
+    pi: torch.Tensor
+    reversible: bool
+
+    def stationary(self) -> torch.Tensor:
+        """f64 [n_states]: pi on the active states, 0 elsewhere."""
+        out = torch.zeros(self.n_states, dtype=torch.float64)
+        out[self.active] = self.pi
+        return out
+
+    def timescales(self, k: Optional[int] = None) -> torch.Tensor:
+        """The implied timescales -lag / ln |lambda_i| in steps for i = 2 .. k + 1 (default: all), f64 [k]: inf at
+        |lambda| = 1, 0 at lambda = 0."""
+        a = self.eigenvalues.shape[0]
+        k = a - 1 if k is None else _check_k(k, max(a - 1, 0), "timescales") if a > 1 else _check_k(k, 0, "timescales (one active state)")
+        mag = self.eigenvalues.abs()[1:k + 1].to(torch.float64)
+        ts = -float(self.lag) / torch.log(mag)
+        return torch.where(mag >= 1.0, torch.full_like(ts, float("inf")), torch.where(mag == 0.0, torch.zeros_like(ts), ts))
+
+    def free_energies(self) -> torch.Tensor:
+        """-ln pi in kT over the active states, minimum 0, f64 [a]."""
+        f = -torch.log(self.pi)
+        return f - f.min()
+
+    def chapman_kolmogorov(self, counts: TransitionCounts, lag_index: int) -> torch.Tensor:
+        """Does the model predict the kinetics at a longer lag: with n = counts.lags[lag_index] / lag (a positive integer,
+        else MdnoError), per active state i the total variation 0.5 sum_j |T^n[i, j] - T_n[i, j]| between the model's n-th
+        power and the matrix estimated the same way, on the same active set, from the counts at n x lag; f64 [a].  NaN for
+        a state without counts at that lag."""
+        if not 0 <= lag_index < len(counts.lags):
+            raise MdnoError(f"chapman_kolmogorov: lag_index = {lag_index} of {len(counts.lags)} lags")
+        big = counts.lags[lag_index]
+        if big % self.lag:
+            raise MdnoError(f"chapman_kolmogorov: lag {big} is no multiple of the model's lag {self.lag}")
+        c = counts.counts[lag_index].sum(0).cpu().to(torch.float64)[self.active][:, self.active]
+        t_n, _ = _transition_matrix(c, self.reversible)
+        return 0.5 * (torch.linalg.matrix_power(self.T, big // self.lag) - t_n).abs().sum(1)
+
+    def population_total_variation(self, other: "MarkovModel") -> torch.Tensor:
+        """The total variation distance of the two stationary distributions over the union of the active sets (a state
+        outside a model's active set has weight 0 there): 0 = the same populations, 1 = disjoint."""
+        if other.n_states != self.n_states:
+            raise MdnoError(f"population_total_variation: {self.n_states} states against {other.n_states}")
+        return 0.5 * (self.stationary() - other.stationary()).abs().sum()
+
+
+def markov_model(counts: TransitionCounts, lag_index: int = 0, reversible: bool = True, member: Optional[int] = None) -> MarkovModel:
+    """A Markov state model from the counts at lags[lag_index], summed over the members (or of one `member`), on the host
+    copy in fp64.  The active set is the largest strongly connected set of the count graph among the visited states (ties:
+    the set with the lowest state).  reversible=True: T = (C + C^T) row-normalised — the symmetrised estimate `tica` uses —,
+    pi = its row sums normalised, spectrum by eigh of D^-1/2 (C + C^T) D^-1/2 (real).  reversible=False: T = C
+    row-normalised, spectrum and pi by eig."""
+    if not 0 <= lag_index < len(counts.lags):
+        raise MdnoError(f"markov_model: lag_index = {lag_index} of {len(counts.lags)} lags")
+    c = counts.counts[lag_index].cpu()
+    c = (c.sum(0) if member is None else c[member]).to(torch.float64)
+    n = c.shape[0]
+    active = _largest_connected_set(c)
+    if not active:
+        raise MdnoError("markov_model: no transition was counted")
+    idx = torch.tensor(active, dtype=torch.int64)
+    T, m = _transition_matrix(c[idx][:, idx], reversible)
+    d = m.sum(1)
+    empty = d == 0                                                                 # (a single state that was only left)
+    T = torch.where(empty[:, None], torch.eye(len(active), dtype=torch.float64), T)
+    if reversible:
+        pi = torch.where(empty, torch.ones_like(d), d)
+        pi = pi / pi.sum()
+        s = 1.0 / torch.sqrt(torch.where(empty, torch.ones_like(d), d))
+        sym = s[:, None] * m * s[None] + torch.diag(empty.to(torch.float64))
+        lam = torch.linalg.eigvalsh(0.5 * (sym + sym.transpose(0, 1))).flip(0)
+        lam = lam[torch.argsort(lam.abs(), descending=True, stable=True)]
+    else:
+        lam = torch.linalg.eigvals(T)
+        lam = lam[torch.argsort(lam.abs(), descending=True, stable=True)]
+        w, v = torch.linalg.eig(T.transpose(0, 1))
+        pi = v[:, torch.argmin((w - 1.0).abs())].real
+        pi = pi.abs() / pi.abs().sum()
+    return MarkovModel(int(counts.lags[lag_index]), n, idx, T, lam, pi, bool(reversible))
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -1758,3 +1758,166 @@ def project_features(x: torch.Tensor, mean: torch.Tensor, vectors: torch.Tensor)
         check(lib.mdnopca_project(ptr(x) if D else None, R, D, ptr(mean) if D else None, ptr(vectors) if D else None, k, ptr(out),
                                   stream_ptr(dev)), "mdnopca_project")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Markov state models (include/mdno_markov.h, csrc/markov.hip)
+MSM_MAX_STATES = 1024               # MDNO_MSM_MAX_STATES
+MSM_ROW_TILE = 64                   # MDNO_MSM_ROW_TILE: rows per workgroup of the assignment
+MSM_CENTRE_TILE = 64                # MDNO_MSM_CENTRE_TILE: centres per workgroup (the minimum runs over the tiles in order)
+MSM_FEATURE_PASS = 32               # MDNO_MSM_FEATURE_PASS
+MSM_ARGMAX_TILE = 64                # MDNO_MSM_ARGMAX_TILE: rows per workgroup of the k-centres argmax
+MSM_SUM_PARTIALS = 16               # MDNO_MSM_SUM_PARTIALS: partial sums per (state, feature) (fixes the order of the sums)
+MSM_SUM_FEATURES = 16               # MDNO_MSM_SUM_FEATURES
+MSM_SUM_STATES = 16                 # MDNO_MSM_SUM_STATES
+MSM_LDS_STATES = 64                 # MDNO_MSM_LDS_STATES: the largest n_states counted in LDS
+MSM_MAX_LAGS = MAX_LAGS             # MDNO_MSM_MAX_LAGS
+
+
+def _msm_matrix(t, what: str):
+    """(`t` as a contiguous device matrix [R, D] of f32 or f64 — anything else is converted to f32 —, its dtype code)."""
+    if not torch.is_tensor(t):
+        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise MdnoError(f"{what} is a CPU tensor: the Markov-model kernels run on the GPU only (no CPU fallback exists)")
+    if t.dim() != 2:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected rank 2")
+    if t.shape[1] >= 2 ** 31:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)}: D exceeds 2^31 - 1")
+    dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+    return (t if t.dtype == dtype else t.to(dtype)).contiguous(), 1 if dtype == torch.float64 else 0
+
+
+def _msm_states(k, what: str, low: int = 1) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not low <= k <= MSM_MAX_STATES:
+        raise MdnoError(f"{what} = {k!r}: expected an integer in {low} .. {MSM_MAX_STATES}")
+    return k
+
+
+def assign_features(x: torch.Tensor, centres: torch.Tensor, origin: Optional[torch.Tensor] = None, labels: bool = True,
+                    dist2: bool = True):
+    """x [R, D], centres [k, D] (device; both f32 or both f64), origin f64 [D] or None -> (label i32 [R], dist2 f64 [R]),
+    None for what was not asked for: the nearest centre of every row and the squared distance to it,
+    d2 = max(0, |x - o|^2 + |c - o|^2 - 2 (x - o).(c - o)) in fp64 with the inner products on the fp64 matrix pipe
+    (include/mdno_markov.h has the rule; mdnomsm_assign).  The lowest index wins a tie; a row with a NaN or Inf gets -1 and
+    NaN, a centre with one is never chosen; k = 0 gives -1 everywhere.  The bits of a row's result depend on that row, the
+    centres it is compared with, the origin and D alone.  Asynchronous on the current stream."""
+    x, code = _msm_matrix(x, "x")
+    centres, ccode = _msm_matrix(centres, "centres")
+    R, D = x.shape
+    k = centres.shape[0]
+    if ccode != code:
+        raise MdnoError(f"centres are {centres.dtype}, x is {x.dtype}: expected one element type")
+    if centres.shape[1] != D or centres.device != x.device:
+        raise MdnoError(f"centres have shape {tuple(centres.shape)} on {centres.device}: expected [k, {D}] on {x.device}")
+    if k > MSM_MAX_STATES:
+        raise MdnoError(f"centres has k = {k} rows: expected 0 .. {MSM_MAX_STATES}")
+    if origin is not None:
+        origin = _vector_f64(origin, "origin", D, x.device)
+    if not (labels or dist2):
+        raise MdnoError("assign_features: no output was asked for (labels and dist2 are both False)")
+    lib = _lib.load()
+    dev = x.device
+    out_l = torch.empty(R, dtype=torch.int32, device=dev) if labels else None
+    out_d = torch.empty(R, dtype=torch.float64, device=dev) if dist2 else None
+    if R == 0:
+        return out_l, out_d
+    nbytes = lib.mdnomsm_assign_workspace_bytes(R, k, D)
+    ws = _ws(nbytes, dev) if nbytes else None
+    check(lib.mdnomsm_assign(ptr(x) if D else None, R, D, code, ptr(centres) if k * D else None, k,
+                             ptr(origin) if origin is not None and D else None, ptr(out_l), ptr(out_d), ptr(ws), nbytes,
+                             stream_ptr(dev)), "mdnomsm_assign")
+    return out_l, out_d
+
+
+def kcenters(x: torch.Tensor, k: int, first: int = 0):
+    """x [R, D] (device, f32 or f64) -> (index i64 [k], radius f64 [k]): deterministic farthest-point seeding from row `first`
+    — centre i is the row farthest from the centres before it (the lowest row on a tie, rows with a NaN or Inf never),
+    radius[i] the covering radius before it was added, radius[0] = +inf (include/mdno_markov.h has the rule;
+    mdnomsm_kcenters).  All k rounds are enqueued on the current stream; nothing is read back."""
+    x, code = _msm_matrix(x, "x")
+    R, D = x.shape
+    k = _msm_states(k, "kcenters: k")
+    if k > R:
+        raise MdnoError(f"kcenters: k = {k} centres of {R} rows")
+    if isinstance(first, bool) or not isinstance(first, int) or not 0 <= first < R:
+        raise MdnoError(f"kcenters: first = {first!r}, expected an integer in 0 .. {R - 1}")
+    lib = _lib.load()
+    dev = x.device
+    index = torch.empty(k, dtype=torch.int64, device=dev)
+    radius = torch.empty(k, dtype=torch.float64, device=dev)
+    nbytes = lib.mdnomsm_kcenters_workspace_bytes(R, D)
+    ws = _ws(nbytes, dev)
+    check(lib.mdnomsm_kcenters(ptr(x) if D else None, R, D, code, k, first, ptr(index), ptr(radius), ptr(ws), nbytes,
+                               stream_ptr(dev)), "mdnomsm_kcenters")
+    return index, radius
+
+
+def centroid_sums(x: torch.Tensor, label: torch.Tensor, k: int):
+    """x [R, D] (device, f32 or f64), label i32 [R], k -> (sums f64 [k, D], counts i64 [k]): per state the sum of its rows
+    in a fixed order and their number; labels outside 0 .. k - 1 are skipped, an empty state is zeros
+    (mdnomsm_centroid_sums).  Asynchronous on the current stream."""
+    x, code = _msm_matrix(x, "x")
+    R, D = x.shape
+    k = _msm_states(k, "centroid_sums: k")
+    if not torch.is_tensor(label) or not label.is_cuda or label.device != x.device:
+        raise MdnoError("label is a CPU tensor or on another device than x: expected an int32 device tensor")
+    if label.dtype != torch.int32 or label.shape != (R,):
+        raise MdnoError(f"label is {label.dtype} {tuple(label.shape)}: expected int32 [{R}]")
+    label = label.contiguous()
+    lib = _lib.load()
+    dev = x.device
+    sums = torch.empty((k, D), dtype=torch.float64, device=dev)
+    counts = torch.empty(k, dtype=torch.int64, device=dev)
+    check(lib.mdnomsm_centroid_sums(ptr(x) if R * D else None, R, D, code, ptr(label) if R else None, k, ptr(sums) if D else None,
+                                    ptr(counts), stream_ptr(dev)), "mdnomsm_centroid_sums")
+    return sums, counts
+
+
+def check_msm_lags(lags, what: str = "transition_counts"):
+    """`lags` as a list of Python ints: 1 .. MAX_LAGS integers >= 1, or MdnoError.  Host only."""
+    if torch.is_tensor(lags):
+        lags = lags.detach().cpu().reshape(-1).tolist()
+    try:
+        lags = list(lags)
+        vals = [int(v) for v in lags]
+        same = all(v == w for v, w in zip(vals, lags))
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
+    if not same:
+        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
+    if not 1 <= len(vals) <= MSM_MAX_LAGS:
+        raise MdnoError(f"{what}: {len(vals)} lags, expected 1 .. {MSM_MAX_LAGS}")
+    for v in vals:
+        if not 1 <= v < 2 ** 31:
+            raise MdnoError(f"{what}: lag {v} is below 1 (or exceeds 2^31 - 1)")
+    return vals
+
+
+def transition_counts(label: torch.Tensor, n_states: int, lags, pooled: bool = False):
+    """label i32 [S, M] (device; [S] is one member), lags -> (counts i64 [L, M or 1, n, n], n_skipped i64 [L]): per lag and
+    member (or pooled over the members) the number of origins t with label[t] = from and label[t + lag] = to, sliding
+    window; a pair with a label outside 0 .. n - 1 is counted in n_skipped instead (mdnomsm_transition_counts).  Integer
+    counts: exact.  Asynchronous on the current stream."""
+    if not torch.is_tensor(label):
+        raise MdnoError(f"label must be a torch tensor, got {type(label).__name__}")
+    if not label.is_cuda:
+        raise MdnoError("label is a CPU tensor: the Markov-model kernels run on the GPU only (no CPU fallback exists)")
+    if label.dim() == 1:
+        label = label[:, None]
+    if label.dim() != 2 or label.dtype != torch.int32:
+        raise MdnoError(f"label is {label.dtype} {tuple(label.shape)}: expected int32 [S, M]")
+    S, M = label.shape
+    if S >= 2 ** 31 or M > 65535:
+        raise MdnoError(f"label has shape {tuple(label.shape)}: expected S < 2^31 and M <= 65535")
+    n = _msm_states(n_states, "transition_counts: n_states")
+    vals = check_msm_lags(lags)
+    label = label.contiguous()
+    lib = _lib.load()
+    dev = label.device
+    Mo = 1 if pooled else M
+    counts = torch.empty((len(vals), Mo, n, n), dtype=torch.int64, device=dev)
+    skipped = torch.empty(len(vals), dtype=torch.int64, device=dev)
+    check(lib.mdnomsm_transition_counts(ptr(label) if S * M else None, S, M, n, _lag_arg(vals), len(vals), int(bool(pooled)),
+                                        ptr(counts) if Mo else None, ptr(skipped), stream_ptr(dev)), "mdnomsm_transition_counts")
+    return counts, skipped

@@ -480,6 +480,13 @@ class RolloutEngine:
         from .forecast import superpose
         return superpose(self._observed(first_step, steps), reference)
 
+    def assign(self, discretization, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.Discretization.assign` of the produced frames of steps first_step .. first_step + steps - 1 (default:
+        all) -> `forecast.Assignment`, labels i32 and dist2 f64 [steps, M]: the state of every frame in a partition built
+        from the truth (`forecast.discretize`); the frames are read where they are, on the current stream after the
+        engine's enqueued steps (as `score`)."""
+        return discretization.assign(self._observed(first_step, steps))
+
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):
         """`forecast.covariance` of the produced frames (same range arguments as `score`) after their superposition onto
@@ -670,6 +677,13 @@ class GroupedRolloutEngine:
         `forecast.superpose(self.produced(first_step, steps), reference)`."""
         parts = [e.superpose(reference, first_step, steps) for e in self.engines]
         return torch.cat([a for a, _ in parts], dim=1), torch.cat([r for _, r in parts], dim=1)
+
+    def assign(self, discretization, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.assign` for every group on its own frames, joined along the member axis: a frame's label depends
+        on that frame and the discretization alone, so these are the bits of
+        `discretization.assign(self.produced(first_step, steps))` whatever the grouping."""
+        from .forecast import Assignment
+        return Assignment.cat([e.assign(discretization, first_step, steps) for e in self.engines])
 
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):

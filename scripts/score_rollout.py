@@ -18,11 +18,15 @@ essential dynamics (forecast.pca): the truth, superposed on its first frame, giv
 explained-variance ratios, per member the RMSIP of the member's own top-K subspace with the truth's and the total variation
 between the member's and the truth's PC1/PC2 histograms, both projected on the TRUTH's components; with `--tica LAG` also
 the leading implied timescales of the truth and of the pooled members (INTEGRATION.md "Does the run move along the right
-coordinates?" reads them).
+coordinates?" reads them).  With `--msm N_STATES LAG` (and `--pca K`) also a Markov state model (forecast.discretize,
+forecast.markov_model): the truth is cut into N_STATES states in its own TICA space (with `--tica`, else its PCA space), truth
+and members are assigned to the truth's centres, and printed per member are the total variation of the state populations
+against the truth's, the share of its frames outside the truth's covering radius and the leading implied timescales at LAG
+beside the truth's (INTEGRATION.md "Does the run hop between the right states?" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
-                                    [--pca 10] [--tica 10]
+                                    [--pca 10] [--tica 10] [--msm 100 10]
 """
 import argparse
 import json
@@ -63,9 +67,15 @@ def main() -> None:
                          "RMSIP with them and the total variation of the PC1/PC2 histograms")
     ap.add_argument("--tica", type=int, metavar="LAG", default=None,
                     help="with --pca: also the K leading implied timescales at this lag, of the truth and of the pooled members")
+    ap.add_argument("--msm", type=int, nargs=2, metavar=("N_STATES", "LAG"), default=None,
+                    help="with --pca: also a Markov state model: the truth is cut into N_STATES states in its TICA space (with "
+                         "--tica, else its PCA space); per member the total variation of the state populations, the share of "
+                         "frames outside the truth's covering radius and the leading implied timescales at LAG beside the truth's")
     a = ap.parse_args()
     if a.tica is not None and a.pca is None:
         ap.error("--tica needs --pca K")
+    if a.msm is not None and (a.pca is None or a.msm[0] < 1 or a.msm[1] < 1):
+        ap.error("--msm needs --pca K, N_STATES >= 1 and LAG >= 1")
     if a.msd is not None and len(a.msd) not in (0, 2):
         ap.error("--msd takes no values or R_MAX N_BINS")
 
@@ -192,6 +202,29 @@ def main() -> None:
             if bool(torch.isfinite(f_cov.sums).all()):
                 f_tica = fc.tica(f_cov, eng.covariance(reference, f_cov.mean, a.tica), K)
                 dist["tica_forecast_timescales"] = finite(f_tica.timescales().cpu())
+        if a.msm is not None:
+            n_states, lag = a.msm
+            comps = t_tica if a.tica is not None and 0 < a.tica < S - 1 else t_pc    # the truth's own slow (or principal) coordinates
+            disc = fc.discretize(truth, n_states, components=comps, reference=reference)
+            t_as, f_as = disc.assign(truth), eng.assign(disc)                        # labels [S], [S, M]
+            t_pop, f_pop = t_as.populations(n_states), f_as.populations(n_states)    # [n], [M, n]
+            t_counts = fc.transition_counts(t_as.labels, n_states, [lag])
+            f_counts = fc.transition_counts(f_as.labels, n_states, [lag]).cpu()
+            lead = 3
+
+            def timescales(counts, member=None):
+                try:
+                    ts = fc.markov_model(counts, member=member).timescales()[:lead]
+                except fc.MdnoError:                                                 # (no transition was counted)
+                    return []
+                return finite(ts)
+            dist.update({"msm_states": n_states, "msm_lag": lag, "msm_space": "tica" if comps is not t_pc else "pca",
+                         "msm_covering_radius": float(disc.radius),
+                         "msm_population_total_variation": finite((0.5 * (f_pop - t_pop[None]).abs().sum(1)).cpu()),
+                         "msm_fraction_outside_truth_radius": finite(f_as.outside(disc.radius).cpu()),
+                         "msm_truth_timescales": timescales(t_counts.cpu()),
+                         "msm_forecast_timescales": [timescales(f_counts, m) for m in range(M)],
+                         "msm_pairs_skipped": int(f_counts.n_skipped.sum())})
 
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,

@@ -259,6 +259,18 @@ MARKOV_SIGNATURES = {
     "mdnomsm_transition_counts": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
 }
 
+# include/mdno_internal.h (internal coordinates: pair distances, angle cosines and dihedral (cos, sin) per frame as a feature
+# matrix, and a per-column histogram of one; additive, no version number of its own): name -> (restype, argtypes), kept in
+# step with that header (tests/test_internal_host.py checks both ways).  The names start with mdnoic_, for the reason
+# mdnoens_ has (the header says so too).  `box`, `lo` and `hi` are HOST pointers to doubles.
+INTERNAL_DTYPES = {"float32": 0, "float64": 1}
+INTERNAL_FORMS = {"auto": 0, "lds": 1, "global": 2}
+INTERNAL_RADIANS = 1
+INTERNAL_SIGNATURES = {
+    "mdnoic_features": (_I, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P]),
+    "mdnoic_column_histogram": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -292,7 +304,7 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
             list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
-            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()):
+            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

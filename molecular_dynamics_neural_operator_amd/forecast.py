@@ -84,6 +84,17 @@ the transitions at a lag on the device and estimate the model on the host:
     msm = markov_model(counts)                                  # MarkovModel: active set, T, spectrum, stationary distribution
     msm.timescales(5), msm.chapman_kolmogorov(counts, 1)        # implied timescales in steps; T^2 against the lag-20 estimate
     msm.population_total_variation(markov_model(truth_counts))  # 0 = the truth's state weights, 1 = disjoint
+
+Internal coordinates.  Superposing onto one frame mixes the overall rotation into every coordinate once a structure leaves
+that frame's basin; pair distances and the cos / sin of (pseudo-)dihedrals do not depend on a reference frame at all
+(csrc/internal.hip: fp64 on the fp32 coordinates in a fixed order; include/mdno_internal.h has the rule), and they say
+whether the produced frames are physical chains:
+
+    ft = Featurizer.backbone(N, min_separation=3, stride=4)     # pseudo-bonds, strided pairs, pseudo-angles, pseudo-dihedrals
+    x = eng.internal_coordinates(ft)                            # f32 [S, M, D] = internal_coordinates(eng.frames(), ft, box=eng.box)
+    h = feature_histograms(x, *feature_ranges(truth_x), 32)     # FeatureHistograms: counts i64 [M, D, 34]
+    h.total_variation(truth_h), h.outside()                     # f64 [M, D]: per column against the truth; share outside its range
+    disc = discretize(truth, 100, components=tc, featurizer=ft) # states in internal coordinates: no reference frame
 """
 from __future__ import annotations
 
@@ -744,6 +755,202 @@ def histogram_total_variation(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# Internal coordinates (csrc/internal.hip, include/mdno_internal.h has the rule)
+def _index_array(a, width: int, n_atoms: Optional[int], what: str) -> torch.Tensor:
+    """A host index array as int32 [n, width], validated: integer dtype, shape, 0 <= index (< n_atoms)."""
+    if a is None:
+        return torch.zeros((0, width), dtype=torch.int32)
+    t = a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(a)
+    if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise MdnoError(f"{what}: indices are {t.dtype}, expected an integer array")
+    if t.numel() == 0:
+        return torch.zeros((0, width), dtype=torch.int32)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise MdnoError(f"{what} has shape {tuple(t.shape)}: expected [n, {width}]")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0:
+        raise MdnoError(f"{what}: index {lo} is negative")
+    if hi >= (2 ** 31 - 1 if n_atoms is None else n_atoms):
+        raise MdnoError(f"{what}: index {hi} is outside 0 .. {(2 ** 31 - 1 if n_atoms is None else n_atoms) - 1}")
+    return t.to(torch.int32).contiguous()
+
+
+@dataclass
+class Featurizer:
+    """Which internal coordinates make up a feature row: `pairs` i32 [P, 2] (distances), `triples` i32 [A, 3] (the angle at
+    the middle atom) and `quads` i32 [T, 4] (dihedrals, IUPAC sign), columns in that order, for frames of `n_atoms` atoms
+    (None: any frame that holds the largest index, `top`).  Built from host arrays by `Featurizer.of` and the constructors
+    below, which validate once on the host; `.to(device)` moves the index tensors.  `a + b` concatenates kind by kind."""
+    pairs: torch.Tensor
+    triples: torch.Tensor
+    quads: torch.Tensor
+    n_atoms: Optional[int] = None
+    top: int = -1
+
+    @staticmethod
+    def of(pairs=None, triples=None, quads=None, n_atoms: Optional[int] = None, device=None) -> "Featurizer":
+        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
+            raise MdnoError(f"Featurizer: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        arrays = [_index_array(a, w, n_atoms, what) for a, w, what in ((pairs, 2, "pairs"), (triples, 3, "triples"), (quads, 4, "quads"))]
+        top = max([int(t.max()) for t in arrays if t.numel()], default=-1)
+        f = Featurizer(arrays[0], arrays[1], arrays[2], n_atoms, top)
+        return f if device is None else f.to(device)
+
+    @staticmethod
+    def distances(pairs, n_atoms: Optional[int] = None) -> "Featurizer":
+        return Featurizer.of(pairs=pairs, n_atoms=n_atoms)
+
+    @staticmethod
+    def angles(triples, n_atoms: Optional[int] = None) -> "Featurizer":
+        return Featurizer.of(triples=triples, n_atoms=n_atoms)
+
+    @staticmethod
+    def dihedrals(quads, n_atoms: Optional[int] = None) -> "Featurizer":
+        return Featurizer.of(quads=quads, n_atoms=n_atoms)
+
+    @staticmethod
+    def backbone(n_atoms: int, min_separation: int = 3, stride: int = 1) -> "Featurizer":
+        """The usual feature set of a chain with one site per residue: the n - 1 consecutive pseudo-bonds, every pair
+        (i, j) of the atoms 0, stride, 2 stride, ... with j - i >= min_separation, the n - 2 pseudo-angles and the n - 3
+        pseudo-dihedrals."""
+        for name, v, low in (("n_atoms", n_atoms, 0), ("min_separation", min_separation, 1), ("stride", stride, 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < low:
+                raise MdnoError(f"Featurizer.backbone: {name} = {v!r}, expected an integer >= {low}")
+        n = n_atoms
+        idx = torch.arange(n, dtype=torch.int64)
+        bonds = torch.stack([idx[:-1], idx[1:]], 1) if n > 1 else torch.zeros((0, 2), dtype=torch.int64)
+        sub = idx[::stride]
+        i, j = torch.triu_indices(sub.numel(), sub.numel(), 1)
+        far = torch.stack([sub[i], sub[j]], 1)
+        far = far[far[:, 1] - far[:, 0] >= min_separation]
+        triples = torch.stack([idx[:-2], idx[1:-1], idx[2:]], 1) if n > 2 else None
+        quads = torch.stack([idx[:-3], idx[1:-2], idx[2:-1], idx[3:]], 1) if n > 3 else None
+        return Featurizer.of(torch.cat([bonds, far]), triples, quads, n_atoms=n)
+
+    def __add__(self, other: "Featurizer") -> "Featurizer":
+        if not isinstance(other, Featurizer):
+            return NotImplemented
+        if self.n_atoms is not None and other.n_atoms is not None and self.n_atoms != other.n_atoms:
+            raise MdnoError(f"Featurizer: n_atoms {self.n_atoms} + n_atoms {other.n_atoms}")
+        if self.pairs.device != other.pairs.device:
+            raise MdnoError(f"Featurizer: indices on {self.pairs.device} + indices on {other.pairs.device}")
+        return Featurizer(torch.cat([self.pairs, other.pairs]), torch.cat([self.triples, other.triples]),
+                          torch.cat([self.quads, other.quads]), self.n_atoms if self.n_atoms is not None else other.n_atoms,
+                          max(self.top, other.top))
+
+    @property
+    def n_bonds(self) -> int:
+        """How many of the leading distance columns are consecutive (i, i + 1) pairs — the pseudo-bonds of `backbone`."""
+        p = self.pairs.cpu()
+        run = (p[:, 1] - p[:, 0] == 1).to(torch.int64).cumprod(0) if p.shape[0] else p.new_zeros(0)
+        return int(run.sum())
+
+    def dim(self, radians: bool = False) -> int:
+        return int(self.pairs.shape[0] + self.triples.shape[0] + (1 if radians else 2) * self.quads.shape[0])
+
+    def names(self, radians: bool = False):
+        """One name per column: "d 3-17", "cos a 4-5-6", "cos t 1-2-3-4", "sin t 1-2-3-4" ("a ..." and "t ..." in radians)."""
+        join = lambda row: "-".join(str(int(v)) for v in row)
+        out = ["d " + join(r) for r in self.pairs.tolist()]
+        out += [("a " if radians else "cos a ") + join(r) for r in self.triples.tolist()]
+        for r in self.quads.tolist():
+            out += ["t " + join(r)] if radians else ["cos t " + join(r), "sin t " + join(r)]
+        return out
+
+    def to(self, device) -> "Featurizer":
+        return Featurizer(self.pairs.to(device), self.triples.to(device), self.quads.to(device), self.n_atoms, self.top)
+
+    def check_frames(self, n_atoms: int) -> None:
+        if (self.n_atoms is not None and n_atoms != self.n_atoms) or self.top >= n_atoms:
+            want = f"{self.n_atoms}" if self.n_atoms is not None else f"more than {self.top}"
+            raise MdnoError(f"the featurizer was built for frames of {want} atoms, these have {n_atoms}")
+
+
+def internal_coordinates(frames: torch.Tensor, featurizer: Featurizer, box=None, radians: bool = False,
+                         dtype=torch.float32) -> torch.Tensor:
+    """frames f32 [S, M, N, 3] (device; [F, N, 3] is a plain stack) -> features [S, M, D] ([F, D]) of `dtype`: the distances,
+    angle cosines and dihedral (cos, sin) the featurizer lists, in fp64 on the fp32 coordinates (include/mdno_internal.h has
+    the rule; ops.internal_features).  They do not depend on a reference frame, so they are what `covariance`, `tica`,
+    `kcenters` and `assign` should be fed for anything that unfolds, hinges or diffuses.  `radians`: angles and dihedrals as
+    one column each (what `free_energy` takes for a map of two torsions).  `box`: bond vectors by the minimum image.
+    Asynchronous on the current stream, nothing is read back; CPU tensors and bad arguments raise `MdnoError` before any
+    device work."""
+    if not isinstance(featurizer, Featurizer):
+        raise MdnoError(f"internal_coordinates: featurizer is a {type(featurizer).__name__}")
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise MdnoError("internal_coordinates: frames must be [S, M, N, 3] or [F, N, 3]")
+    featurizer.check_frames(int(frames.shape[-2]))
+    if not frames.is_cuda:
+        raise MdnoError("frames is a CPU tensor: the internal-coordinate kernels run on the GPU only (no CPU fallback exists)")
+    if featurizer.pairs.device != frames.device:
+        featurizer = featurizer.to(frames.device)
+    return ops.internal_features(frames, featurizer.pairs, featurizer.triples, featurizer.quads, box=box, radians=radians,
+                                 dtype=dtype)
+
+
+@dataclass
+class FeatureHistograms:
+    """Per-column histograms of a feature matrix (`feature_histograms`): `counts` i64 [M, D, bins + 2] for features
+    [S, M, D] ([D, bins + 2] for [F, D]) — bin 0 holds the values below lo, the last bin those at or above hi —, `n_nan`
+    i64 [M, D] the NaNs (counted in no bin), `lo` and `hi` the ranges as lists of floats (one entry: shared)."""
+    counts: torch.Tensor
+    n_nan: torch.Tensor
+    lo: Sequence[float]
+    hi: Sequence[float]
+
+    def distribution(self) -> torch.Tensor:
+        """counts / their sum per column, f64 (NaN for a column without a counted value)."""
+        return ForecastScore._ratio(self.counts, self.counts.sum(-1, keepdim=True).expand_as(self.counts))
+
+    def total_variation(self, other: "FeatureHistograms") -> torch.Tensor:
+        """Per column, 0.5 sum |p - q| over all bins + 2 bins: f64 [M, D] or [D]; the other's leading dimensions broadcast
+        (a run [M, D, .] against a truth [D, .])."""
+        if self.counts.shape[-2:] != other.counts.shape[-2:]:
+            raise MdnoError(f"total_variation: {tuple(self.counts.shape)} against {tuple(other.counts.shape)}")
+        return 0.5 * (self.distribution() - other.distribution()).abs().sum(-1)
+
+    def outside(self) -> torch.Tensor:
+        """The share of the counted values below lo or at or above hi, per column: f64 [M, D] or [D]."""
+        return ForecastScore._ratio(self.counts[..., 0] + self.counts[..., -1], self.counts.sum(-1))
+
+    def cpu(self) -> "FeatureHistograms":
+        return FeatureHistograms(self.counts.cpu(), self.n_nan.cpu(), self.lo, self.hi)
+
+
+def feature_ranges(features: torch.Tensor):
+    """(lo, hi) as lists of D floats: per column the smallest value and the next double above the largest (so that the
+    largest falls into the last regular bin), NaNs left out; a constant column gets [v - 0.5, v + 0.5).  One read-back."""
+    if not torch.is_tensor(features) or features.dim() not in (2, 3) or features.numel() == 0:
+        raise MdnoError("feature_ranges: features must be a non-empty [S, M, D] or [F, D]")
+    x = features.reshape(-1, features.shape[-1]).to(torch.float64)
+    lo = torch.nan_to_num(x, nan=float("inf")).min(0).values.cpu().tolist()
+    hi = torch.nan_to_num(x, nan=float("-inf")).max(0).values.cpu().tolist()
+    out_lo, out_hi = [], []
+    for l, h in zip(lo, hi):
+        if not (math.isfinite(l) and math.isfinite(h)):
+            raise MdnoError("feature_ranges: a column holds no finite value (or an infinite one)")
+        out_lo.append(l if h > l else l - 0.5)
+        out_hi.append(math.nextafter(h, math.inf) if h > l else l + 0.5)
+    return out_lo, out_hi
+
+
+def feature_histograms(features: torch.Tensor, lo, hi, bins: int = 50) -> FeatureHistograms:
+    """features [S, M, D] or [F, D] (device, f32 or f64) -> `FeatureHistograms` over `bins` equal bins of [lo, hi) per column
+    (lo, hi: a number each, or D numbers — `feature_ranges` of the truth), per member for [S, M, D]; counted on the device
+    with integer atomics (ops.column_histogram), nothing read back."""
+    if not torch.is_tensor(features) or features.dim() not in (2, 3):
+        raise MdnoError("feature_histograms: features must be [S, M, D] or [F, D]")
+    D = features.shape[-1]
+    lo, hi, bins = ops.check_column_ranges(lo, hi, bins, D)
+    members = features.shape[1] if features.dim() == 3 else 1
+    if members == 0:
+        raise MdnoError("feature_histograms: features has no member")
+    counts, n_nan = ops.column_histogram(features.reshape(features.shape[0], members * D), lo, hi, bins, groups=members)
+    lead = (members, D) if features.dim() == 3 else (D,)
+    return FeatureHistograms(counts.reshape(lead + (bins + 2,)), n_nan.reshape(lead), lo, hi)
+
+
+# ------------------------------------------------------------------------------------------------
 # Markov state models (csrc/markov.hip, include/mdno_markov.h has the rules)
 @dataclass
 class Assignment:
@@ -862,18 +1069,30 @@ def kmeans(X: torch.Tensor, k: int, iters: int = 10, init: Optional[torch.Tensor
 class Discretization:
     """A partition of conformation space into states (`discretize`): frames are superposed onto `reference` f32 [N, 3],
     projected onto `components` (if any) and assigned to the nearest of `centres` [k, D]; `radius` (an f64 scalar on the
-    device) is the covering radius of the frames it was built from: the largest distance of one of them to its centre."""
-    reference: torch.Tensor
+    device) is the covering radius of the frames it was built from: the largest distance of one of them to its centre.
+    With a `featurizer` the frames are not superposed at all: their internal coordinates (`internal_coordinates`, under
+    `box`) take the place of the superposed Cartesians, and `reference` is None."""
+    reference: Optional[torch.Tensor]
     components: Optional[Components]
     centres: torch.Tensor
     radius: torch.Tensor
+    featurizer: Optional[Featurizer] = None
+    box: Optional[Tuple[float, float, float]] = None
 
     @property
     def n_states(self) -> int:
         return int(self.centres.shape[0])
 
     def features(self, frames: torch.Tensor):
-        """(rows [S M, D], leading shape) of frames f32 [S, M, N, 3] or [F, N, 3]: superposed, then projected."""
+        """(rows [S M, D], leading shape) of frames f32 [S, M, N, 3] or [F, N, 3]: superposed (or, with a featurizer, turned
+        into internal coordinates), then projected."""
+        if self.featurizer is not None:
+            X = internal_coordinates(frames, self.featurizer, box=self.box)
+            lead = tuple(X.shape[:-1])
+            X = X.reshape(-1, X.shape[-1])
+            if self.components is not None:                       # (not `project`: it would take three columns for frames)
+                X = ops.project_features(X, self.components.mean, self.components.vectors)
+            return X, lead
         aligned, _ = superpose(frames, self.reference)
         lead = tuple(frames.shape[:-2])
         if self.components is None:
@@ -889,18 +1108,27 @@ class Discretization:
 
 
 def discretize(truth: torch.Tensor, n_states: int, components: Optional[Components] = None, method: str = "kcenters",
-               iters: int = 10, reference: Optional[torch.Tensor] = None) -> Discretization:
+               iters: int = 10, reference: Optional[torch.Tensor] = None, featurizer: Optional[Featurizer] = None,
+               box=None) -> Discretization:
     """Cut the space the frames of `truth` (f32 [S, M, N, 3] or [F, N, 3]) visit into `n_states` states: superposed onto
     `reference` (by default the first frame), projected onto `components` if given (pca / tica of the same superposed
     frames), then clustered by "kcenters" (farthest-point: even coverage, the covering radius is minimised greedily) or
-    "kmeans" (`iters` Lloyd rounds from that seeding)."""
+    "kmeans" (`iters` Lloyd rounds from that seeding).  With a `featurizer` the frames' internal coordinates (under `box`)
+    take the place of the superposed Cartesians — no reference frame is involved, and `components` are then those of the
+    internal coordinates; without one nothing changes."""
     if method not in ("kcenters", "kmeans"):
         raise MdnoError(f"discretize: method = {method!r}, expected 'kcenters' or 'kmeans'")
     if not torch.is_tensor(truth) or truth.dim() not in (3, 4) or truth.shape[-1] != 3:
         raise MdnoError("discretize: truth must be frames [S, M, N, 3] or [F, N, 3]")
-    if reference is None:
+    if featurizer is not None:
+        if reference is not None:
+            raise MdnoError("discretize: a featurizer and a reference frame were both given (internal coordinates need none)")
+        box = ops.check_box(box, 0.0)
+    elif box is not None:
+        raise MdnoError("discretize: box is only used with a featurizer")
+    elif reference is None:
         reference = truth.reshape(-1, truth.shape[-2], 3)[0].contiguous() if truth.numel() else truth.new_zeros(truth.shape[-2], 3)
-    d = Discretization(reference, components, truth.new_zeros(0, 0), torch.zeros((), dtype=torch.float64))
+    d = Discretization(reference, components, truth.new_zeros(0, 0), torch.zeros((), dtype=torch.float64), featurizer, box)
     rows, _ = d.features(truth)
     if method == "kcenters":
         centres = kcenters(rows, n_states)[0]
@@ -908,7 +1136,7 @@ def discretize(truth: torch.Tensor, n_states: int, components: Optional[Componen
     else:
         centres, fit, _ = kmeans(rows, n_states, iters)
     worst = torch.nan_to_num(fit.dist2.reshape(-1), nan=0.0).max() if rows.shape[0] else torch.zeros((), dtype=torch.float64, device=rows.device)
-    return Discretization(reference, components, centres, torch.sqrt(worst))
+    return Discretization(reference, components, centres, torch.sqrt(worst), featurizer, box)
 
 
 @dataclass

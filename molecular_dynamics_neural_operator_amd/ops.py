@@ -1921,3 +1921,119 @@ def transition_counts(label: torch.Tensor, n_states: int, lags, pooled: bool = F
     check(lib.mdnomsm_transition_counts(ptr(label) if S * M else None, S, M, n, _lag_arg(vals), len(vals), int(bool(pooled)),
                                         ptr(counts) if Mo else None, ptr(skipped), stream_ptr(dev)), "mdnomsm_transition_counts")
     return counts, skipped
+
+
+# ------------------------------------------------------------------------------------------------
+# Internal coordinates (include/mdno_internal.h, csrc/internal.hip)
+IC_WORKGROUP = 256                  # MDNO_IC_WORKGROUP: threads of a workgroup
+IC_LDS_ATOMS = 2048                 # MDNO_IC_LDS_ATOMS: the largest N whose frames are staged in LDS
+IC_MAX_GROUP_FRAMES = 16            # MDNO_IC_MAX_GROUP_FRAMES
+IC_FEATURE_CHUNK = 8192             # MDNO_IC_FEATURE_CHUNK: index tuples of a frame one workgroup owns
+IC_MAX_BINS = 4096                  # MDNO_IC_MAX_BINS
+IC_HIST_ROWS = 4096                 # MDNO_IC_HIST_ROWS: rows a workgroup of the column histogram counts
+IC_HIST_TABLE = 8192                # MDNO_IC_HIST_TABLE: counters of its LDS table
+IC_HIST_COLUMNS = 128               # MDNO_IC_HIST_COLUMNS: columns whose ranges one launch carries
+IC_FORMS = _lib.INTERNAL_FORMS
+
+
+def ic_frames_per_group(n_atoms: int) -> int:
+    """MDNO_IC_FRAMES_PER_GROUP(N): the frames one workgroup of mdnoic_features owns."""
+    if n_atoms <= 0 or IC_LDS_ATOMS // n_atoms < 1:
+        return 1
+    return min(IC_LDS_ATOMS // n_atoms, IC_MAX_GROUP_FRAMES)
+
+
+def _ic_indices(t, width: int, what: str, dev) -> torch.Tensor:
+    """An index array as contiguous int32 [n, width] on `dev` (None: no entries)."""
+    if t is None:
+        return torch.zeros((0, width), dtype=torch.int32, device=dev)
+    if not torch.is_tensor(t):
+        raise MdnoError(f"{what} must be a torch tensor or None, got {type(t).__name__}")
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != width:
+        raise MdnoError(f"{what} is {t.dtype} {tuple(t.shape)}: expected int32 [n, {width}]")
+    if t.device != dev:
+        raise MdnoError(f"{what} is on {t.device}, the frames are on {dev}")
+    if t.shape[0] >= 2 ** 31:
+        raise MdnoError(f"{what} has {t.shape[0]} rows: more than 2^31 - 1")
+    return t.to(torch.int32).contiguous()
+
+
+def internal_features(frames: torch.Tensor, pairs=None, triples=None, quads=None, box=None, radians: bool = False,
+                      dtype=torch.float32, form: str = "auto") -> torch.Tensor:
+    """frames f32 [..., N, 3] and device index arrays pairs i32 [P, 2], triples [A, 3], quads [T, 4] (None: none) ->
+    out [..., D] of `dtype` (f32 or f64), D = P + A + 2 T: the distances, the cosines of the angles at the middle atom, then
+    (cos, sin) of every dihedral (IUPAC sign), in fp64 on the fp32 coordinates by the rule of include/mdno_internal.h
+    (mdnoic_features).  `radians`: angles and dihedrals as one column each, D = P + A + T.  `box` = (Lx, Ly, Lz), 0 for an
+    open axis: bond vectors by the minimum image (no cutoff is tested).  An index outside 0 .. N - 1 gives NaN and reads
+    nothing.  `form`: "auto" (frames staged in LDS up to IC_LDS_ATOMS atoms), "lds" or "global" to force one (the same
+    bits).  Asynchronous on the current stream, nothing is read back."""
+    if form not in IC_FORMS:
+        raise MdnoError(f"form {form!r}: expected one of {sorted(IC_FORMS)}")
+    if dtype not in (torch.float32, torch.float64):
+        raise MdnoError(f"dtype {dtype}: expected torch.float32 or torch.float64")
+    box = check_box(box, 0.0)
+    frames, lead, F, N = _flat_frames(frames)
+    if form == "lds" and N > IC_LDS_ATOMS:
+        raise MdnoError(f"form 'lds' holds frames of at most {IC_LDS_ATOMS} atoms, N = {N}")
+    dev = frames.device
+    pairs, triples, quads = (_ic_indices(t, w, n, dev) for t, w, n in ((pairs, 2, "pairs"), (triples, 3, "triples"), (quads, 4, "quads")))
+    P, A, T = pairs.shape[0], triples.shape[0], quads.shape[0]
+    D = P + A + (1 if radians else 2) * T
+    if D >= 2 ** 31:
+        raise MdnoError(f"{D} feature columns: more than 2^31 - 1")
+    lib = _lib.load()
+    out = torch.empty(lead + (D,), dtype=dtype, device=dev)
+    check(lib.mdnoic_features(ptr(frames) if F * N else None, F, N, ptr(pairs) if P else None, P, ptr(triples) if A else None, A,
+                              ptr(quads) if T else None, T, box_arg(box) if box else None, _lib.INTERNAL_RADIANS if radians else 0,
+                              _lib.INTERNAL_DTYPES[str(dtype).split(".")[-1]], ptr(out) if F * D else None, IC_FORMS[form],
+                              stream_ptr(dev)), "mdnoic_features")
+    return out
+
+
+def check_column_ranges(lo, hi, n_bins, D: int):
+    """(lo, hi as lists of Python floats — one entry: a range shared by all columns, else D —, n_bins as int) for a column
+    histogram, or MdnoError: finite, hi > lo, n_bins in 1 .. IC_MAX_BINS.  Host only."""
+    import math
+    if isinstance(n_bins, bool) or not isinstance(n_bins, int) or not 1 <= n_bins <= IC_MAX_BINS:
+        raise MdnoError(f"column_histogram: n_bins={n_bins!r} is outside 1 .. {IC_MAX_BINS}")
+    vals = []
+    for name, v in (("lo", lo), ("hi", hi)):
+        if torch.is_tensor(v):
+            v = v.detach().cpu().reshape(-1).tolist()
+        try:
+            v = [float(e) for e in v] if hasattr(v, "__len__") or hasattr(v, "__iter__") else [float(v)]
+        except (TypeError, ValueError):
+            raise MdnoError(f"column_histogram: {name}={v!r}: expected a number or {D} numbers") from None
+        vals.append(v)
+    lo, hi = vals
+    if len(lo) != len(hi) or len(lo) not in (1, D):
+        raise MdnoError(f"column_histogram: {len(lo)} lower and {len(hi)} upper bounds for {D} columns: expected 1 or {D} of each")
+    for a, (l, h) in enumerate(zip(lo, hi)):
+        if not (math.isfinite(l) and math.isfinite(h) and h > l and math.isfinite(h - l)):
+            raise MdnoError(f"column_histogram: range [{l}, {h}) of column {a} is not finite or is empty")
+    return lo, hi, n_bins
+
+
+def column_histogram(x: torch.Tensor, lo, hi, n_bins: int, groups: int = 1):
+    """x [R, D] (device, f32 or f64), lo and hi (a number each, or D numbers: host values) -> (counts i64 [D, n_bins + 2],
+    n_nan i64 [D]): per column the histogram of its values over n_bins equal bins of [lo, hi); counts[:, 0] holds the values
+    below lo, counts[:, -1] those at or above hi, a NaN is counted in n_nan alone, so counts.sum(1) + n_nan == R
+    (include/mdno_internal.h has the rule; mdnoic_column_histogram).  `groups` = G: x is [R, G D], G groups of D columns
+    that share the D ranges (the members of a feature tensor [S, M, D]); counts [G D, n_bins + 2], n_nan [G D].  Integer
+    counts: exact.  Asynchronous on the current stream."""
+    x, code = _msm_matrix(x, "x")
+    R, width = x.shape
+    if isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups <= 65535 or width % groups:
+        raise MdnoError(f"column_histogram: groups={groups!r} for {width} columns: expected 1 .. 65535 groups of equally many columns")
+    D = width // groups
+    lo, hi, n_bins = check_column_ranges(lo, hi, n_bins, D)
+    lib = _lib.load()
+    dev = x.device
+    counts = torch.empty((width, n_bins + 2), dtype=torch.int64, device=dev)
+    n_nan = torch.empty(width, dtype=torch.int64, device=dev)
+    if D == 0:
+        return counts, n_nan
+    lo_arg, hi_arg = (C.c_double * len(lo))(*lo), (C.c_double * len(hi))(*hi)
+    check(lib.mdnoic_column_histogram(ptr(x) if R else None, R, D, groups, code, lo_arg, hi_arg, int(len(lo) == 1),
+                                      n_bins, ptr(counts), ptr(n_nan), stream_ptr(dev)), "mdnoic_column_histogram")
+    return counts, n_nan

@@ -487,6 +487,15 @@ class RolloutEngine:
         engine's enqueued steps (as `score`)."""
         return discretization.assign(self._observed(first_step, steps))
 
+    def internal_coordinates(self, featurizer, radians: bool = False, dtype=torch.float32, first_step: int = 0,
+                             steps: Optional[int] = None) -> torch.Tensor:
+        """`forecast.internal_coordinates` of the produced frames of steps first_step .. first_step + steps - 1 (default:
+        all) in the engine's own box -> features [steps, M, D]: distances, angle cosines and dihedral (cos, sin) that do not
+        depend on a reference frame; the frames are read where they are, on the current stream after the engine's enqueued
+        steps (as `score`)."""
+        from .forecast import internal_coordinates
+        return internal_coordinates(self._observed(first_step, steps), featurizer, box=self.box, radians=radians, dtype=dtype)
+
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):
         """`forecast.covariance` of the produced frames (same range arguments as `score`) after their superposition onto
@@ -684,6 +693,13 @@ class GroupedRolloutEngine:
         `discretization.assign(self.produced(first_step, steps))` whatever the grouping."""
         from .forecast import Assignment
         return Assignment.cat([e.assign(discretization, first_step, steps) for e in self.engines])
+
+    def internal_coordinates(self, featurizer, radians: bool = False, dtype=torch.float32, first_step: int = 0,
+                             steps: Optional[int] = None) -> torch.Tensor:
+        """`RolloutEngine.internal_coordinates` for every group on its own frames, joined along the member axis: a frame's
+        row depends on that frame alone, so these are the bits of
+        `forecast.internal_coordinates(self.produced(first_step, steps), featurizer, box=self.box)`."""
+        return torch.cat([e.internal_coordinates(featurizer, radians, dtype, first_step, steps) for e in self.engines], dim=1)
 
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):

@@ -22,11 +22,16 @@ coordinates?" reads them).  With `--msm N_STATES LAG` (and `--pca K`) also a Mar
 forecast.markov_model): the truth is cut into N_STATES states in its own TICA space (with `--tica`, else its PCA space), truth
 and members are assigned to the truth's centres, and printed per member are the total variation of the state populations
 against the truth's, the share of its frames outside the truth's covering radius and the leading implied timescales at LAG
-beside the truth's (INTEGRATION.md "Does the run hop between the right states?" reads them).
+beside the truth's (INTEGRATION.md "Does the run hop between the right states?" reads them).  With `--internal [MIN_SEP STRIDE]`
+also the internal coordinates (forecast.Featurizer.backbone(atoms, MIN_SEP, STRIDE), default 3 4: pseudo-bonds, the pairs of
+every STRIDE-th atom at least MIN_SEP apart, pseudo-angles and pseudo-dihedrals): per member the largest and the median
+per-column total variation of its feature histograms against the truth's over the truth's own ranges, and the share of its
+bond lengths outside the truth's range; `--pca`, `--tica` and `--msm` then work on these features instead of the superposed
+Cartesian coordinates (INTEGRATION.md "Features that do not depend on a reference frame" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
-                                    [--pca 10] [--tica 10] [--msm 100 10]
+                                    [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4]
 """
 import argparse
 import json
@@ -71,7 +76,13 @@ def main() -> None:
                     help="with --pca: also a Markov state model: the truth is cut into N_STATES states in its TICA space (with "
                          "--tica, else its PCA space); per member the total variation of the state populations, the share of "
                          "frames outside the truth's covering radius and the leading implied timescales at LAG beside the truth's")
+    ap.add_argument("--internal", type=int, nargs="*", metavar="MIN_SEP STRIDE", default=None,
+                    help="also score the internal coordinates of the backbone feature set (default 3 4): per member the largest "
+                         "and median per-column total variation of the feature histograms against the truth's and the share of "
+                         "bond lengths outside the truth's range; --pca/--tica/--msm then run on these features")
     a = ap.parse_args()
+    if a.internal is not None and (len(a.internal) not in (0, 2) or any(v < 1 for v in a.internal)):
+        ap.error("--internal takes no values or MIN_SEP STRIDE, both >= 1")
     if a.tica is not None and a.pca is None:
         ap.error("--tica needs --pca K")
     if a.msm is not None and (a.pca is None or a.msm[0] < 1 or a.msm[1] < 1):
@@ -172,14 +183,34 @@ def main() -> None:
                      "coverage": finite(cr.coverage(a.coverage).cpu()),
                      "nearest_true_frame_rmsd_median": finite(cr.nearest.nanmedian(0).values.cpu())})
 
+    internal = None
+    if a.internal is not None and S > 0:
+        from molecular_dynamics_neural_operator_amd import forecast as fc
+        min_sep, stride = a.internal or (3, 4)
+        ft = fc.Featurizer.backbone(N, min_sep, stride).to(dev)
+        t_feat = fc.internal_coordinates(truth, ft, box=eng.box)                     # [S, D]
+        f_feat = eng.internal_coordinates(ft)                                        # [S, M, D]
+        lo, hi = fc.feature_ranges(t_feat)                                           # the truth's own range per column
+        ic_bins, nb = 32, ft.n_bonds
+        tv = fc.feature_histograms(f_feat, lo, hi, ic_bins).total_variation(fc.feature_histograms(t_feat, lo, hi, ic_bins))
+        bonds = fc.feature_histograms(f_feat[..., :nb].contiguous(), min(lo[:nb]), max(hi[:nb]), 1) if nb else None
+        dist.update({"internal_min_separation": min_sep, "internal_stride": stride, "internal_features": ft.dim(),
+                     "internal_bins": ic_bins, "internal_total_variation_max": finite(tv.max(1).values.cpu()),
+                     "internal_total_variation_median": finite(tv.nanmedian(1).values.cpu()),
+                     "internal_bond_fraction_outside_truth_range": finite(bonds.outside().mean(1).cpu()) if nb else []})
+        internal = (ft, t_feat[:, None].contiguous(), f_feat)
+
     if a.pca is not None and S > 2:
         from molecular_dynamics_neural_operator_amd import forecast as fc
         K, bins = a.pca, 32
         reference = truth[0].contiguous()
-        t_al = fc.superpose(truth, reference)[0]                                     # [S, 1, N, 3]
+        if internal is not None:                                                     # rows of internal coordinates, no reference
+            t_al, f_al = internal[1], internal[2]                                    # [S, 1, D], [S, M, D]
+        else:
+            t_al = fc.superpose(truth, reference)[0]                                 # [S, 1, N, 3]
+            f_al = eng.superpose(reference)[0]                                       # [S, M, N, 3]
         t_cov = fc.covariance(t_al)
         t_pc = fc.pca(t_cov, K)
-        f_al = eng.superpose(reference)[0]                                           # [S, M, N, 3]
         t_proj, f_proj = fc.project(t_al, t_pc), fc.project(f_al, t_pc)              # [S, 1, K], [S, M, K]
         lo = torch.minimum(t_proj.amin((0, 1)), f_proj.nan_to_num(posinf=0.0, neginf=0.0).amin((0, 1))).cpu()
         hi = torch.maximum(t_proj.amax((0, 1)), f_proj.nan_to_num(posinf=0.0, neginf=0.0).amax((0, 1))).cpu()
@@ -194,18 +225,22 @@ def main() -> None:
             tv.append(float(fc.histogram_total_variation(fc.free_energy(f_proj[:, m], 0, j, bins, rng)[1], t_hist)))
         dist.update({"pca_k": K, "pca_truth_explained_ratio": finite(t_pc.explained_ratio().cpu()),
                      "pca_rmsip_with_truth": finite(np.asarray(rmsip)), "pca_pc12_total_variation": finite(np.asarray(tv)),
-                     "pca_truth_rmsf_mean": float(t_cov.rmsf().mean())})
+                     **({"pca_space": "internal"} if internal is not None else {"pca_truth_rmsf_mean": float(t_cov.rmsf().mean())})})
         if a.tica is not None and 0 < a.tica < S - 1:
             t_tica = fc.tica(t_cov, fc.covariance(t_al, t_cov.mean, a.tica), K)
-            f_cov = eng.covariance(reference)
+            f_cov = fc.covariance(f_al) if internal is not None else eng.covariance(reference)
             dist.update({"tica_lag": a.tica, "tica_truth_timescales": finite(t_tica.timescales().cpu())})
             if bool(torch.isfinite(f_cov.sums).all()):
-                f_tica = fc.tica(f_cov, eng.covariance(reference, f_cov.mean, a.tica), K)
+                f_lag = fc.covariance(f_al, f_cov.mean, a.tica) if internal is not None else eng.covariance(reference, f_cov.mean, a.tica)
+                f_tica = fc.tica(f_cov, f_lag, K)
                 dist["tica_forecast_timescales"] = finite(f_tica.timescales().cpu())
         if a.msm is not None:
             n_states, lag = a.msm
             comps = t_tica if a.tica is not None and 0 < a.tica < S - 1 else t_pc    # the truth's own slow (or principal) coordinates
-            disc = fc.discretize(truth, n_states, components=comps, reference=reference)
+            if internal is not None:
+                disc = fc.discretize(truth, n_states, components=comps, featurizer=internal[0], box=eng.box)
+            else:
+                disc = fc.discretize(truth, n_states, components=comps, reference=reference)
             t_as, f_as = disc.assign(truth), eng.assign(disc)                        # labels [S], [S, M]
             t_pop, f_pop = t_as.populations(n_states), f_as.populations(n_states)    # [n], [M, n]
             t_counts = fc.transition_counts(t_as.labels, n_states, [lag])
@@ -218,7 +253,7 @@ def main() -> None:
                 except fc.MdnoError:                                                 # (no transition was counted)
                     return []
                 return finite(ts)
-            dist.update({"msm_states": n_states, "msm_lag": lag, "msm_space": "tica" if comps is not t_pc else "pca",
+            dist.update({"msm_states": n_states, "msm_lag": lag, "msm_space": ("internal " if internal is not None else "") + ("tica" if comps is not t_pc else "pca"),
                          "msm_covering_radius": float(disc.radius),
                          "msm_population_total_variation": finite((0.5 * (f_pop - t_pop[None]).abs().sum(1)).cpu()),
                          "msm_fraction_outside_truth_radius": finite(f_as.outside(disc.radius).cpu()),

@@ -271,6 +271,16 @@ INTERNAL_SIGNATURES = {
     "mdnoic_column_histogram": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
+# include/mdno_internal_grad.h (the adjoint of mdnoic_features in its default mode: the gradient with respect to the features
+# -> the gradient with respect to the positions; additive, no version number of its own): name -> (restype, argtypes), kept
+# in step with that header (tests/test_internal_grad_host.py checks both ways).  The name starts with mdnoicg_, because
+# tests/test_internal_host.py holds the mdnoic_ exports to the table above (the header says so too).  `box` is a HOST
+# pointer to doubles; the element types and forms are INTERNAL_DTYPES and INTERNAL_FORMS.
+INTERNAL_GRAD_MAX_ITEMS = 1 << 29
+INTERNAL_GRAD_SIGNATURES = {
+    "mdnoicg_features_bwd": (_I, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P, _I, _P, _I, _P, _I, _I, _P]),
+}
+
 _lib = None
 
 
@@ -304,7 +314,8 @@ def load() -> C.CDLL:
     for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
             list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
-            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
+            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + \
+            list(INTERNAL_GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

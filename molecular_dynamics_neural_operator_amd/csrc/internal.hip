@@ -20,6 +20,7 @@
 // random in any: no padding helps a gather whose addresses the caller chooses.  So the image is the one that costs
 // nothing to build.  24 KiB per workgroup at most: six workgroups fit a CU's 160 KiB beside their registers.
 #include "common.h"
+#include "internal_rule.h"
 #include "pbc.h"
 #include "../../include/mdno_internal.h"
 
@@ -42,22 +43,7 @@ typedef unsigned long long u64;
 
 __device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7ff8000000000000ll); }
 __device__ __forceinline__ double clamp1(double c) { return c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c); }
-__device__ __forceinline__ double dot3(const double p[3], const double q[3]) { return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2]; }
-__device__ __forceinline__ void cross3(const double p[3], const double q[3], double r[3]) {
-    r[0] = p[1] * q[2] - p[2] * q[1];
-    r[1] = p[2] * q[0] - p[0] * q[2];
-    r[2] = p[0] * q[1] - p[1] * q[0];
-}
-// v(a->b) under the box; x = the frame's coordinates (LDS or global), a and b inside 0 .. N - 1
-__device__ __forceinline__ void bond(const float* x, int a, int b, const PbcBox& box, double v[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double d = (double)x[3 * b + c] - (double)x[3 * a + c];
-        if (box.L[c] > 0.0) d = d - rint(d * box.inv[c]) * box.L[c];
-        v[c] = d;
-    }
-}
-__device__ __forceinline__ bool inside(int a, int N) { return (unsigned)a < (unsigned)N; }
+// (dot3, cross3, bond and inside are internal_rule.h's: the backward kernel forms the same vectors from them)
 
 // One item of one frame: r[0] (and r[1] for a dihedral outside radians mode).  `it` counts pairs, then triples, then quads.
 __device__ __forceinline__ void ic_item(const float* x, int N, int it, const int* __restrict__ pairs, int P,

@@ -99,7 +99,7 @@ whether the produced frames are physical chains:
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -786,6 +786,7 @@ class Featurizer:
     quads: torch.Tensor
     n_atoms: Optional[int] = None
     top: int = -1
+    _incidence: dict = field(default_factory=dict, init=False, repr=False, compare=False)    # (n_atoms, device) -> table
 
     @staticmethod
     def of(pairs=None, triples=None, quads=None, n_atoms: Optional[int] = None, device=None) -> "Featurizer":
@@ -860,10 +861,65 @@ class Featurizer:
     def to(self, device) -> "Featurizer":
         return Featurizer(self.pairs.to(device), self.triples.to(device), self.quads.to(device), self.n_atoms, self.top)
 
+    def incidence(self, n_atoms: int, device=None):
+        """The incidence table the backward kernel walks (include/mdno_internal_grad.h): (atom_ptr i32 [n_atoms + 1],
+        inc i32 [n_inc]) on `device` (None: where the indices are), a CSR by atom with inc[e] = item * 4 + slot, items
+        counting the pairs, then the triples, then the quads, slot = the position in the tuple.  Built on the host: the
+        tuples flattened in (item, slot) order, stably sorted by atom (so an atom's entries ascend; a tuple that names an
+        atom twice gives it two), entries whose atom is >= n_atoms dropped.  Cached per (n_atoms, device) on this instance;
+        `.to` and `+` make instances without a cache."""
+        if isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0:
+            raise MdnoError(f"Featurizer.incidence: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        device = self.pairs.device if device is None else torch.device(device)
+        key = (n_atoms, str(device))
+        hit = self._incidence.get(key)
+        if hit is not None:
+            return hit
+        items = self.pairs.shape[0] + self.triples.shape[0] + self.quads.shape[0]
+        if items >= ops.ICG_MAX_ITEMS:
+            raise MdnoError(f"Featurizer.incidence: {items} index tuples, the table holds fewer than 2^29")
+        atoms, codes, first = [], [], 0
+        for t in (self.pairs, self.triples, self.quads):
+            n, w = t.shape
+            atoms.append(t.detach().cpu().to(torch.int64).reshape(-1))
+            codes.append(((first + torch.arange(n, dtype=torch.int64))[:, None] * 4 + torch.arange(w, dtype=torch.int64)[None, :]).reshape(-1))
+            first += n
+        atoms, codes = torch.cat(atoms), torch.cat(codes)
+        keep = (atoms >= 0) & (atoms < n_atoms)
+        atoms, codes = atoms[keep], codes[keep]
+        order = torch.sort(atoms, stable=True).indices
+        atom_ptr = torch.zeros(n_atoms + 1, dtype=torch.int64)
+        atom_ptr[1:] = torch.cumsum(torch.bincount(atoms, minlength=n_atoms), 0)
+        table = (atom_ptr.to(torch.int32).to(device), codes[order].to(torch.int32).to(device))
+        self._incidence[key] = table
+        return table
+
     def check_frames(self, n_atoms: int) -> None:
         if (self.n_atoms is not None and n_atoms != self.n_atoms) or self.top >= n_atoms:
             want = f"{self.n_atoms}" if self.n_atoms is not None else f"more than {self.top}"
             raise MdnoError(f"the featurizer was built for frames of {want} atoms, these have {n_atoms}")
+
+
+class _InternalCoordinatesFn(torch.autograd.Function):
+    """internal_coordinates under autograd: the forward is the ops.internal_features call it always was (the same bits), the
+    backward one mdnoicg_features_bwd launch (include/mdno_internal_grad.h) over the featurizer's incidence table."""
+
+    @staticmethod
+    def forward(ctx, frames, featurizer, owner, box, dtype):
+        ctx.save_for_backward(frames)
+        ctx.featurizer, ctx.owner, ctx.box = featurizer, owner, box          # owner: the caller's instance, which keeps the table
+        return ops.internal_features(frames, featurizer.pairs, featurizer.triples, featurizer.quads, box=box, dtype=dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        frames, = ctx.saved_tensors
+        ft = ctx.featurizer
+        atom_ptr, inc = ctx.owner.incidence(int(frames.shape[-2]), frames.device)
+        wide = frames.dtype == torch.float64
+        grad = ops.internal_features_bwd(frames, g.contiguous(), ft.pairs, ft.triples, ft.quads, atom_ptr, inc, box=ctx.box,
+                                         dtype=torch.float64 if wide else torch.float32)      # (a stride-0 g: sum().backward())
+        return grad if grad.dtype == frames.dtype else grad.to(frames.dtype), None, None, None, None
 
 
 def internal_coordinates(frames: torch.Tensor, featurizer: Featurizer, box=None, radians: bool = False,
@@ -874,16 +930,28 @@ def internal_coordinates(frames: torch.Tensor, featurizer: Featurizer, box=None,
     `kcenters` and `assign` should be fed for anything that unfolds, hinges or diffuses.  `radians`: angles and dihedrals as
     one column each (what `free_energy` takes for a map of two torsions).  `box`: bond vectors by the minimum image.
     Asynchronous on the current stream, nothing is read back; CPU tensors and bad arguments raise `MdnoError` before any
-    device work."""
+    device work.
+    DIFFERENTIABLE in the default mode: where `frames.requires_grad` and grad mode is on, the result carries a grad_fn whose
+    backward is one hand-written kernel (include/mdno_internal_grad.h has the rule: every clamp as the identity, an item
+    whose incoming gradient is exactly zero skipped — mask a degenerate feature by zeroing its gradient —, no double
+    backward).  The forward is the same launch and the same bits either way.  `radians=True` has no gradient: with frames
+    that require grad it raises `MdnoError` (detach them)."""
     if not isinstance(featurizer, Featurizer):
         raise MdnoError(f"internal_coordinates: featurizer is a {type(featurizer).__name__}")
     if not torch.is_tensor(frames) or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
         raise MdnoError("internal_coordinates: frames must be [S, M, N, 3] or [F, N, 3]")
     featurizer.check_frames(int(frames.shape[-2]))
+    wants_grad = frames.requires_grad and torch.is_grad_enabled()
+    if wants_grad and radians:
+        raise MdnoError("internal_coordinates: radians=True is not differentiable and frames requires grad (detach the frames, "
+                        "or take the cosine and sine columns of the default mode)")
     if not frames.is_cuda:
         raise MdnoError("frames is a CPU tensor: the internal-coordinate kernels run on the GPU only (no CPU fallback exists)")
+    owner = featurizer
     if featurizer.pairs.device != frames.device:
         featurizer = featurizer.to(frames.device)
+    if wants_grad:
+        return _InternalCoordinatesFn.apply(frames, featurizer, owner, box, dtype)
     return ops.internal_features(frames, featurizer.pairs, featurizer.triples, featurizer.quads, box=box, radians=radians,
                                  dtype=dtype)
 

@@ -1990,6 +1990,62 @@ def internal_features(frames: torch.Tensor, pairs=None, triples=None, quads=None
     return out
 
 
+ICG_MAX_ITEMS = _lib.INTERNAL_GRAD_MAX_ITEMS    # MDNO_ICG_MAX_ITEMS: an incidence is item * 4 + slot in an int32
+ICG_TARGET_GROUPS = 1024            # MDNO_ICG_TARGET_GROUPS
+ICG_MIN_THREADS = 64                # MDNO_ICG_MIN_THREADS
+
+
+def icg_atom_chunk(n_frames: int, n_atoms: int) -> int:
+    """The atoms of a frame group one workgroup of mdnoicg_features_bwd owns (include/mdno_internal_grad.h, FORMS AND GRID)."""
+    G = ic_frames_per_group(n_atoms)
+    groups = -(-n_frames // G)
+    C = n_atoms
+    while C > 0 and groups * -(-n_atoms // C) < ICG_TARGET_GROUPS and G * C > ICG_MIN_THREADS:
+        C = (C + 1) // 2
+    return C
+
+
+def internal_features_bwd(frames: torch.Tensor, g: torch.Tensor, pairs, triples, quads, atom_ptr: torch.Tensor, inc: torch.Tensor,
+                          box=None, dtype=torch.float32, form: str = "auto") -> torch.Tensor:
+    """The adjoint of `internal_features` in its default mode: frames f32 [..., N, 3], g [..., D] (f32 or f64, the gradient
+    with respect to the features, D = P + A + 2 T), the index arrays of the forward and the incidence table atom_ptr i32
+    [N + 1], inc i32 [n_inc] (inc[e] = item * 4 + slot, ascending within an atom: forecast.Featurizer.incidence builds it) ->
+    grad [..., N, 3] of `dtype` (f32 or f64): per (frame, atom) one fp64 accumulation chain over the atom's incidences, by
+    the rule of include/mdno_internal_grad.h (mdnoicg_features_bwd).  An item whose g is exactly zero is skipped; every
+    element is written.  `form` as in `internal_features` (the same bits).  Asynchronous on the current stream, nothing is
+    read back."""
+    if form not in IC_FORMS:
+        raise MdnoError(f"form {form!r}: expected one of {sorted(IC_FORMS)}")
+    if dtype not in (torch.float32, torch.float64):
+        raise MdnoError(f"dtype {dtype}: expected torch.float32 or torch.float64")
+    box = check_box(box, 0.0)
+    frames, lead, F, N = _flat_frames(frames)
+    if form == "lds" and N > IC_LDS_ATOMS:
+        raise MdnoError(f"form 'lds' holds frames of at most {IC_LDS_ATOMS} atoms, N = {N}")
+    dev = frames.device
+    pairs, triples, quads = (_ic_indices(t, w, n, dev) for t, w, n in ((pairs, 2, "pairs"), (triples, 3, "triples"), (quads, 4, "quads")))
+    P, A, T = pairs.shape[0], triples.shape[0], quads.shape[0]
+    D = P + A + 2 * T
+    if P + A + T >= ICG_MAX_ITEMS:
+        raise MdnoError(f"{P + A + T} index tuples: the incidence table holds fewer than 2^29")
+    if not torch.is_tensor(g) or g.dtype not in (torch.float32, torch.float64) or g.device != dev or tuple(g.shape) != lead + (D,):
+        what = f"{g.dtype} {tuple(g.shape)} on {g.device}" if torch.is_tensor(g) else type(g).__name__
+        raise MdnoError(f"g is {what}: expected float32 or float64 {lead + (D,)} on {dev}")
+    for t, n, what in ((atom_ptr, N + 1, "atom_ptr"), (inc, None, "inc")):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):
+            raise MdnoError(f"{what}: expected an int32 vector{'' if n is None else f' of {n} entries'} on {dev}")
+    g, atom_ptr, inc = g.contiguous(), atom_ptr.contiguous(), inc.contiguous()
+    n_inc = inc.shape[0]
+    lib = _lib.load()
+    grad = torch.empty(lead + (N, 3), dtype=dtype, device=dev)
+    code = lambda t: _lib.INTERNAL_DTYPES[str(t).split(".")[-1]]
+    check(lib.mdnoicg_features_bwd(ptr(frames) if F * N else None, F, N, ptr(pairs) if P else None, P, ptr(triples) if A else None, A,
+                                   ptr(quads) if T else None, T, ptr(atom_ptr), ptr(inc) if n_inc else None, n_inc,
+                                   box_arg(box) if box else None, 0, ptr(g) if F * D else None, code(g.dtype),
+                                   ptr(grad) if F * N else None, code(dtype), IC_FORMS[form], stream_ptr(dev)), "mdnoicg_features_bwd")
+    return grad
+
+
 def check_column_ranges(lo, hi, n_bins, D: int):
     """(lo, hi as lists of Python floats — one entry: a range shared by all columns, else D —, n_bins as int) for a column
     histogram, or MdnoError: finite, hi > lo, n_bins in 1 .. IC_MAX_BINS.  Host only."""

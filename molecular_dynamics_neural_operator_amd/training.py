@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import MdnoError
 from .dataset import PairData
+from .graph_kernel import LpLoss
 
 
 class KernelIntegralBlock(torch.autograd.Function):
@@ -735,3 +736,109 @@ def validate_epoch(model, batches, loss_fn, batch_size: Optional[int] = None):
     vals = torch.stack([v.detach().reshape(()) for v in losses] + [v.detach().reshape(()) for v in mses]).double().cpu().tolist()
     tot, tot_mse = sum(vals[:n]), sum(vals[n:])      # (one copy; batch-order sums in double, as train_epoch)
     return tot / n, tot_mse / n
+
+
+class StructureLoss(LpLoss):
+    """A `loss_fn` for `train_epoch`, `validate_epoch`, unrolled training and `DataParallelTrainer` as they are, that puts a
+    structure term beside the Cartesian one:
+
+        loss(out, y) = base(out, y) + sum over kinds of w_kind * mean((ic(out) - ic(y)) ** 2)
+
+    out, y [B, N * 3]; ic = `forecast.internal_coordinates(..., featurizer, box)` in its default mode (distances, angle
+    cosines, dihedral (cos, sin)); the kinds are the featurizer's distance, angle and dihedral columns, and each mean runs
+    over that kind's columns and the B frames.  `weight` is one number for all three or a (distances, angles, dihedrals)
+    triple; a kind whose weight is 0 (or that has no column) is not evaluated, so weight = 0 IS `base`.  The features and
+    their gradient are one hand-written kernel each (include/mdno_internal.h, include/mdno_internal_grad.h); the difference,
+    the square and the weighted sum that is the mean are torch operations — a handful of small framework kernels per step
+    on this opt-in path, which scripts/train_aten_audit.py --structure-weight lists.  `rel_with_mse` returns this loss and the MSE the base logs.
+    It is an `LpLoss` that carries its base's `d`, `p`, `reduction` and `size_average` (p = None over any other base), which
+    is what `DataParallelTrainer` asks of a loss; a rank's structure term is the mean over ITS shard of the batch, so under
+    several ranks it is the global term where the base averages (`size_average=True`: shards weighted by their share) and
+    the sum of the shards' means where the base sums.  The absolute form (`abs`) has no structure term and is refused."""
+
+    def __init__(self, base, featurizer, weight=1.0, box=None):
+        from .forecast import Featurizer
+        if not callable(base):
+            raise MdnoError(f"StructureLoss: base is a {type(base).__name__}, expected a loss function")
+        if not isinstance(featurizer, Featurizer):
+            raise MdnoError(f"StructureLoss: featurizer is a {type(featurizer).__name__}")
+        if featurizer.n_atoms is None:
+            raise MdnoError("StructureLoss: the featurizer has no n_atoms (build it with n_atoms=N): out [B, N * 3] does not say "
+                            "how many atoms a frame has")
+        try:
+            w = [float(weight)] * 3 if not hasattr(weight, "__len__") else [float(v) for v in weight]
+        except (TypeError, ValueError):
+            w = []
+        if len(w) != 3 or not all(np.isfinite(v) and v >= 0.0 for v in w):
+            raise MdnoError(f"StructureLoss: weight = {weight!r}, expected a finite number >= 0 or three of them "
+                            "(distances, angles, dihedrals)")
+        if isinstance(base, LpLoss):
+            super().__init__(base.d, base.p, base.size_average, base.reduction)
+        else:
+            self.d, self.p, self.reduction, self.size_average = 2, None, False, False
+        self.base, self.featurizer, self.weight = base, featurizer, tuple(w)
+        self.box = ops.check_box(box, 0.0)
+        self._on = {}                   # device -> the featurizer's indices there
+        self._wcol = {}                 # (device, B) -> the weight of every column, w_kind / (B columns of the kind)
+
+    def _featurizer_on(self, device):
+        ft = self._on.get(device)
+        if ft is None:
+            ft = self._on[device] = self.featurizer if self.featurizer.pairs.device == device else self.featurizer.to(device)
+        return ft
+
+    def structure(self, out, y):
+        """The structure term alone (a 0-dim tensor), or None where every weight is 0."""
+        from .forecast import internal_coordinates
+        ft = self._featurizer_on(out.device)
+        N = ft.n_atoms
+        P, A, T = ft.pairs.shape[0], ft.triples.shape[0], ft.quads.shape[0]
+        kinds = [(w, lo, hi) for w, lo, hi in zip(self.weight, (0, P, P + A), (P, P + A, P + A + 2 * T)) if w != 0.0 and hi > lo]
+        if not kinds:
+            return None
+        B = out.shape[0]
+        if out.dim() != 2 or out.shape[1] != 3 * N or tuple(y.shape) != tuple(out.shape):
+            raise MdnoError(f"StructureLoss: out {tuple(out.shape)}, y {tuple(y.shape)}: expected [B, {3 * N}] both")
+        f_out = internal_coordinates(out.reshape(B, N, 3), ft, box=self.box)
+        with torch.no_grad():
+            f_y = internal_coordinates(y.to(out.device).reshape(B, N, 3), ft, box=self.box)
+        # one weighted sum per run of adjacent weighted kinds (w_kind / (B columns) per column IS w_kind times the kind's
+        # mean): four small kernels forward where a mean per kind takes a dozen; a kind of weight 0 lies in no run
+        key = (out.device, B)
+        wcol = self._wcol.get(key)
+        if wcol is None:
+            wcol = torch.zeros(P + A + 2 * T, dtype=torch.float32)
+            for w, lo, hi in kinds:
+                wcol[lo:hi] = w / (B * (hi - lo))
+            wcol = self._wcol[key] = wcol.to(out.device)
+        runs = []
+        for _, lo, hi in kinds:
+            if runs and runs[-1][1] == lo:
+                runs[-1][1] = hi
+            else:
+                runs.append([lo, hi])
+        total = None
+        for lo, hi in runs:
+            whole = lo == 0 and hi == wcol.shape[0]
+            d = f_out - f_y if whole else f_out[:, lo:hi] - f_y[:, lo:hi]
+            term = torch.sum(d * d * (wcol if whole else wcol[lo:hi]))
+            total = term if total is None else total + term
+        return total
+
+    def rel(self, out, y):
+        loss, extra = self.base(out, y), self.structure(out, y)
+        return loss if extra is None else loss + extra
+
+    def __call__(self, out, y):
+        return self.rel(out, y)
+
+    def abs(self, out, y):
+        raise MdnoError("StructureLoss wraps its base's relative form (call it, or rel / rel_with_mse); abs has no structure term")
+
+    def rel_with_mse(self, out, y):
+        if hasattr(self.base, "rel_with_mse"):
+            loss, mse = self.base.rel_with_mse(out, y)
+        else:
+            loss, mse = self.base(out, y), F.mse_loss(out.detach(), y)
+        extra = self.structure(out, y)
+        return (loss if extra is None else loss + extra), mse

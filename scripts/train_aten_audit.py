@@ -1,6 +1,6 @@
 """Which ATen operators (and device copies) still run inside one cfg4 training batch, and from which line.
 
-  python scripts/train_aten_audit.py [--precision bf16] [--batches 3]
+  python scripts/train_aten_audit.py [--precision bf16] [--batches 3] [--structure-weight W]
 
 torch.profiler over a few train_epoch batches at the cfg4 shape (N = 28, batch 128, k = 1024, depth 6) with Python
 stacks: per operator the calls per batch and the innermost frame inside this repository.  A measurement aid for
@@ -25,6 +25,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--precision", choices=["fp32", "bf16"], default="bf16")
 ap.add_argument("--batches", type=int, default=3)
 ap.add_argument("--batch-size", type=int, default=128)
+ap.add_argument("--structure-weight", type=float, default=0.0,
+                help="W > 0: the loss is training.StructureLoss(LpLoss, Featurizer.backbone(28), W) — its torch operations show below")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 N, W, B = 28, 10, a.batch_size
@@ -47,6 +49,10 @@ try:
 except (RuntimeError, TypeError):
     opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=5e-4)
 loss_fn = LpLoss(size_average=False)
+if a.structure_weight != 0.0:
+    from molecular_dynamics_neural_operator_amd.forecast import Featurizer  # noqa: E402
+    from molecular_dynamics_neural_operator_amd.training import StructureLoss  # noqa: E402
+    loss_fn = StructureLoss(loss_fn, Featurizer.backbone(N), weight=a.structure_weight)
 idx = [list(range(s, s + B)) for s in range(0, (a.batches + 2) * B, B)]
 train_epoch(model, (dtraj.batch(i) for i in idx[:2]), opt, loss_fn)          # warm-up
 torch.cuda.synchronize()

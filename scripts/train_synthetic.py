@@ -51,6 +51,11 @@ ap.add_argument("--unroll", type=int, default=1,
                      "device-collated batches, --precision fp32 unless --unroll-detach)")
 ap.add_argument("--unroll-detach", action="store_true",
                 help="cut the gradient at every fed-back frame (the pushforward variant)")
+ap.add_argument("--structure-weight", type=float, default=0.0,
+                help="W > 0: train and validate on LpLoss + W * (mean squared difference of the internal coordinates, per "
+                     "kind: training.StructureLoss over Featurizer.backbone(N, K, S)); 0: the loss is not wrapped")
+ap.add_argument("--structure-min-sep", type=int, default=3, help="K: the least sequence separation of a non-bonded pair")
+ap.add_argument("--structure-stride", type=int, default=1, help="S: non-bonded pairs among every S-th atom")
 ap.add_argument("--workdir", default="/tmp/mdno_train")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -117,11 +122,18 @@ else:                 # training.Adam: torch.optim.Adam's arithmetic and state a
     opt = Adam(model.parameters(), lr=a.lr, weight_decay=5e-4)
 sched = torch.optim.lr_scheduler.StepLR(opt, step_size=50, gamma=0.8)
 loss_fn = LpLoss(size_average=False)
+step_loss = loss_fn                # what the device path trains and validates on (the CPU baseline leg keeps the plain loss)
+if a.structure_weight != 0.0:
+    from molecular_dynamics_neural_operator_amd.forecast import Featurizer  # noqa: E402
+    from molecular_dynamics_neural_operator_amd.training import StructureLoss  # noqa: E402
+    if a.host_collate or a.cpu_batches:
+        ap.error("--structure-weight runs on the device (drop --host-collate and --cpu-batches)")
+    step_loss = StructureLoss(loss_fn, Featurizer.backbone(N, a.structure_min_sep, a.structure_stride), weight=a.structure_weight)
 
 
 def validate():
     """The reference's validate() (graph_kernel.py:476-493): eval mode, no autograd, model(batch) per batch."""
-    return validate_epoch(model, vbatches, loss_fn)[0]
+    return validate_epoch(model, vbatches, step_loss)[0]
 
 
 summary = {"frames": a.frames, "batch_size": B, "train_batches": len(batches), "edges_per_batch":
@@ -129,12 +141,15 @@ summary = {"frames": a.frames, "batch_size": B, "train_batches": len(batches), "
            "depth": a.depth, "collate": "host" if a.host_collate else "device"}
 summary["precision"] = a.precision
 summary["unroll"], summary["unroll_detach"] = a.unroll, a.unroll_detach
-train_epoch(model, batches[:1], opt, loss_fn)          # warm-up (allocator, kernels)
+if step_loss is not loss_fn:
+    summary.update(structure_weight=a.structure_weight, structure_min_sep=a.structure_min_sep, structure_stride=a.structure_stride,
+                   structure_features=step_loss.featurizer.dim())
+train_epoch(model, batches[:1], opt, step_loss)        # warm-up (allocator, kernels)
 torch.cuda.synchronize()
 torch.cuda.reset_peak_memory_stats()
 for ep in range(a.epochs):
     t0 = time.perf_counter()
-    tl, mse = train_epoch(model, batches, opt, loss_fn, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep,
+    tl, mse = train_epoch(model, batches, opt, step_loss, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep,
                           unroll=a.unroll, unroll_detach=a.unroll_detach)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0

@@ -281,6 +281,17 @@ INTERNAL_GRAD_SIGNATURES = {
     "mdnoicg_features_bwd": (_I, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P, _I, _P, _I, _P, _I, _I, _P]),
 }
 
+# include/mdno_constrain.h (distance-constraint projection of frames, and of the frame a rollout step produces; additive, no
+# version number of its own): name -> (restype, argtypes), kept in step with that header (tests/test_constrain_host.py
+# checks both ways).  The names start with mdnocst_, the plan's setter included, for the reason mdnoens_ has (the header says
+# so too).  `box` is a HOST pointer to three doubles; the table (pairs, lo, hi, colour_ptr, weights) lies on the device.
+CONSTRAIN_MAX_ATOMS = 6144          # MDNOCST_MAX_ATOMS: the largest N (the state of a frame lies in LDS as fp64)
+CONSTRAIN_MAX_CONSTRAINTS = 1 << 26  # MDNOCST_MAX_CONSTRAINTS
+CONSTRAIN_SIGNATURES = {
+    "mdnocst_project": (_I, [_P, _P, _L, _I, _P, _P, _P, _L, _P, _I, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "mdnocst_rollout_plan_set_constraints": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _I, _D, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -315,7 +326,7 @@ def load() -> C.CDLL:
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
             list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
             list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + \
-            list(INTERNAL_GRAD_SIGNATURES.items()):
+            list(INTERNAL_GRAD_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "pbc.h"
 #include "../../include/mdno_noise.h"
+#include "../../include/mdno_constrain.h"
 #include "../../include/mdno_pbc.h"
 
 #include <string>
@@ -366,6 +367,19 @@ struct mdno_rollout_plan {
     bool pbc_on;
     PbcBox box;
     float* pbc_attr;                 // f32 [edge_cap, 6], caller-owned: the step's edge attributes
+    // constrained rollout (mdnocst_rollout_plan_set_constraints): cst_C == 0 -> none of it is launched or captured
+    long long cst_C;
+    const int* cst_pairs;
+    const double* cst_lo;
+    const double* cst_hi;
+    const int* cst_colour_ptr;
+    int cst_colours;
+    const float* cst_weights;
+    int cst_iterations;
+    double cst_tol;
+    int* cst_sweeps;                 // [max_steps, M], caller-owned (or NULL), as the two below
+    double* cst_viol_in;
+    double* cst_viol_out;
 };
 
 static void plan_counter_words(const mdno_rollout_plan* pl, int** conv, int** mlp) {
@@ -411,6 +425,11 @@ static int plan_enqueue_step(mdno_rollout_plan* pl, hipStream_t s) {
     // the new frame is perturbed where it lies, before the next step's graph and windows read it
     if (pl->noise_sigma != 0.f)
         MDNO_TRY(noise_step(pl->traj, W, pl->r.t_dev, pl->M, pl->N, pl->noise_members, pl->noise_seed, pl->noise_sigma, s));
+    // and then projected onto its distance bands, still before anything reads it
+    if (pl->cst_C != 0)
+        MDNO_TRY(constrain_step(pl->traj, W, pl->r.t_dev, pl->M, pl->N, pl->max_steps, pl->cst_pairs, pl->cst_lo, pl->cst_hi,
+                                pl->cst_C, pl->cst_colour_ptr, pl->cst_colours, pl->cst_weights, pl->pbc_on ? &pl->box : nullptr,
+                                pl->cst_iterations, pl->cst_tol, pl->cst_sweeps, pl->cst_viol_in, pl->cst_viol_out, s));
     return MDNO_OK;
 }
 
@@ -552,6 +571,41 @@ extern "C" int mdno_rollout_plan_set_box(mdno_rollout_plan* pl, const double* bo
     if (same || !pl->capture_stream) return MDNO_OK;
     // the captured step holds the graph kernels, the box and the edge source: capture it again (as set_noise does; if
     // the capture fails the error is returned and the plan is left without graphs: plain launches, same frames)
+    MDNO_HIP(hipStreamSynchronize(pl->capture_stream));
+    plan_drop_graphs(pl);
+    return plan_capture(pl);
+}
+
+extern "C" int mdnocst_rollout_plan_set_constraints(mdno_rollout_plan* pl, const int32_t* pairs, const double* lo,
+                                                    const double* hi, int64_t C, const int32_t* colour_ptr, int n_colours,
+                                                    const float* weights, int iterations, double tol, int32_t* sweeps,
+                                                    double* viol_in, double* viol_out) {
+    const char* who = "mdnocst_rollout_plan_set_constraints";
+    MDNO_REQUIRE(pl != nullptr, MDNO_EINVAL, "%s: null plan", who);
+    const bool now = C != 0 && pairs != nullptr;
+    if (now) MDNO_TRY(constrain_check(who, pl->N, pairs, lo, hi, (long long)C, colour_ptr, n_colours, iterations, tol));
+    const bool was = pl->cst_C != 0;
+    const bool same = was == now && (!now || (pl->cst_C == (long long)C && pl->cst_pairs == pairs && pl->cst_lo == lo &&
+                                              pl->cst_hi == hi && pl->cst_colour_ptr == colour_ptr && pl->cst_colours == n_colours &&
+                                              pl->cst_weights == weights && pl->cst_iterations == iterations &&
+                                              pl->cst_tol == tol && pl->cst_sweeps == sweeps && pl->cst_viol_in == viol_in &&
+                                              pl->cst_viol_out == viol_out));
+    pl->cst_C = now ? (long long)C : 0;
+    pl->cst_pairs = now ? pairs : nullptr;
+    pl->cst_lo = now ? lo : nullptr;
+    pl->cst_hi = now ? hi : nullptr;
+    pl->cst_colour_ptr = now ? colour_ptr : nullptr;
+    pl->cst_colours = now ? n_colours : 0;
+    pl->cst_weights = now ? weights : nullptr;
+    pl->cst_iterations = now ? iterations : 0;
+    pl->cst_tol = now ? tol : 0.0;
+    pl->cst_sweeps = now ? sweeps : nullptr;
+    pl->cst_viol_in = now ? viol_in : nullptr;
+    pl->cst_viol_out = now ? viol_out : nullptr;
+    if (now) MDNO_TRY(constrain_prepare());
+    if (same || !pl->capture_stream) return MDNO_OK;
+    // the captured step holds the projection launch (or its absence) and its arguments: capture it again (as set_noise
+    // does; if the capture fails the error is returned and the plan is left without graphs: plain launches, same frames)
     MDNO_HIP(hipStreamSynchronize(pl->capture_stream));
     plan_drop_graphs(pl);
     return plan_capture(pl);

@@ -209,4 +209,15 @@ int fc_out(const float* x, const float* w, const float* b, int rows, int width, 
 int noise_step(float* traj, int W, const int* t_dev, int M, int N, const int* member_ids, unsigned long long seed,
                float sigma, hipStream_t s);
 
+// Constrained rollout (constrain.hip, include/mdno_constrain.h): traj[W + step][m] is projected onto its distance bands where
+// it lies, step = *t_dev - 1 as for the noise, and row `step` of sweeps / viol_in / viol_out [max_steps, M] (NULL: not kept)
+// is written.  constrain_check: the table's validation, without device work; constrain_prepare: what must happen outside a
+// stream capture before the first constrain_step is captured.
+int constrain_check(const char* who, int N, const int* pairs, const double* lo, const double* hi, long long C, const int* colour_ptr,
+                    int n_colours, int iterations, double tol);
+int constrain_prepare();
+int constrain_step(float* traj, int W, const int* t_dev, int M, int N, int max_steps, const int* pairs, const double* lo,
+                   const double* hi, long long C, const int* colour_ptr, int n_colours, const float* weights, const PbcBox* box,
+                   int iterations, double tol, int* sweeps, double* viol_in, double* viol_out, hipStream_t s);
+
 }  // namespace mdno

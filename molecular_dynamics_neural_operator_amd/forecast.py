@@ -95,6 +95,14 @@ whether the produced frames are physical chains:
     h = feature_histograms(x, *feature_ranges(truth_x), 32)     # FeatureHistograms: counts i64 [M, D, 34]
     h.total_variation(truth_h), h.outside()                     # f64 [M, D]: per column against the truth; share outside its range
     disc = discretize(truth, 100, components=tc, featurizer=ft) # states in internal coordinates: no reference frame
+
+Distance constraints.  The scores above say, after the fact, that a run has left the chain manifold; a SHAKE-style projection
+keeps a produced frame on it before it is fed back (csrc/constrain.hip: whole frames staged in LDS as fp64, the constraints
+walked colour by colour; include/mdno_constrain.h has the rule):
+
+    cons = DistanceConstraints.from_frames(truth, ft, margin=0.1)  # every listed pair inside the truth's own range
+    frames, rep = project_constraints(frames, cons, iterations=8)  # ConstraintReport: sweeps i32, viol_in, viol_out f64 [S, M]
+    RolloutEngine(model, M, N, W, constraints=cons)                # the same projection at the end of every step
 """
 from __future__ import annotations
 
@@ -1359,6 +1367,212 @@ def markov_model(counts: TransitionCounts, lag_index: int = 0, reversible: bool 
         pi = v[:, torch.argmin((w - 1.0).abs())].real
         pi = pi.abs() / pi.abs().sum()
     return MarkovModel(int(counts.lags[lag_index]), n, idx, T, lam, pi, bool(reversible))
+
+
+# ------------------------------------------------------------------------------------------------
+# Distance constraints (csrc/constrain.hip, include/mdno_constrain.h has the rule)
+def greedy_colours(pairs) -> list:
+    """The colour of every constraint of a host list of (i, j): in list order, each takes the lowest colour that neither of
+    its atoms has yet (include/mdno_constrain.h, ORDER).  Within a colour no two constraints share an atom."""
+    used, colours = {}, []
+    for i, j in pairs:
+        m = used.get(i, 0) | used.get(j, 0)
+        bit = (m + 1) & ~m                       # the lowest zero bit of m
+        used[i] = used.get(i, 0) | bit
+        used[j] = used.get(j, 0) | bit
+        colours.append(bit.bit_length() - 1)
+    return colours
+
+
+@dataclass
+class ColouredConstraints:
+    """A constraint table as the kernel takes it (`DistanceConstraints.coloured`): sorted by colour, on one device."""
+    pairs: torch.Tensor              # i32 [C, 2]
+    lo: torch.Tensor                 # f64 [C]
+    hi: torch.Tensor                 # f64 [C]
+    colour_ptr: torch.Tensor         # i32 [n_colours + 1]
+    weights: Optional[torch.Tensor]  # f32 [N] or None
+    order: torch.Tensor              # i64 [C] (host): row k of the table is constraint order[k] of the list
+
+    @property
+    def n_colours(self) -> int:
+        return int(self.colour_ptr.shape[0]) - 1
+
+
+@dataclass
+class ConstraintReport:
+    """What a projection did per frame: `sweeps` i32, `viol_in` and `viol_out` f64, the largest |length - band| before the
+    first and after the last sweep, shaped as the frames' leading dimensions ([S, M] or [F])."""
+    sweeps: torch.Tensor
+    viol_in: torch.Tensor
+    viol_out: torch.Tensor
+
+    @staticmethod
+    def cat(parts: Sequence["ConstraintReport"], dim: int = 1) -> "ConstraintReport":
+        return ConstraintReport(torch.cat([p.sweeps for p in parts], dim), torch.cat([p.viol_in for p in parts], dim),
+                                torch.cat([p.viol_out for p in parts], dim))
+
+
+@dataclass
+class DistanceConstraints:
+    """Distance bands lo <= |x_i - x_j| <= hi for the pairs of `pairs` i32 [C, 2] (lo, hi f64 [C]; hi = inf: a lower bound
+    only; lo == hi: an equality) with optional per-atom `weights` f32 [n_atoms] in the role of inverse masses (0 pins an
+    atom; None: 1 everywhere).  Built and validated on the host by `of`, `chain` and `from_frames`; `a + b` concatenates two
+    lists (the weights must agree), `.to(device)` moves the tensors, `.coloured(device)` is the table the kernel walks."""
+    pairs: torch.Tensor
+    lo: torch.Tensor
+    hi: torch.Tensor
+    weights: Optional[torch.Tensor] = None
+    n_atoms: Optional[int] = None
+    top: int = -1
+    _coloured: dict = field(default_factory=dict, init=False, repr=False, compare=False)     # device -> ColouredConstraints
+
+    @staticmethod
+    def of(pairs, lo, hi, weights=None, n_atoms: Optional[int] = None) -> "DistanceConstraints":
+        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
+            raise MdnoError(f"DistanceConstraints: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        p = _index_array(pairs, 2, n_atoms, "pairs")
+        n_c = int(p.shape[0])
+        if n_c > ops.CST_MAX_CONSTRAINTS:
+            raise MdnoError(f"DistanceConstraints: {n_c} constraints, more than {ops.CST_MAX_CONSTRAINTS}")
+        if n_c and bool((p[:, 0] == p[:, 1]).any()):
+            k = int((p[:, 0] == p[:, 1]).nonzero()[0])
+            raise MdnoError(f"DistanceConstraints: constraint {k} joins atom {int(p[k, 0])} to itself (i == j)")
+        bounds = []
+        for v, what in ((lo, "lo"), (hi, "hi")):
+            try:      # (Python numbers straight to f64: as_tensor alone would round them to f32 first)
+                t = v.detach().cpu().to(torch.float64) if torch.is_tensor(v) else torch.as_tensor(v, dtype=torch.float64)
+                t = t.reshape(-1)
+            except (TypeError, ValueError, RuntimeError):
+                raise MdnoError(f"DistanceConstraints: {what} is not an array of numbers") from None
+            if t.numel() == 1 and n_c != 1:
+                t = t.expand(n_c)
+            if t.numel() != n_c:
+                raise MdnoError(f"DistanceConstraints: {t.numel()} entries of {what} for {n_c} constraints")
+            if bool(torch.isnan(t).any()):
+                raise MdnoError(f"DistanceConstraints: {what} holds a NaN")
+            if bool((t < 0).any()):
+                raise MdnoError(f"DistanceConstraints: {what} holds a negative bound")
+            bounds.append(t.contiguous().clone())
+        lo_t, hi_t = bounds
+        if bool(torch.isinf(lo_t).any()):
+            raise MdnoError("DistanceConstraints: lo holds an infinite bound")
+        if bool((lo_t > hi_t).any()):
+            k = int((lo_t > hi_t).nonzero()[0])
+            raise MdnoError(f"DistanceConstraints: constraint {k} has lo = {float(lo_t[k])} > hi = {float(hi_t[k])}")
+        top = int(p.max()) if n_c else -1
+        w = None
+        if weights is not None:
+            w = weights.detach().cpu() if torch.is_tensor(weights) else torch.as_tensor(weights)
+            w = w.to(torch.float32).reshape(-1).contiguous().clone()
+            if n_atoms is None:
+                n_atoms = int(w.numel())
+            if w.numel() != n_atoms or top >= n_atoms:
+                raise MdnoError(f"DistanceConstraints: {w.numel()} weights for frames of {max(n_atoms, top + 1)} atoms")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise MdnoError("DistanceConstraints: weights must be finite and >= 0")
+        return DistanceConstraints(p, lo_t, hi_t, w, n_atoms, top)
+
+    @staticmethod
+    def chain(n_atoms: int, lo, hi, weights=None) -> "DistanceConstraints":
+        """The n - 1 consecutive pseudo-bonds (i, i + 1) of a chain, each inside [lo, hi] (numbers, or one per bond)."""
+        if isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0:
+            raise MdnoError(f"DistanceConstraints.chain: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        idx = torch.arange(n_atoms, dtype=torch.int64)
+        bonds = torch.stack([idx[:-1], idx[1:]], 1) if n_atoms > 1 else torch.zeros((0, 2), dtype=torch.int64)
+        return DistanceConstraints.of(bonds, lo, hi, weights, n_atoms)
+
+    @staticmethod
+    def from_frames(truth: torch.Tensor, pairs_or_featurizer, margin: float = 0.0, box=None, weights=None) -> "DistanceConstraints":
+        """Bands taken from a true trajectory: for every pair (an index array [C, 2], or the distance columns of a
+        `Featurizer`) the smallest and the largest distance over all frames of truth f32 [..., N, 3] (device), through
+        `internal_coordinates` in f64 and amin / amax, widened by `margin` on both sides (lo - margin clamped at 0)."""
+        margin = float(margin)
+        if not (math.isfinite(margin) and margin >= 0.0):
+            raise MdnoError(f"DistanceConstraints.from_frames: margin = {margin}, expected a finite number >= 0")
+        if not torch.is_tensor(truth) or truth.dim() < 3 or truth.shape[-1] != 3:
+            raise MdnoError("DistanceConstraints.from_frames: truth must be [..., N, 3]")
+        n = int(truth.shape[-2])
+        pairs = pairs_or_featurizer.pairs if isinstance(pairs_or_featurizer, Featurizer) else pairs_or_featurizer
+        ft = Featurizer.of(pairs=pairs, n_atoms=n)
+        if ft.pairs.shape[0] == 0 or truth.numel() == 0:
+            raise MdnoError("DistanceConstraints.from_frames: no pairs or no frames")
+        d = internal_coordinates(truth.detach().reshape(-1, n, 3), ft, box=box, dtype=torch.float64)
+        lo = (torch.amin(d, 0) - margin).clamp_min(0.0)
+        hi = torch.amax(d, 0) + margin
+        return DistanceConstraints.of(ft.pairs, lo.cpu(), hi.cpu(), weights, n)
+
+    def __len__(self) -> int:
+        return int(self.pairs.shape[0])
+
+    def __add__(self, other: "DistanceConstraints") -> "DistanceConstraints":
+        if not isinstance(other, DistanceConstraints):
+            return NotImplemented
+        if self.n_atoms is not None and other.n_atoms is not None and self.n_atoms != other.n_atoms:
+            raise MdnoError(f"DistanceConstraints: n_atoms {self.n_atoms} + n_atoms {other.n_atoms}")
+        if self.pairs.device != other.pairs.device:
+            raise MdnoError(f"DistanceConstraints: a list on {self.pairs.device} + a list on {other.pairs.device}")
+        a, b = self.weights, other.weights
+        if (a is None) != (b is None) or (a is not None and not torch.equal(a, b)):
+            raise MdnoError("DistanceConstraints: the two lists carry different weights")
+        return DistanceConstraints(torch.cat([self.pairs, other.pairs]), torch.cat([self.lo, other.lo]), torch.cat([self.hi, other.hi]),
+                                   a, self.n_atoms if self.n_atoms is not None else other.n_atoms, max(self.top, other.top))
+
+    def to(self, device) -> "DistanceConstraints":
+        return DistanceConstraints(self.pairs.to(device), self.lo.to(device), self.hi.to(device),
+                                   None if self.weights is None else self.weights.to(device), self.n_atoms, self.top)
+
+    def colours(self) -> list:
+        """The colour of every constraint, in list order (`greedy_colours`)."""
+        return greedy_colours(self.pairs.cpu().tolist())
+
+    def coloured(self, device=None) -> ColouredConstraints:
+        """The table sorted stably by colour on `device` (None: where the list is), with its colour_ptr; coloured on the host,
+        once per device (`.to` and `+` make instances without a cache)."""
+        device = self.pairs.device if device is None else torch.device(device)
+        hit = self._coloured.get(str(device))
+        if hit is not None:
+            return hit
+        col = torch.tensor(self.colours(), dtype=torch.int64)
+        order = torch.sort(col, stable=True).indices if col.numel() else col
+        n_colours = int(col.max()) + 1 if col.numel() else 0
+        ptr_ = torch.zeros(n_colours + 1, dtype=torch.int64)
+        if n_colours:
+            ptr_[1:] = torch.cumsum(torch.bincount(col, minlength=n_colours), 0)
+        table = ColouredConstraints(self.pairs.cpu()[order].contiguous().to(device), self.lo.cpu()[order].contiguous().to(device),
+                                    self.hi.cpu()[order].contiguous().to(device), ptr_.to(torch.int32).to(device),
+                                    None if self.weights is None else self.weights.to(device), order)
+        self._coloured[str(device)] = table
+        return table
+
+    def check_frames(self, n_atoms: int) -> None:
+        if (self.n_atoms is not None and n_atoms != self.n_atoms) or self.top >= n_atoms:
+            want = f"{self.n_atoms}" if self.n_atoms is not None else f"more than {self.top}"
+            raise MdnoError(f"the constraints were built for frames of {want} atoms, these have {n_atoms}")
+        if self.weights is not None and int(self.weights.numel()) != n_atoms:
+            raise MdnoError(f"the constraints carry {int(self.weights.numel())} weights, the frames have {n_atoms} atoms")
+
+
+def project_constraints(frames: torch.Tensor, constraints: DistanceConstraints, box=None, iterations: int = 8, tol: float = 0.0,
+                        out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ConstraintReport]:
+    """frames f32 [S, M, N, 3] (device; [F, N, 3] is a plain stack) -> (the frames with every listed pair distance moved
+    towards its band, ConstraintReport): per frame up to `iterations` sweeps over the coloured constraints, SHAKE-style, in
+    fp64 on the fp32 coordinates, until the largest |length - band| is at most `tol` (include/mdno_constrain.h has the rule;
+    ops.project_constraints).  A frame inside every band comes back with the same bits and 0 sweeps; `iterations=0` only
+    measures.  `out=frames` projects in place.  `box`: bond vectors by the minimum image.  Frames of at most
+    `ops.CST_MAX_ATOMS` atoms.  Not differentiable.  Asynchronous on the current stream, nothing is read back; CPU tensors
+    and bad arguments raise `MdnoError` before any device work."""
+    if not isinstance(constraints, DistanceConstraints):
+        raise MdnoError(f"project_constraints: constraints is a {type(constraints).__name__}")
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise MdnoError("project_constraints: frames must be [S, M, N, 3] or [F, N, 3]")
+    constraints.check_frames(int(frames.shape[-2]))
+    if not frames.is_cuda:
+        raise MdnoError("frames is a CPU tensor: the projection kernel runs on the GPU only (no CPU fallback exists)")
+    t = constraints.coloured(frames.device)
+    res, sweeps, vin, vout = ops.project_constraints(frames.detach(), t.pairs, t.lo, t.hi, t.colour_ptr, t.weights, box=box,
+                                                     iterations=iterations, tol=tol, out=out)
+    return res, ConstraintReport(sweeps, vin, vout)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -2093,3 +2093,87 @@ def column_histogram(x: torch.Tensor, lo, hi, n_bins: int, groups: int = 1):
     check(lib.mdnoic_column_histogram(ptr(x) if R else None, R, D, groups, code, lo_arg, hi_arg, int(len(lo) == 1),
                                       n_bins, ptr(counts), ptr(n_nan), stream_ptr(dev)), "mdnoic_column_histogram")
     return counts, n_nan
+
+
+# ------------------------------------------------------------------------------------------------
+# Distance-constraint projection (include/mdno_constrain.h, csrc/constrain.hip)
+CST_MAX_ATOMS = _lib.CONSTRAIN_MAX_ATOMS                # MDNOCST_MAX_ATOMS
+CST_MAX_CONSTRAINTS = _lib.CONSTRAIN_MAX_CONSTRAINTS    # MDNOCST_MAX_CONSTRAINTS
+CST_GROUP_ATOMS = 1024                                  # MDNOCST_GROUP_ATOMS
+CST_MAX_GROUP_FRAMES = 16                               # MDNOCST_MAX_GROUP_FRAMES
+
+
+def cst_frames_per_group(n_atoms: int) -> int:
+    """MDNOCST_FRAMES_PER_GROUP(N): the frames one workgroup of mdnocst_project owns."""
+    if n_atoms <= 0 or CST_GROUP_ATOMS // n_atoms < 1:
+        return 1
+    return min(CST_GROUP_ATOMS // n_atoms, CST_MAX_GROUP_FRAMES)
+
+
+def check_constraint_table(pairs, lo, hi, colour_ptr, weights, n_atoms: int, dev):
+    """The coloured table of a projection as the C ABI takes it: pairs i32 [C, 2], lo / hi f64 [C], colour_ptr i32
+    [n_colours + 1], weights f32 [n_atoms] or None, all contiguous on `dev`; MdnoError otherwise.  Shapes, dtypes and devices
+    only: the values were validated on the host when the table was made (forecast.DistanceConstraints)."""
+    if not torch.is_tensor(pairs) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.device != dev:
+        raise MdnoError(f"pairs: expected int32 [C, 2] on {dev}")
+    n_c = int(pairs.shape[0])
+    if n_c > CST_MAX_CONSTRAINTS:
+        raise MdnoError(f"{n_c} constraints: more than {CST_MAX_CONSTRAINTS}")
+    for t, what in ((lo, "lo"), (hi, "hi")):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != (n_c,) or t.device != dev:
+            raise MdnoError(f"{what}: expected float64 [{n_c}] on {dev}")
+    if not torch.is_tensor(colour_ptr) or colour_ptr.dtype != torch.int32 or colour_ptr.dim() != 1 or colour_ptr.shape[0] < 1 or \
+            colour_ptr.device != dev:
+        raise MdnoError(f"colour_ptr: expected int32 [n_colours + 1] on {dev}")
+    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (n_atoms,)
+                                or weights.device != dev):
+        raise MdnoError(f"weights: expected float32 [{n_atoms}] on {dev} or None")
+    return (pairs.contiguous(), lo.contiguous(), hi.contiguous(), colour_ptr.contiguous(),
+            None if weights is None else weights.contiguous())
+
+
+def check_projection_args(iterations, tol):
+    import math
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations < 2 ** 31:
+        raise MdnoError(f"iterations={iterations!r}: expected an integer >= 0")
+    tol = float(tol)
+    if math.isnan(tol) or tol < 0.0:
+        raise MdnoError(f"tol={tol}: expected a number >= 0")
+    return iterations, tol
+
+
+def project_constraints(frames: torch.Tensor, pairs: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, colour_ptr: torch.Tensor,
+                        weights=None, box=None, iterations: int = 8, tol: float = 0.0, out=None):
+    """frames f32 [..., N, 3] and a COLOURED constraint table on the same device (pairs i32 [C, 2], lo / hi f64 [C] sorted by
+    colour, colour_ptr i32 [n_colours + 1], weights f32 [N] or None) -> (projected f32 [..., N, 3], sweeps i32 [...],
+    viol_in f64 [...], viol_out f64 [...]) by the rule of include/mdno_constrain.h (mdnocst_project): up to `iterations`
+    sweeps per frame, until its largest |length - band| is at most `tol`.  `out`: where the frames go (`frames` itself for
+    an in-place projection; default: a new tensor).  `box` = (Lx, Ly, Lz), 0 for an open axis: bond vectors by the minimum
+    image.  N <= CST_MAX_ATOMS.  Asynchronous on the current stream, nothing is read back."""
+    iterations, tol = check_projection_args(iterations, tol)
+    box = check_box(box, 0.0)
+    frames, lead, F, N = _flat_frames(frames)
+    if N > CST_MAX_ATOMS:
+        raise MdnoError(f"project_constraints: frames of {N} atoms, the kernel holds at most {CST_MAX_ATOMS} (the state of a frame "
+                        f"lies in LDS)")
+    dev = frames.device
+    pairs, lo, hi, colour_ptr, weights = check_constraint_table(pairs, lo, hi, colour_ptr, weights, N, dev)
+    n_c, n_colours = int(pairs.shape[0]), int(colour_ptr.shape[0]) - 1
+    if out is None:
+        out = torch.empty(lead + (N, 3), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != lead + (N, 3) or \
+            not out.is_contiguous():
+        raise MdnoError(f"out: expected a contiguous float32 {lead + (N, 3)} on {dev}")
+    elif out.data_ptr() != frames.data_ptr() and F * N and \
+            out.data_ptr() < frames.data_ptr() + frames.numel() * 4 and frames.data_ptr() < out.data_ptr() + out.numel() * 4:
+        raise MdnoError("out overlaps frames without being frames")
+    lib = _lib.load()
+    sweeps = torch.empty(lead, dtype=torch.int32, device=dev)
+    viol_in = torch.empty(lead, dtype=torch.float64, device=dev)
+    viol_out = torch.empty(lead, dtype=torch.float64, device=dev)
+    check(lib.mdnocst_project(ptr(frames) if F * N else None, ptr(out) if F * N else None, F, N, ptr(pairs) if n_c else None,
+                              ptr(lo) if n_c else None, ptr(hi) if n_c else None, n_c, ptr(colour_ptr), n_colours,
+                              ptr(weights) if weights is not None and N else None, box_arg(box) if box else None, iterations, tol,
+                              ptr(sweeps) if F else None, ptr(viol_in) if F else None, ptr(viol_out) if F else None,
+                              stream_ptr(dev)), "mdnocst_project")
+    return out, sweeps, viol_in, viol_out

@@ -87,11 +87,19 @@ class RolloutEngine:
     attributes the graph kernel wrote (a buffer [edge_cap, 6] the engine owns).  0 = an open axis; every periodic axis
     needs L >= 2 * threshold; one box for all members, constant in time.  Frames are never wrapped.  With box = None
     (the default) nothing of this is launched or captured.  `first_step_from_sample` is unchanged: the sample brings
-    its own edges (graph_kernel.construct_pairdata(..., box=))."""
+    its own edges (graph_kernel.construct_pairdata(..., box=)).
+
+    constraints = a `forecast.DistanceConstraints`: a constrained rollout (include/mdno_constrain.h
+    mdnocst_rollout_plan_set_constraints) — every step projects the frame it produces onto the
+    distance bands where it lies, after the noise and before anything reads it: up to `constraint_iterations` sweeps per
+    member, until its largest violation is at most `constraint_tol`, in the engine's own box.  The frames are those of
+    `forecast.project_constraints` applied to every produced frame before it is fed back; `constraint_report` says what
+    each step needed.  With constraints = None (the default) nothing of this is launched or captured."""
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0,
                  max_steps: int = 1000, edge_cap: Optional[int] = None, device=None, use_graph: bool = True,
-                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None):
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None, constraints=None,
+                 constraint_iterations: int = 8, constraint_tol: float = 0.0):
         self.box = check_rollout_box(model, box, threshold)
         self._box_attr = None            # f32 [edge_cap, 6] on the device, made with every plan of a periodic engine
         self._box_arg = None
@@ -113,6 +121,10 @@ class RolloutEngine:
             raise MdnoError(f"member_ids: expected {self.M} ids in [0, 2^31), got {ids[:8]}{'..' if len(ids) > 8 else ''}")
         self.member_ids = ids
         self._member_ids_dev = None      # int32 [M] on the device, made when noise is on (the plan keeps its address)
+        self.constraints, self.constraint_iterations, self.constraint_tol = self._check_constraints(
+            constraints, constraint_iterations, constraint_tol)
+        self._cst_table = None           # the coloured table on the device and the reports [max_steps, M], made when
+        self._cst_report = None          # constraints are on (the plan keeps their addresses)
         self.edge_cap = int(edge_cap) if edge_cap is not None else self.M * self.N * self.N
         self.edge_cap = max(self.edge_cap, self.M * self.N)
         # no capacity given and the complete-graph bound is large (N > 256): the capacity is fitted to the graph of
@@ -210,6 +222,8 @@ class RolloutEngine:
             self._attach_box()
         else:
             self._box_attr = None
+        if self.constraints is not None:  # (a rebuilt plan gets its constraints again, as it gets its box)
+            self._attach_constraints()
         if self._timer_records:          # the timer lived in the plan just destroyed: its records are gone, the attachment is not
             check(self.lib.mdno_rollout_plan_timer_attach(self.plan, self._timer_records), "timer_attach")
 
@@ -234,6 +248,64 @@ class RolloutEngine:
             check(self.lib.mdno_rollout_plan_set_box(self.plan, None, None), "mdno_rollout_plan_set_box")
         else:
             self._attach_box()
+
+    def _check_constraints(self, constraints, iterations, tol):
+        """(constraints or None, iterations, tol) of an engine, validated on the host; an empty list is no constraints."""
+        from .forecast import DistanceConstraints
+        iterations, tol = ops.check_projection_args(iterations, tol)
+        if constraints is None:
+            return None, iterations, tol
+        if not isinstance(constraints, DistanceConstraints):
+            raise MdnoError(f"constraints is a {type(constraints).__name__}: expected a forecast.DistanceConstraints or None")
+        constraints.check_frames(self.N)
+        if self.N > ops.CST_MAX_ATOMS:
+            raise MdnoError(f"constraints: frames of {self.N} atoms, the projection holds at most {ops.CST_MAX_ATOMS}")
+        return (constraints if len(constraints) else None), iterations, tol
+
+    def _attach_constraints(self) -> None:
+        """self.constraints, coloured on the device, and the report buffers, given to the plan."""
+        from .forecast import ConstraintReport
+        t = self.constraints.coloured(self.device)
+        if self._cst_report is None:
+            self._cst_report = ConstraintReport(torch.zeros((self.max_steps, self.M), dtype=torch.int32, device=self.device),
+                                                torch.zeros((self.max_steps, self.M), dtype=torch.float64, device=self.device),
+                                                torch.zeros((self.max_steps, self.M), dtype=torch.float64, device=self.device))
+        self._cst_table, r = t, self._cst_report
+        check(self.lib.mdnocst_rollout_plan_set_constraints(
+            self.plan, ptr(t.pairs), ptr(t.lo), ptr(t.hi), int(t.pairs.shape[0]), ptr(t.colour_ptr), t.n_colours, ptr(t.weights),
+            self.constraint_iterations, self.constraint_tol, ptr(r.sweeps), ptr(r.viol_in), ptr(r.viol_out)),
+            "mdnocst_rollout_plan_set_constraints")
+
+    def set_constraints(self, constraints, iterations: Optional[int] = None, tol: Optional[float] = None) -> None:
+        """Give the engine other distance constraints, or None for the plain step (mdnocst_rollout_plan_set_constraints:
+        with None the plan has the launches and the captured graph of one that never had constraints).  `iterations`, `tol`:
+        None keeps the engine's.  Before the first step after reset() only; later resets keep them."""
+        if self.steps_done != 0:
+            raise MdnoError("set_constraints: only before the first step after reset()")
+        self.constraints, self.constraint_iterations, self.constraint_tol = self._check_constraints(
+            constraints, self.constraint_iterations if iterations is None else iterations,
+            self.constraint_tol if tol is None else tol)
+        if not self.plan:
+            return
+        if self.constraints is None:
+            self._cst_table = None
+            check(self.lib.mdnocst_rollout_plan_set_constraints(self.plan, None, None, None, 0, None, 0, None, 0, 0.0, None, None,
+                                                                None), "mdnocst_rollout_plan_set_constraints")
+        else:
+            self._attach_constraints()
+
+    def constraint_report(self, first_step: int = 0, steps: Optional[int] = None):
+        """What the projection did to the frames of steps first_step .. first_step + steps - 1 (default: all produced) ->
+        `forecast.ConstraintReport`, sweeps i32 and viol_in / viol_out f64 [steps, M] (views of the engine's buffers, read
+        on the current stream after the engine's enqueued steps)."""
+        from .forecast import ConstraintReport
+        if self.constraints is None or self._cst_report is None:
+            raise MdnoError("constraint_report: the engine has no constraints")
+        first_step, steps = self._score_range(first_step, steps)
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        r = self._cst_report
+        sl = slice(first_step, first_step + steps)
+        return ConstraintReport(r.sweeps[sl], r.viol_in[sl], r.viol_out[sl])
 
     @property
     def steps_per_launch(self) -> int:
@@ -285,7 +357,8 @@ class RolloutEngine:
         first loop iteration does (graph_kernel.py:401-404: `dataset[start]` carries the graph of the
         window's FIRST frame, dataset.py:189-201; only later steps rebuild it on the newest frame).
         Single-member engines only; call after reset().  With noise_sigma > 0 the frame gets the noise of step 0 like
-        any other step's (the values `ops.noise_fill` gives for this member, added in the same fp32 arithmetic)."""
+        any other step's (the values `ops.noise_fill` gives for this member, added in the same fp32 arithmetic), and with
+        constraints it is then projected like any other step's (`forecast.project_constraints`; row 0 of the report)."""
         if self.M != 1 or self.steps_done != 0:
             raise MdnoError("first_step_from_sample: needs M == 1 and a freshly reset engine")
         graph = ops.coo_to_csr(edge_index.to(self.device), self.N)
@@ -295,6 +368,12 @@ class RolloutEngine:
         if self.noise_sigma > 0.0:
             out = out + ops.noise_fill(self.noise_seed, self.member_ids, 0, self.N, sigma=self.noise_sigma,
                                        device=self.device).view(self.N, 3)
+        if self.constraints is not None:     # and the projection of step 0, after the noise like any other step's
+            from .forecast import project_constraints
+            out, rep = project_constraints(out.reshape(1, self.N, 3), self.constraints, box=self.box,
+                                           iterations=self.constraint_iterations, tol=self.constraint_tol)
+            out, r = out.view(self.N, 3), self._cst_report
+            r.sweeps[0], r.viol_in[0], r.viol_out[0] = rep.sweeps, rep.viol_in, rep.viol_out
         self.traj[self.W, 0].copy_(out)
         self.edges_per_step[0] = int(edge_index.shape[1])
         torch.cuda.current_stream(self.device).synchronize()
@@ -533,7 +612,8 @@ class GroupedRolloutEngine:
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0, max_steps: int = 1000,
                  edge_cap: Optional[int] = None, device=None, use_graph: bool = True, groups: int = 2,
-                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None):
+                 noise_sigma: float = 0.0, noise_seed: int = 0, member_ids=None, box=None, constraints=None,
+                 constraint_iterations: int = 8, constraint_tol: float = 0.0):
         self.box = check_rollout_box(model, box, threshold)      # one box for every group
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
         ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
@@ -550,7 +630,9 @@ class GroupedRolloutEngine:
         self.engines = [RolloutEngine(model, hi - lo, n_atoms, window, threshold, max_steps=max_steps,
                                       edge_cap=None if edge_cap is None else max(1, -(-int(edge_cap) * (hi - lo) // self.M)),
                                       device=device, use_graph=use_graph, noise_sigma=noise_sigma, noise_seed=noise_seed,
-                                      member_ids=ids[lo:hi], box=self.box) for lo, hi in self.bounds]
+                                      member_ids=ids[lo:hi], box=self.box, constraints=constraints,
+                                      constraint_iterations=constraint_iterations, constraint_tol=constraint_tol)
+                        for lo, hi in self.bounds]           # (one constraint list, one table on the device, for every group)
         self.device = self.engines[0].device
         self.max_steps = int(max_steps)
 
@@ -595,6 +677,21 @@ class GroupedRolloutEngine:
     def step(self, steps: int) -> None:
         for e in self.engines:      # asynchronous on each engine's own stream
             e.step(steps)
+
+    @property
+    def constraints(self):
+        return self.engines[0].constraints
+
+    def set_constraints(self, constraints, iterations: Optional[int] = None, tol: Optional[float] = None) -> None:
+        """`RolloutEngine.set_constraints` for every group."""
+        for e in self.engines:
+            e.set_constraints(constraints, iterations, tol)
+
+    def constraint_report(self, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.constraint_report` of every group, members in order: a member's projection depends on its own
+        frame alone, so these are the reports of one engine holding every member."""
+        from .forecast import ConstraintReport
+        return ConstraintReport.cat([e.constraint_report(first_step, steps) for e in self.engines])
 
     def fallback_counts(self) -> dict:
         """Sum of the groups' counters (RolloutEngine.fallback_counts)."""

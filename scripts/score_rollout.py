@@ -27,11 +27,16 @@ also the internal coordinates (forecast.Featurizer.backbone(atoms, MIN_SEP, STRI
 every STRIDE-th atom at least MIN_SEP apart, pseudo-angles and pseudo-dihedrals): per member the largest and the median
 per-column total variation of its feature histograms against the truth's over the truth's own ranges, and the share of its
 bond lengths outside the truth's range; `--pca`, `--tica` and `--msm` then work on these features instead of the superposed
-Cartesian coordinates (INTEGRATION.md "Features that do not depend on a reference frame" reads them).
+Cartesian coordinates (INTEGRATION.md "Features that do not depend on a reference frame" reads them).  With
+`--constrain [MARGIN]` the free run is made a second time with distance constraints on the pseudo-bonds
+(forecast.DistanceConstraints.from_frames: each inside the truth's own range widened by MARGIN), projected at the end of every
+step (include/mdno_constrain.h), and "constrained" holds, as [free run, constrained run], the diverged members, the RMSD,
+native-fraction and Jaccard series and the share of bond lengths outside the truth's range, with the mean violation before and
+after the projection and the mean sweep count per step (INTEGRATION.md "Keeping a rollout on the chain manifold" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
-                                    [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4]
+                                    [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4] [--constrain 0.1]
 """
 import argparse
 import json
@@ -80,7 +85,13 @@ def main() -> None:
                     help="also score the internal coordinates of the backbone feature set (default 3 4): per member the largest "
                          "and median per-column total variation of the feature histograms against the truth's and the share of "
                          "bond lengths outside the truth's range; --pca/--tica/--msm then run on these features")
+    ap.add_argument("--constrain", type=float, nargs="?", const=0.0, metavar="MARGIN", default=None,
+                    help="run the free run a second time with distance constraints on the pseudo-bonds, each held inside the "
+                         "truth's own range widened by MARGIN (default 0), and print the scores of both runs side by side")
+    ap.add_argument("--constrain-iterations", type=int, default=8, help="with --constrain: sweeps per step at most")
     a = ap.parse_args()
+    if a.constrain is not None and not (a.constrain >= 0.0 and a.constrain_iterations >= 0):
+        ap.error("--constrain takes a MARGIN >= 0 and --constrain-iterations a number >= 0")
     if a.internal is not None and (len(a.internal) not in (0, 2) or any(v < 1 for v in a.internal)):
         ap.error("--internal takes no values or MIN_SEP STRIDE, both >= 1")
     if a.tica is not None and a.pca is None:
@@ -260,6 +271,35 @@ def main() -> None:
                          "msm_truth_timescales": timescales(t_counts.cpu()),
                          "msm_forecast_timescales": [timescales(f_counts, m) for m in range(M)],
                          "msm_pairs_skipped": int(f_counts.n_skipped.sum())})
+
+    if a.constrain is not None and S > 0:
+        from molecular_dynamics_neural_operator_amd import forecast as fc
+        bonds = fc.Featurizer.of(pairs=fc.DistanceConstraints.chain(N, 0.0, 1.0).pairs, n_atoms=N).to(dev)     # the pseudo-bonds
+        cons = fc.DistanceConstraints.from_frames(truth, bonds, margin=a.constrain, box=eng.box)
+        eng_c = RolloutEngine(model, M, N, W, a.threshold, max_steps=S, device=dev, noise_sigma=a.noise_sigma,
+                              noise_seed=a.noise_seed, constraints=cons, constraint_iterations=a.constrain_iterations)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng_c.run(torch.from_numpy(np.ascontiguousarray(wins.transpose(1, 0, 2, 3))), torch.from_numpy(syn.amino_acids(N, seed=1)), S)
+        torch.cuda.synchronize()
+        produce_c = time.perf_counter() - t0
+        cc, rep = eng_c.score(truth).cpu(), eng_c.constraint_report()
+        t_b = fc.internal_coordinates(truth, bonds, box=eng.box)
+        b_lo, b_hi = float(t_b.min()), float(t_b.max())
+
+        def outside(e):                                                              # share of bond lengths outside the truth's range
+            return finite(fc.feature_histograms(e.internal_coordinates(bonds), b_lo, b_hi, 1).outside().mean(1).cpu())
+        dist["constrained"] = {
+            "margin": a.constrain, "iterations": a.constrain_iterations, "constraints": len(cons), "colours": cons.coloured(dev).n_colours,
+            "members_diverged": [int((c.first_nonfinite >= 0).sum()), int((cc.first_nonfinite >= 0).sum())],
+            "mean_rmsd": [series(c.rmsd.nanmean(1)), series(cc.rmsd.nanmean(1))],
+            "mean_native_fraction": [series(c.native_fraction().nanmean(1)), series(cc.native_fraction().nanmean(1))],
+            "mean_jaccard": [series(c.jaccard().nanmean(1)), series(cc.jaccard().nanmean(1))],
+            "bond_fraction_outside_truth_range": [outside(eng), outside(eng_c)],
+            "mean_viol_in": series(rep.viol_in.mean(1).cpu()), "mean_viol_out": series(rep.viol_out.mean(1).cpu()),
+            "mean_sweeps": series(rep.sweeps.double().mean(1).cpu()),
+            "produce_s": [produce_s, produce_c], "note": "every pair is [free run, constrained run]"}
+        eng_c.close()
 
     print(json.dumps({
         "members": M, "atoms": N, "steps": S, "window": W, "threshold": a.threshold, "conv_mode": eng.conv_mode,

@@ -369,7 +369,8 @@ int mdno_unpack_tensors(int count, const mdno_flat_tensor* tensors, const float*
  *                         mdno_gemm_atb_split_f16_workspace_bytes(rows, n1, n2))
  *   mdno_colsum           out (+)= column sums of A [rows,n]                       (bias grads)
  *   mdno_relu_bwd         out = g * (y > 0) [* row_scale[row]]
- *   mdno_relu_bwd2        gz = g * (y > 0) and gs = gz * row_scale[row] in one pass (same values as two calls)
+ *   mdno_relu_bwd2        gz = g * (y > 0) and gs = gz * row_scale[row] in one pass (same values as two calls);
+ *                         n % 4 == 0 and g, y, gz, gs 16-byte aligned, MDNO_EINVAL otherwise
  *   mdno_transpose        At [cols,rows] = A [rows,cols]^T
  *   mdno_inv_degree       inv[r] = 1/max(deg_r,1) (mean) or 1 (add)
  *   mdno_nnconv_bwd_x     g_prev[r] = gz[r].root^T + sum_{e: src e = r} W_e . gs[dst e]; edges grouped by

@@ -496,6 +496,10 @@ extern "C" int mdno_relu_bwd2(const float* g, const float* y, const float* row_s
                               float* gs, void* stream) {
     MDNO_REQUIRE(g && y && row_scale && gz && gs && rows > 0 && n > 0 && n % 4 == 0, MDNO_EINVAL,
                  "mdno_relu_bwd2: bad arguments (n % 4)");
+    // the kernel reads and writes 16 bytes at a time and has no one-element form: refuse before any launch
+    MDNO_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gz) |
+                   reinterpret_cast<uintptr_t>(gs)) & 15) == 0,
+                 MDNO_EINVAL, "mdno_relu_bwd2: g, y, gz and gs must be 16-byte aligned");
     const long long quads = rows * n / 4;
     hipLaunchKernelGGL(relu_bwd2_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), g, y, row_scale, gz, gs, (long long)rows, n);

@@ -438,12 +438,18 @@ def _ws(nbytes: int, dev) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
+def _aligned16(*tensors) -> bool:
+    """What the split-plane entry points ask of their operands (a contiguous view may start anywhere in its buffer)."""
+    return all(t.data_ptr() % 16 == 0 for t in tensors)
+
+
 def linear(a: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], relu: bool = False,
            gemm_mode: str = "f32") -> torch.Tensor:
     """act(a . w^T + b): a [rows,k], w [n,k] (torch Linear layout).  gemm_mode "split_bf16" runs the
     product on the bf16 matrix pipe with the exact 3-way split (fp32-level error), "split_f16" on two fp16
     planes per operand with every row scaled by its own power of two (3 products instead of 6, fp32-level
-    error), where the shape tiles (k % 32 == 0, n % 128 == 0); other shapes and "f32" use the fp32 kernels."""
+    error), where the shape tiles (k % 32 == 0, n % 128 == 0) and a, w are 16-byte aligned; other shapes, misaligned
+    views and "f32" use the fp32 kernels."""
     lib = _lib.load()
     a, w = f32(a), f32(w)
     rows, k = a.shape
@@ -452,12 +458,13 @@ def linear(a: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], relu: bo
     if rows == 0:               # (an edge network over a graph without edges)
         return c
     bb = f32(b) if b is not None else None
-    if gemm_mode == "split_f16" and k % 32 == 0 and n % 128 == 0 and rows > 0:
+    tiles = k % 32 == 0 and n % 128 == 0 and rows > 0 and _aligned16(a, w)
+    if gemm_mode == "split_f16" and tiles:
         ws = _ws(lib.mdno_linear_split_f16_workspace_bytes(rows, n, k), a.device)
         check(lib.mdno_linear_split_f16_fwd(ptr(a), ptr(w), ptr(bb), rows, n, k, int(relu), ptr(c), ptr(ws), ws.numel(),
                                             stream_ptr(a.device)), "mdno_linear_split_f16_fwd")
         return c
-    if gemm_mode != "f32" and k % 32 == 0 and n % 128 == 0 and rows > 0:
+    if gemm_mode != "f32" and tiles:
         ws = _ws(lib.mdno_linear_split_workspace_bytes(rows, n, k), a.device)
         check(lib.mdno_linear_split_fwd(ptr(a), ptr(w), ptr(bb), rows, n, k, int(relu), ptr(c), ptr(ws), ws.numel(),
                                         stream_ptr(a.device)), "mdno_linear_split_fwd")
@@ -470,7 +477,7 @@ def linear(a: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], relu: bo
 def gemm_atb(a: torch.Tensor, b: torch.Tensor, gemm_mode: str = "f32") -> torch.Tensor:
     """a^T . b over rows: a [rows,n1], b [rows,n2] -> [n1,n2] (fixed-order partial sums).  gemm_mode "split_f16":
     on two fp16 planes per operand, columns scaled by powers of two (fp32-level error), where the shape tiles
-    (n1, n2 multiples of 256); otherwise the exact fp32 MFMA."""
+    (n1, n2 multiples of 256) and a, b are 16-byte aligned; otherwise the fp32 kernels."""
     lib = _lib.load()
     a, b = f32(a), f32(b)
     rows, n1 = a.shape
@@ -478,7 +485,7 @@ def gemm_atb(a: torch.Tensor, b: torch.Tensor, gemm_mode: str = "f32") -> torch.
     c = torch.empty((n1, n2), dtype=torch.float32, device=a.device)
     if rows == 0:               # an empty sum
         return c.zero_()
-    if gemm_mode == "split_f16" and lib.mdno_gemm_atb_split_f16_supported(rows, n1, n2):
+    if gemm_mode == "split_f16" and lib.mdno_gemm_atb_split_f16_supported(rows, n1, n2) and _aligned16(a, b):
         ws = _ws(lib.mdno_gemm_atb_split_f16_workspace_bytes(rows, n1, n2), a.device)
         check(lib.mdno_gemm_atb_split_f16(ptr(a), ptr(b), rows, n1, n2, ptr(c), 0, ptr(ws), ws.numel(), stream_ptr(a.device)),
               "mdno_gemm_atb_split_f16")

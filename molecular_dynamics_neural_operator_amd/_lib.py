@@ -292,6 +292,14 @@ CONSTRAIN_SIGNATURES = {
     "mdnocst_rollout_plan_set_constraints": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _I, _D, _P, _P, _P]),
 }
 
+# include/mdno_pbc_train.h (training under a periodic box: edge attributes as a function of positions on the minimum
+# image; additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
+# (tests/test_pbc_train_host.py checks both ways).  The name starts with mdnopbt_, for the reason mdnoens_ has (the
+# header says so too).  `box` is a HOST pointer to three doubles.
+PBC_TRAIN_SIGNATURES = {
+    "mdnopbt_edge_attr_from_pos": (_I, [_P, _P, _P, _P, _L, _I, _D, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -326,7 +334,8 @@ def load() -> C.CDLL:
             list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
             list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
             list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + \
-            list(INTERNAL_GRAD_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()):
+            list(INTERNAL_GRAD_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()) + \
+            list(PBC_TRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

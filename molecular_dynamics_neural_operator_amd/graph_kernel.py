@@ -608,19 +608,29 @@ def _unwrap(model):
 
 
 def recursive_propagation(model, dataset, device, num_steps: int, starting_points: list,
-                          threshold: float = 8.0) -> List[PairData]:
+                          threshold: float = 8.0, box=None) -> List[PairData]:
     """Autoregressive rollout from each starting sample; returns the per-step ``PairData`` (on the
-    CPU, like the reference).  The loop itself runs on the device (rollout.RolloutEngine)."""
-    from .rollout import RolloutEngine
+    CPU, like the reference).  The loop itself runs on the device (rollout.RolloutEngine).
+
+    ``box`` = (Lx, Ly, Lz): a periodic rollout (``RolloutEngine(box=)``).  The first step still runs on the sample's
+    own edges — those of a periodic sample, ``construct_pairdata(..., box=)`` — and every returned ``PairData`` carries
+    what ``construct_pairdata(window, aa, threshold, box=box)`` gives: the minimum-image graph of the window's newest
+    frame, ``edge_index[0]`` = sources, imaged attributes.  With box None the open code path runs as it is."""
+    from .rollout import RolloutEngine, check_rollout_box
     net = _unwrap(model)
+    box = check_rollout_box(net, box, threshold)
     net.eval()
     forecasts: List[PairData] = []
     for start in starting_points:
         sample = dataset[start]
         win = sample.x_position if sample.x_position.dim() == 3 else sample.x_position.unsqueeze(0)
         W, N, _ = win.shape
-        eng = RolloutEngine(net, members=1, n_atoms=N, window=W, threshold=threshold, max_steps=num_steps,
-                            device=device)
+        if box is None:
+            eng = RolloutEngine(net, members=1, n_atoms=N, window=W, threshold=threshold, max_steps=num_steps,
+                                device=device)
+        else:
+            eng = RolloutEngine(net, members=1, n_atoms=N, window=W, threshold=threshold, max_steps=num_steps,
+                                device=device, box=box)
         eng.reset(win.unsqueeze(1), sample.x_aminoacid)
         if num_steps > 0:
             # iteration 0 runs on the sample's own graph (first window frame), later ones on the
@@ -630,15 +640,17 @@ def recursive_propagation(model, dataset, device, num_steps: int, starting_point
         eng.synchronize()
         traj = eng.frames()                                                      # [steps,1,N,3]
         frames = torch.cat([win.to(traj.device), traj[:, 0]], dim=0)             # [W+steps,N,3]
-        forecasts.extend(_pairdata_of_windows(frames, W, num_steps, sample.x_aminoacid, threshold))
+        forecasts.extend(_pairdata_of_windows(frames, W, num_steps, sample.x_aminoacid, threshold, box))
     return forecasts
 
 
-def _pairdata_of_windows(frames: torch.Tensor, W: int, num_steps: int, x_aminoacid, threshold: float) -> List[PairData]:
+def _pairdata_of_windows(frames: torch.Tensor, W: int, num_steps: int, x_aminoacid, threshold: float,
+                         box=None) -> List[PairData]:
     """``construct_pairdata(frames[i+1 : i+1+W]).to("cpu")`` for i = 0 .. num_steps-1 (what the reference returns per
     step, graph_kernel.py:406-412), with the graphs of many steps built in ONE launch — every newest frame is a
     "member" of one radius-graph call — and one device-to-host copy per tensor: at N = 28 a step of the rollout takes
-    0.1 ms, a graph + four copies per step took longer than that."""
+    0.1 ms, a graph + four copies per step took longer than that.  Under ``box`` the one launch is the periodic graph with
+    its imaged attribute rows, and a step's ``PairData`` is ``construct_pairdata(..., box=box)``'s: sources first."""
     N = frames.shape[1]
     aa = x_aminoacid.cpu() if torch.is_tensor(x_aminoacid) else x_aminoacid
     frames_cpu = frames.cpu()
@@ -648,26 +660,34 @@ def _pairdata_of_windows(frames: torch.Tensor, W: int, num_steps: int, x_aminoac
         s1 = min(num_steps, s0 + chunk)
         last = frames[s0 + W:s1 + W].contiguous()                    # newest frame of windows s0 .. s1-1: [S,N,3]
         S = s1 - s0
-        g = ops.radius_graph(last.reshape(S * N, 3), N, threshold)
-        e = g.edge_count()
-        dst, src = g.dst[:e].long(), g.src[:e].long()
-        flat = last.reshape(S * N, 3)
-        edge_attr = torch.cat([flat[dst], flat[src]], dim=1).cpu()   # [pos[row], pos[col]] as construct_pairdata
+        if box is not None:
+            g, attr = ops.radius_graph_pbc(last.reshape(S * N, 3), N, threshold, box)
+            e = g.edge_count()
+            dst, src = g.dst[:e].long(), g.src[:e].long()
+            edge_attr = attr[:e].cpu()                                # [image of pos[src] next to dst, pos[dst]]
+        else:
+            g = ops.radius_graph(last.reshape(S * N, 3), N, threshold)
+            e = g.edge_count()
+            dst, src = g.dst[:e].long(), g.src[:e].long()
+            flat = last.reshape(S * N, 3)
+            edge_attr = torch.cat([flat[dst], flat[src]], dim=1).cpu()   # [pos[row], pos[col]] as construct_pairdata
         offs = g.row_ptr[::N].cpu().tolist()                          # first edge of every member (and the total)
         dst, src = dst.cpu(), src.cpu()
         for m in range(S):
             a, b = offs[m], offs[m + 1]
-            ei = torch.stack([dst[a:b] - m * N, src[a:b] - m * N])
+            ei = torch.stack([dst[a:b] - m * N, src[a:b] - m * N]) if box is None else \
+                torch.stack([src[a:b] - m * N, dst[a:b] - m * N])
             i = s0 + m
             out.append(PairData(x_aminoacid=aa, x_position=frames_cpu[i + 1:i + 1 + W].clone(),
                                 edge_attr=edge_attr[a:b].clone(), edge_index=ei))
     return out
 
 
-def propogate(model, dataset, device, num_steps: int, threshold: float = 8.0):
+def propogate(model, dataset, device, num_steps: int, threshold: float = 8.0, box=None):
     """Notebook rollout: starts at ``dataset[0]`` and also records the per-step MSE against
-    ``dataset[i+1].x_position`` (bba_analysis.ipynb:351)."""
-    forecasts = recursive_propagation(model, dataset, device, num_steps, [0], threshold)
+    ``dataset[i+1].x_position`` (bba_analysis.ipynb:351).  ``box``: as ``recursive_propagation``."""
+    forecasts = recursive_propagation(model, dataset, device, num_steps, [0], threshold) if box is None else \
+        recursive_propagation(model, dataset, device, num_steps, [0], threshold, box=box)
     metrics = defaultdict(list)
     for i, f in enumerate(forecasts):
         truth = dataset[i + 1].x_position

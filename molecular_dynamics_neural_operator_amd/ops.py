@@ -987,6 +987,20 @@ def collate_samples(pos: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor, m
     return x_position, y, edge_index, edge_attr
 
 
+def collate_positions(pos: torch.Tensor, meta: torch.Tensor, B: int, N: int, W: int, horizon: int):
+    """The positions launch of mdno_collate_samples alone (max_edges_per_sample = 0: its edge launch does not run) ->
+    (x_position [W,B*N,3], y [B*N,3]) — for batches whose edges do not come from a stored list (a periodic
+    DeviceTrajectory).  The edge arguments are one small buffer nothing reads or writes: the entry refuses null."""
+    lib = _lib.load()
+    dev = pos.device
+    x_position = torch.empty((W, B * N, 3), dtype=torch.float32, device=dev)
+    y = torch.empty((B * N, 3), dtype=torch.float32, device=dev)
+    unused = torch.empty(8, dtype=torch.int64, device=dev)
+    check(lib.mdno_collate_samples(ptr(pos), ptr(unused), ptr(unused), ptr(meta), B, N, W, horizon, 0, ptr(x_position),
+                                   ptr(y), ptr(unused), ptr(unused), stream_ptr(dev)), "mdno_collate_samples")
+    return x_position, y
+
+
 def collate_targets(pos: torch.Tensor, meta: torch.Tensor, B: int, N: int, W: int, horizon: int, steps: int) -> torch.Tensor:
     """Targets of an unrolled step (include/mdno_unroll.h mdno_collate_targets): y f32 [steps, B*N, 3], step k of sample
     b = frame meta[b] + W + horizon - 1 + k of the resident trajectory `pos` [T,N,3]; one launch."""
@@ -1022,13 +1036,25 @@ def edge_mlp_input_bwd(gz1: torch.Tensor, w0: torch.Tensor, num_edges: torch.Ten
     return out
 
 
-def edge_attr_from_pos(pos: torch.Tensor, graph: CSRGraph) -> torch.Tensor:
+def edge_attr_from_pos(pos: torch.Tensor, graph: CSRGraph, box=None, cutoff: float = 8.0) -> torch.Tensor:
     """edge_attr f32 [E, 6] = [pos[src p], pos[dst p]] in the graph's CSR edge order (mdno_edge_attr_from_pos): the
-    attributes the forward forms from `edge_pos` for the same graph."""
+    attributes the forward forms from `edge_pos` for the same graph.
+    `box` = (Lx, Ly, Lz) with a periodic axis: the source is moved to its minimum image next to the destination
+    (include/mdno_pbc_train.h mdnopbt_edge_attr_from_pos; `cutoff` only validates the box, as everywhere) — on a graph
+    from `radius_graph_pbc` of the same positions, the rows that call wrote, bit for bit.  box None or all zero: the
+    open call, untouched."""
+    box = check_box(box, cutoff)
     lib = _lib.load()
     pos = f32(pos).reshape(-1, 3)
     E = graph.edge_count()
     ea = torch.empty((E, 6), dtype=torch.float32, device=pos.device)
+    if box is not None:
+        if E:
+            b = box_arg(box)
+            check(lib.mdnopbt_edge_attr_from_pos(ptr(pos), ptr(graph.src), ptr(graph.dst), ptr(graph.num_edges), E,
+                                                 pos.shape[0], float(cutoff), b, ptr(ea), stream_ptr(pos.device)),
+                  "mdnopbt_edge_attr_from_pos")
+        return ea
     if E:
         check(lib.mdno_edge_attr_from_pos(ptr(pos), ptr(graph.src), ptr(graph.dst), ptr(graph.num_edges), E, pos.shape[0],
                                           ptr(ea), stream_ptr(pos.device)), "mdno_edge_attr_from_pos")

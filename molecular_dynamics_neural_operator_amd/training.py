@@ -194,19 +194,25 @@ class FcOut(torch.autograd.Function):
 class EdgeAttrFromPositions(torch.autograd.Function):
     """edge_attr [E, 6] = [pos[src p], pos[dst p]] in `graph`'s CSR edge order, differentiable in `pos` [R, 3]
     (include/mdno_unroll.h mdno_edge_attr_from_pos / mdno_edge_attr_pos_bwd).  The graph is data: no gradient goes
-    through its topology.  `graph.by_src` (ops.source_sorted) is used by the backward where it is already there."""
+    through its topology.  `graph.by_src` (ops.source_sorted) is used by the backward where it is already there.
+    `box` (with `cutoff`, which only validates it): the source half of every row is the source's minimum image next to
+    the destination, pos[src p] - k L (include/mdno_pbc_train.h).  The shift k L is a constant of the edge — k is
+    piecewise constant in the positions, and no gradient goes through it, as none goes through the topology — so the
+    backward is the open one, the same kernel on the same arguments."""
 
     @staticmethod
-    def forward(ctx, pos, graph):
+    def forward(ctx, pos, graph, box=None, cutoff=8.0):
         ctx.graph, ctx.rows = graph, pos.reshape(-1, 3).shape[0]
         ctx.shape = tuple(pos.shape)
-        return ops.edge_attr_from_pos(pos, graph)
+        if box is None:
+            return ops.edge_attr_from_pos(pos, graph)
+        return ops.edge_attr_from_pos(pos, graph, box, cutoff)
 
     @staticmethod
     def backward(ctx, g):
         graph = ctx.graph
         by_src = getattr(graph, "by_src", None) or ops.source_sorted(graph, ctx.rows)
-        return ops.edge_attr_pos_bwd(g.contiguous(), graph, by_src, ctx.rows).view(ctx.shape), None
+        return ops.edge_attr_pos_bwd(g.contiguous(), graph, by_src, ctx.rows).view(ctx.shape), None, None, None
 
 
 _PROLOGUE_KEYS = ("lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "lstm_fc.weight",
@@ -233,9 +239,19 @@ class DeviceTrajectory:
     host only fills a 3*B+1 word table from the dataset's offsets — no per-sample Python, no per-sample H2D
     copies, no device->host read.  `batch(indices)` returns a collated `PairData` (time-major x_position
     [W,B*N,3], y, edge_index, edge_attr, x_aminoacid tiled) whose samples are `dataset[i]` for i in indices,
-    in that order — the same tensors `collate([dataset[i] ...])` builds on the host (tested bitwise)."""
+    in that order — the same tensors `collate([dataset[i] ...])` builds on the host (tested bitwise).
 
-    def __init__(self, dataset, device):
+    `box` = (Lx, Ly, Lz) (with `cutoff`; include/mdno_pbc.h): the trajectory lies in a periodic cell.  The stored
+    contact maps are then not used: a sample's edges are the minimum-image radius graph of its first window frame
+    (frame idx, the frame whose stored map the open path uses) and its attributes that graph's imaged rows — what
+    `construct_pairdata(window[:1], aa, cutoff, box=box)` gives per sample on the host, `edge_index[0]` = sources,
+    sorted by target.  The edges of every stored frame are counted once, here (one read-back), so `batch()` sizes its
+    buffers without reading the device, as on the open path; the batch carries `box` and `cutoff`, which
+    `unrolled_forward` takes from it.  With box None (or all zero) every line below runs as it always has."""
+
+    def __init__(self, dataset, device, box=None, cutoff: float = 8.0):
+        self.box = ops.check_box(box, cutoff)
+        self.cutoff = float(cutoff)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise MdnoError("DeviceTrajectory needs a GPU device (no CPU fallback)")
@@ -243,13 +259,17 @@ class DeviceTrajectory:
         self.length = len(dataset)
         pos = np.ascontiguousarray(dataset.edge_attrs, dtype=np.float32)                  # [T,N,3]
         self.N = int(pos.shape[1])
-        cms = [np.asarray(c).reshape(2, -1) for c in dataset.edge_indices]
-        counts = np.array([c.shape[1] for c in cms], dtype=np.int64)
-        self.counts = counts
-        self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.pos = torch.from_numpy(pos).to(self.device)
-        self.rows = torch.from_numpy(np.concatenate([c[0] for c in cms]).astype(np.int32)).to(self.device)
-        self.cols = torch.from_numpy(np.concatenate([c[1] for c in cms]).astype(np.int32)).to(self.device)
+        if self.box is None:
+            cms = [np.asarray(c).reshape(2, -1) for c in dataset.edge_indices]
+            counts = np.array([c.shape[1] for c in cms], dtype=np.int64)
+            self.counts = counts
+            self.offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            self.rows = torch.from_numpy(np.concatenate([c[0] for c in cms]).astype(np.int32)).to(self.device)
+            self.cols = torch.from_numpy(np.concatenate([c[1] for c in cms]).astype(np.int32)).to(self.device)
+        else:
+            self.counts = self._count_periodic_edges()
+            self.offsets = self.rows = self.cols = None
         self.x_aminoacid = dataset.x_aminoacid.to(self.device)
         self._aa_tiled = {}
         # the per-batch index table travels through a ring of PINNED host buffers: the upload is asynchronous, and a
@@ -258,6 +278,19 @@ class DeviceTrajectory:
         self._meta_ring, self._meta_slot = [], 0
 
     _META_SLOTS = 4
+
+    def _count_periodic_edges(self) -> np.ndarray:
+        """Edges of the minimum-image radius graph of every stored frame, i64 [T] on the host: chunks of frames as the
+        members of one topology-only graph call (at most 64M edge slots each, as graph_kernel._pairdata_of_windows),
+        a frame's count = the difference of its first and the next frame's first row pointer."""
+        T, N = int(self.pos.shape[0]), self.N
+        chunk = max(1, min(T, (64 << 20) // max(N * N, 1)))
+        counts = []
+        for t0 in range(0, T, chunk):
+            frames = self.pos[t0:t0 + chunk]
+            g, _ = ops.radius_graph_pbc(frames.reshape(-1, 3), N, self.cutoff, self.box, with_attr=False)
+            counts.append(torch.diff(g.row_ptr[::N]))
+        return torch.cat(counts).cpu().numpy().astype(np.int64)           # the one read-back
 
     def _meta_buffer(self, words: int):
         if len(self._meta_ring) < self._META_SLOTS:
@@ -294,7 +327,9 @@ class DeviceTrajectory:
         noise_std > 0: the input windows (`x_position` only — `y`, `edge_attr` and `edge_index` stay clean) get
         noise_std * z(noise_seed, sample index, epoch, frame, atom, component) added on the device (include/mdno_noise.h
         mdno_noise_add_window).  The key is the sample's index in the dataset: a sample's noise does not depend on the
-        batch it is in, the batch size or the rank.  The batch carries `sample_ids` / `rows_per_sample` either way."""
+        batch it is in, the batch size or the rank.  The batch carries `sample_ids` / `rows_per_sample` either way.
+        Under a box (`DeviceTrajectory(box=)`): `edge_index` [2, E] holds the sources in row 0 (sorted by target, sources
+        ascending), `edge_attr` the imaged rows, and the batch carries `box` and `cutoff` (`_periodic_batch`)."""
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= self.length:
             raise IndexError(f"sample indices must lie in [0, {self.length})")
@@ -307,6 +342,8 @@ class DeviceTrajectory:
             raise IndexError(f"unroll={K}: sample indices must lie in [0, {self.length - K}] (the last target is frame "
                              f"index + window + {K - 1})")
         B = int(idx.size)
+        if self.box is not None:
+            return self._periodic_batch(idx, B, K, noise_std, noise_seed, epoch)
         cnt = self.counts[idx]
         slot = self._meta_buffer(3 * B + 1)
         meta = slot[0][:3 * B + 1].numpy()
@@ -329,6 +366,33 @@ class DeviceTrajectory:
             out.y_unroll = ops.collate_targets(self.pos, meta_d, B, self.N, self.W, self.horizon, K)
         else:
             out.y_unroll = y.unsqueeze(0)
+        if float(noise_std) != 0.0:
+            out.x_position = add_window_noise(out, noise_std, noise_seed, epoch)
+        return out
+
+    def _periodic_batch(self, idx: np.ndarray, B: int, K: int, noise_std: float, noise_seed: int, epoch: int) -> PairData:
+        """`batch` under a box: positions and targets by the launches of the open path (mdno_collate_samples without its
+        edge launch, mdno_collate_targets), the edges and their imaged attributes by ONE periodic radius graph of the B
+        clean first frames (members of one call), sized by the counts taken at construction — nothing is read back.
+        Noise perturbs `x_position` only, after the graph is built."""
+        E = int(self.counts[idx].sum())
+        slot = self._meta_buffer(3 * B + 1)
+        meta = slot[0][:3 * B + 1].numpy()
+        meta[:B] = idx
+        meta[B:] = 0                      # (no stored edge list: offsets and cumulative counts are not read)
+        meta_d = slot[0][:3 * B + 1].to(self.device, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(self.device))
+        xp, y = ops.collate_positions(self.pos, meta_d, B, self.N, self.W, self.horizon)
+        g, attr = ops.radius_graph_pbc(xp[0], self.N, self.cutoff, self.box, edge_cap=E)
+        if B not in self._aa_tiled:
+            self._aa_tiled[B] = self.x_aminoacid.repeat(B)
+        out = PairData(x_aminoacid=self._aa_tiled[B], x_position=xp, y=y, edge_attr=attr[:E],
+                       edge_index=torch.stack([g.src[:E], g.dst[:E]]).to(torch.long))
+        out.num_graphs = B
+        out.sample_ids, out.rows_per_sample = idx.copy(), self.N
+        out.box, out.cutoff = self.box, self.cutoff
+        out.y_unroll = ops.collate_targets(self.pos, meta_d, B, self.N, self.W, self.horizon, K) if K > 1 else y.unsqueeze(0)
         if float(noise_std) != 0.0:
             out.x_position = add_window_noise(out, noise_std, noise_seed, epoch)
         return out
@@ -504,7 +568,26 @@ def _forward_step(model, xp, aa, B: int, edge_index=None, edge_attr=None, graph=
     return FcOut.apply(x, model.fc2.weight, model.fc2.bias), graph
 
 
-def unrolled_forward(model, batch, steps: int, cutoff: float = 8.0, detach: bool = False):
+def _unroll_box(model, batch, cutoff: float, box):
+    """The box an unrolled step on `batch` runs in — `box`, by default the one the batch was collated in
+    (`DeviceTrajectory(box=)` batches carry it) — as ops.check_box returns it, or None for the open step.  Host checks
+    only: a box or cutoff other than the batch's own, or a model that does not read six edge attributes
+    (rollout.check_rollout_box's rule), raises MdnoError."""
+    own = getattr(batch, "box", None)
+    if box is None and own is None:
+        return None
+    from .rollout import check_rollout_box
+    box = check_rollout_box(model, own if box is None else box, cutoff)
+    if own is not None:
+        if float(cutoff) != float(batch.cutoff):
+            raise MdnoError(f"unrolled_forward: cutoff={cutoff}, but the batch was collated with cutoff={batch.cutoff} "
+                            f"(its first step's edges were built with it)")
+        if box != ops.check_box(own, batch.cutoff):
+            raise MdnoError(f"unrolled_forward: box={box}, but the batch was collated in box={tuple(own)}")
+    return box
+
+
+def unrolled_forward(model, batch, steps: int, cutoff: float = 8.0, detach: bool = False, box=None):
     """`steps` model steps from a training window, each prediction fed back as `recursive_propagation` does
     (graph_kernel.py: the window slides by one frame, the new frame's radius graph and edge attributes replace the
     stored ones) -> (outs, graphs): `outs[k]` [B*N, 3] is the prediction of frame t + 1 + k, `graphs[k]` the CSRGraph
@@ -515,11 +598,17 @@ def unrolled_forward(model, batch, steps: int, cutoff: float = 8.0, detach: bool
     Step 1 is `train_forward(model, batch)` on the dataset's stored edge list and attributes; `train_conv_mode` is
     resolved per step on that step's edge count.  Every fed-back step reads its edge count back from the device
     (one device-to-host word: its buffers are sized by it) — the one place the training path waits for the device.
-    The model predicts frames at horizon 1; `batch` is one sample, a list, or a collated batch of B samples."""
+    The model predicts frames at horizon 1; `batch` is one sample, a list, or a collated batch of B samples.
+    `box` (default: the box a `DeviceTrajectory(box=)` batch carries): a periodic cell.  Every fed-back step then runs
+    on the minimum-image radius graph of its frame (`ops.radius_graph_pbc`, topology only) with the imaged attributes
+    `EdgeAttrFromPositions.apply(frame, graph, box, cutoff)`; the shift of an edge is data, like the edge itself, so
+    the backward launches what the open one does.  A box or cutoff other than the batch's own raises.  Without a box the
+    function launches exactly what it always has."""
     steps = int(steps)
     if steps < 1:
         raise MdnoError(f"unrolled_forward: steps={steps} (>= 1)")
     batch = collate(batch) if not isinstance(batch, PairData) else batch
+    box = _unroll_box(model, batch, cutoff, box)
     W = batch.x_position.shape[0] if batch.x_position.dim() == 3 else 1
     feeds_grad = steps > 1 and not detach and torch.is_grad_enabled()
     check_trainable(model, W, input_grad=feeds_grad or _wants_grad(batch.x_position) or _wants_grad(batch.edge_attr))
@@ -541,11 +630,14 @@ def unrolled_forward(model, batch, steps: int, cutoff: float = 8.0, detach: bool
     for _ in range(1, steps):
         frame = out.detach() if detach else out
         xp = torch.cat([xp[1:], frame.unsqueeze(0)], dim=0)
-        rg = ops.radius_graph(frame.detach(), R // B, cutoff)
+        if box is None:
+            rg = ops.radius_graph(frame.detach(), R // B, cutoff)
+        else:
+            rg, _ = ops.radius_graph_pbc(frame.detach(), R // B, cutoff, box, with_attr=False)
         E = rg.edge_count()                                # the device->host read of this step
         cap = max(E, 1)
         graph = ops.CSRGraph(rg.row_ptr, rg.src[:cap], rg.dst[:cap], rg.num_edges, cap, None, rg.status, n_edges=E)
-        ea = EdgeAttrFromPositions.apply(frame, graph)
+        ea = EdgeAttrFromPositions.apply(frame, graph) if box is None else EdgeAttrFromPositions.apply(frame, graph, box, cutoff)
         out, graph = _forward_step(model, xp, aa, B, edge_attr=ea, graph=graph)
         outs.append(out)
         graphs.append(graph)
@@ -619,7 +711,9 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
     unroll = K > 1: every batch — collated by `DeviceTrajectory.batch(indices, unroll=K)`, which adds the K true frames
     `y_unroll` — trains on `unrolled_forward(model, batch, K, cutoff, detach=unroll_detach)`: the loss is the mean over
     the K steps of `loss_fn(out_k, y_k)`, and the returned pair is that mean and the mean MSE of the K steps.  unroll = 1
-    is the one-step path: the same launches, the same bits."""
+    is the one-step path: the same launches, the same bits.
+    Periodic batches (`DeviceTrajectory(box=)`) pass through as they are: a batch knows its box and cutoff, the noisy
+    copy keeps them, and `cutoff` must be the batches' own when `unroll > 1`."""
     K = int(unroll)
     if K < 1:
         raise MdnoError(f"unroll={unroll} (>= 1)")
@@ -641,6 +735,9 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
             batch.num_graphs = getattr(clean, "num_graphs", 1)
             batch.x_position = add_window_noise(clean, noise_std, noise_seed, epoch)
             if K > 1:
+                batch.y_unroll = getattr(clean, "y_unroll", None)
+            if getattr(clean, "box", None) is not None:      # a periodic batch: the rebuilt one stays periodic
+                batch.box, batch.cutoff = clean.box, clean.cutoff
                 batch.y_unroll = getattr(clean, "y_unroll", None)
         if K > 1:
             l2, mse = _unrolled_loss(model, batch, B, K, loss_fn, cutoff, unroll_detach)

@@ -31,10 +31,15 @@
 //                         contraction index SLOWEST, and the MFMA fragments come out of gfx950's transposing read
 //                         ds_read_b64_tr_b16; register prefetch of the next stage under the MFMAs.  One more workgroup
 //                         per destination sums the neighbours' features (s0, the b3 term).
-//   K2  project_kernel / project_f16_kernel
-//                         workgroup = (256 destinations, 1/128 of the 64 k contraction): S tiles fp32 -> planes on the
-//                         fly, W3R's likewise (bf16) or pre-split (fp16); partial sums per K slice.
-//   K3  finish_kernel     per destination: K slices added in slice order, root / bias / mean / ReLU.
+//   K2  project_kernel    workgroup = (256 destinations, 1/128 of the 64 k contraction): S tiles fp32 -> planes on the
+//                         fly, W3R's likewise (bf16); one partial sum per K slice, 128 per destination.
+//       project_f16_kernel
+//                         workgroup = (64 destinations, chain es of 32): the four slices es + 32 u of the same 128, one
+//                         behind the other, W3R pre-split (fp16); the four slice partials added in registers in slice
+//                         order: one partial per chain, 32 per destination.
+//   K3  finish_kernel<PPC>  per destination: the tree "128 slices, chain es = slices es + 32 u in order, chains in
+//                         order" — both levels behind the slice partials (PPC = 4), the second behind
+//                         project_f16_kernel's chain partials (PPC = 1) —, then root / bias / mean / ReLU.
 // Fixed summation orders everywhere: a destination's result depends on its own edges only (bitwise the same alone or
 // in any batch), no float atomics.
 #include <type_traits>
@@ -554,7 +559,12 @@ __global__ __launch_bounds__(256) void moment_f32_kernel(const float* __restrict
 // fp32 K-tiles of both operands (S rows, W3R rows) are split into three bf16 planes on the fly and staged in
 // XOR-swizzled 64-B LDS rows; six plane products per pair.  PJ_SLICES is a constant and a slice's k-tiles a function of k alone: the association of a destination's
 // sum does not depend on the launch.  The last slice also takes the two s0 k-tiles (x B3).
+// The tree over a destination's slices, in every GEMM mode: 128 slices, chain es (of FN_CHAINS = 32) = slices es + 32 u,
+// u = 0..3, added in that order from 0; the 32 chains added in chain order.  project_kernel<256> and project_f32_kernel
+// store the 128 slice partials and finish_kernel<4> does both levels; project_f16_kernel does the first level itself
+// (its workgroup owns a chain) and stores the 32 chain partials for finish_kernel<1>.
 constexpr int PJ_SLICES = 128;
+constexpr int FN_CHAINS = 32;
 // 256 destinations per workgroup: two 128-row tiles of the S image against ONE W3R tile —
                                    // a CU streams at ~23.5 GB/s whatever the source, and with 128 rows a third of what
                                    // went through it was W3R (L2 hits): 34 us; (64 rows: 43 us)
@@ -678,133 +688,166 @@ __global__ __launch_bounds__(PJ_ROWS * 2) void project_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------- K2 on two fp16 planes (gemm_mode SPLIT_F16)
-// project_kernel's loop with half the matrix work: S's rows times the power of two that puts the row's largest entry
+// project_kernel's products with half the matrix work: S's rows times the power of two that puts the row's largest entry
 // (rowmax: K1's record, one value per column block of the row) in [2^13, 2^14), split into two fp16 planes on the way
 // to LDS; W3R comes pre-split (w3_planes_f16_kernel: 16 B per thread and plane tile, no vector work); three plane
-// products per pair in ONE accumulator; the epilogue takes both scales out again (exact powers of two).  The same slices, the
-// same partials layout, the same fixed association as project_kernel.
-__global__ __launch_bounds__(512) void project_f16_kernel(const float* __restrict__ S, const unsigned short* __restrict__ w3h_bits,
-                                                          float* __restrict__ part, int K, int cnt, int row0,
+// products per pair in ONE accumulator; both scales are taken out again at a slice's end (exact powers of two).
+// Workgroup (64 destinations, chain es of FN_CHAINS): the same 128 slices and the same fixed association as
+// project_kernel + finish_kernel<4> — the workgroup runs the chain's four slices es, es + 32, es + 64, es + 96 one behind
+// the other, every slice from a zeroed accumulator over its k-tiles in ascending order, and adds the four slice
+// partials in registers in that order (chain = 0; chain += p): the first level of K3's tree.  It stores ONE partial per
+// chain — part[es] of the 128-slice array, a quarter of it — and finish_kernel<1> adds the 32 chains in chain order.
+// 256 workgroups at 504 destinations as with (256 rows, slice), and every byte of S is still read by one workgroup.
+constexpr int PJ_CHAIN_ROWS = 64;
+// register sets of one stage (two k-tiles, 64 B per thread) each: 64 KiB on their way per workgroup.  Measured at 504
+// destinations, k = 1024 (EXPERIMENTS, the chain-partials section): 2 sets 30.3-30.8 us per launch by events, 4 sets 31.2, 6 sets 32.4-33.3 —
+// more bytes in flight do not help here (W3R, L2 hits, is half of what comes into the CU); the cause was not looked for
+constexpr int PJ_F16_SETS = 2;
+static_assert(PJ_SLICES == 4 * FN_CHAINS && PJ_F16_SETS % 2 == 0, "project_f16_kernel: four slices per chain, two LDS buffers");
+__global__ __launch_bounds__(512) void project_f16_kernel(const float* S, const unsigned short* w3h_bits,
+                                                          float* part, int K, int cnt, int row0,
                                                           long long part_stride, const float* __restrict__ rowmax, int nq,
                                                           const float* __restrict__ colinv) {
     // (w3h_bits: the fp16 planes as raw 16-bit words — a _Float16 in the signature leaves the name mangled in traces)
-    const _Float16* __restrict__ w3h = reinterpret_cast<const _Float16*>(w3h_bits);
-    constexpr int PJ_ROWS = 256, PJ_A_PLANE = PJ_ROWS * 64, PJ_B_BASE = 2 * PJ_A_PLANE, NT = 2, RQ = 64;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * PJ_A_PLANE + 2 * PJ_B_PLANE];      // 40 KiB
-    __shared__ int rowexp[PJ_ROWS];      // exponent of each row's scale (K1's and this kernel's): taken out again in the epilogue
-    const int ngrp = gridDim.x / PJ_SLICES;
+    const _Float16* w3h = reinterpret_cast<const _Float16*>(w3h_bits);
+    constexpr int ROWS = PJ_CHAIN_ROWS, A_PLANE = ROWS * 64, B_BASE = 2 * A_PLANE, TILE = 2 * A_PLANE + 2 * PJ_B_PLANE;
+    constexpr int STAGE = 2 * TILE, NSET = PJ_F16_SETS;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];      // two stages of two k-tiles: 64 KiB
+    __shared__ int rowexp[ROWS];      // exponent of each row's scale (K1's and this kernel's): taken out again at a slice's end
+    // The row groups of one chain stream the same W3R tiles: they sit on ONE XCD (workgroup ids b, b+8, .. share an
+    // XCD) next to each other, so that a chain's four slices of W3R come through that XCD's L2 once (4 chains per XCD).
+    const int ngrp = gridDim.x / FN_CHAINS;
     const int xcd = blockIdx.x & 7, rr = blockIdx.x >> 3;
-    const int rg = rr % ngrp, slice = (rr / ngrp) * 8 + xcd;
+    const int rg = rr % ngrp, es = (rr / ngrp) * 8 + xcd;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
     const int srow = tid >> 3, scol = (tid & 7) * 4;
-    const int nkt = (int)moment_nkt(K), per = (nkt - 2) / PJ_SLICES;
-    const int kt0 = slice * per, nk = per + (slice == PJ_SLICES - 1 ? 2 : 0);
-    const int first = rg * PJ_ROWS;
-    const int rows_here = cnt - first < PJ_ROWS ? cnt - first : PJ_ROWS;
+    // a stage = two k-tiles (a slice is an even number of them); the chain's slices es + 32 u one behind the other: hs
+    // stages each, and the two s0 k-tiles behind slice 127 as one more stage of chain 31
+    const int nkt = (int)moment_nkt(K), per = (nkt - 2) / PJ_SLICES, hs = per >> 1;
+    const int last = 4 * hs - 1 + (es == FN_CHAINS - 1 ? 1 : 0);
+    // the loads walk the chain's stages: ld_i = the next stage to load, ld_kt its first k-tile (two on inside a slice,
+    // FN_CHAINS slices on at a slice's end; the s0 stage lies right behind slice 127's; past the end: the last stage again)
+    int ld_i = 0, ld_kt = es * per;
+    auto next_stage = [&]() {
+        const bool jump = ld_i + 1 == hs || ld_i + 1 == 2 * hs || ld_i + 1 == 3 * hs;
+        const int step = ld_i < last ? 2 + (jump ? (FN_CHAINS - 1) * per : 0) : 0;
+        ld_kt += step;
+        ld_i += ld_i < last ? 1 : 0;
+    };
+    const int first = rg * ROWS;
+    const int rows_here = cnt - first < ROWS ? cnt - first : ROWS;
     const int live = (rows_here + 31) >> 5;
-    auto a_row = [&](int r) { return r < rows_here ? r : rows_here - 1; };      // (as project_kernel: the last live row again)
-    auto a_ptr = [&](int r) {
-        return S + ((size_t)(NT * rg + (r >> 7)) * nkt + kt0) * 4096 + (r & 127) * 32 + scol;
-    };
-    // the scale of a row: from the maxima of its nq column blocks (rows past the last destination take the last one's)
-    auto row_scale = [&](int r) {
-        const float* m = rowmax + (size_t)(first + r) * (nq + 1);
-        float v = 0.f;
-        for (int q = 0; q < nq; ++q) v = fmaxf(v, m[q]);
-        return f16_row_scale(v);
-    };
-    auto row_exp = [&](int r) { return (int)rowmax[(size_t)(first + r) * (nq + 1) + nq]; };      // K1's ex + 5 of the row
-    const int r0_ = a_row(srow), r1_ = a_row(srow + RQ), r2_ = a_row(srow + 2 * RQ), r3_ = a_row(srow + 3 * RQ);
-    const float* A0 = a_ptr(r0_);
-    const float* A1 = a_ptr(r1_);
-    const float* A2 = a_ptr(r2_);
-    const float* A3 = a_ptr(r3_);
-    const float sc0 = row_scale(r0_), sc1 = row_scale(r1_), sc2 = row_scale(r2_), sc3 = row_scale(r3_);
-    if ((tid & 7) == 0) {      // (read in the epilogue, behind the loop's barriers)
-        rowexp[srow] = f32_exponent(sc0) + row_exp(r0_); rowexp[srow + RQ] = f32_exponent(sc1) + row_exp(r1_);
-        rowexp[srow + 2 * RQ] = f32_exponent(sc2) + row_exp(r2_); rowexp[srow + 3 * RQ] = f32_exponent(sc3) + row_exp(r3_);
-    }
+    // (as project_kernel: rows past the last destination read the last live row again, every load unconditional)
+    const int rc = first + (srow < rows_here ? srow : rows_here - 1);      // the thread's row of the chunk
+    const float* Ag = S + (size_t)(rc >> 7) * nkt * 4096 + (rc & 127) * 32 + scol;
+    // the scale of a row: from the maxima of its nq column blocks; [nq] = K1's ex + 5 of the row
+    const float* rm = rowmax + (size_t)rc * (nq + 1);
+    float rmax = 0.f;
+    for (int q = 0; q < nq; ++q) rmax = fmaxf(rmax, rm[q]);
+    const float sc = f16_row_scale(rmax);
+    if ((tid & 7) == 0) rowexp[srow] = f32_exponent(sc) + (int)rm[nq];      // (read behind the first stage's barrier)
     // W3R's plane tiles: thread (plane bp, row bo, 16-B chunk bc)
     const int bp = tid >> 8, bo = (tid >> 2) & 63, bc = tid & 3;
-    const _Float16* Bg = w3h + ((size_t)kt0 * 2 + bp) * 2048 + bo * 32 + bc * 8;
-    struct Tile { float4 a0, a1, a2, a3; uint4 b; };
-    auto load = [&](Tile& r, int kt) {
-        r.a0 = *reinterpret_cast<const float4*>(A0 + (size_t)kt * 4096);
-        r.a1 = *reinterpret_cast<const float4*>(A1 + (size_t)kt * 4096);
-        r.a2 = *reinterpret_cast<const float4*>(A2 + (size_t)kt * 4096);
-        r.a3 = *reinterpret_cast<const float4*>(A3 + (size_t)kt * 4096);
-        r.b = *reinterpret_cast<const uint4*>(Bg + (size_t)kt * 4096);
+    const _Float16* Bg = w3h + (size_t)bp * 2048 + bo * 32 + bc * 8;
+    // NSET stages in flight per thread (32 B per k-tile and thread: one 16-B piece of S and one of W3R's planes)
+    struct Stage { float4 a0, a1; uint4 b0, b1; };
+    auto load = [&](Stage& r) {
+        const size_t kt = (size_t)ld_kt;
+        next_stage();
+        r.a0 = *reinterpret_cast<const float4*>(Ag + kt * 4096);
+        r.a1 = *reinterpret_cast<const float4*>(Ag + (kt + 1) * 4096);
+        r.b0 = *reinterpret_cast<const uint4*>(Bg + kt * 4096);
+        r.b1 = *reinterpret_cast<const uint4*>(Bg + (kt + 1) * 4096);
+        // (the sets are loaded in the order they are stored in: in the filling round, where nothing lies between the loads,
+        // the compiler otherwise issues the first set's last, and its vmcnt wait then drains all of them)
+        asm volatile("" ::: "memory");
     };
-    auto st_off = [&](int row) { return row * 64 + ((((tid & 7) >> 1) ^ ((row >> 2) & 3)) << 4) + (tid & 1) * 8; };
-    unsigned char* a_st0 = lds + st_off(srow);
-    unsigned char* a_st1 = lds + st_off(srow + RQ);
-    unsigned char* a_st2 = lds + st_off(srow + 2 * RQ);
-    unsigned char* a_st3 = lds + st_off(srow + 3 * RQ);
-    unsigned char* b_st = lds + PJ_B_BASE + bp * PJ_B_PLANE + bo * 64 + ((bc ^ ((bo >> 2) & 3)) << 4);
-    auto scaled = [](const float4 v, float sc) { return make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc); };
-    auto store = [&](const Tile& r) {
-        split2_store4(scaled(r.a0, sc0), a_st0, PJ_A_PLANE);
-        split2_store4(scaled(r.a1, sc1), a_st1, PJ_A_PLANE);
-        split2_store4(scaled(r.a2, sc2), a_st2, PJ_A_PLANE);
-        split2_store4(scaled(r.a3, sc3), a_st3, PJ_A_PLANE);
-        *reinterpret_cast<uint4*>(b_st) = r.b;
+    const int a_st = srow * 64 + ((((tid & 7) >> 1) ^ ((srow >> 2) & 3)) << 4) + (tid & 1) * 8;
+    const int b_st = B_BASE + bp * PJ_B_PLANE + bo * 64 + ((bc ^ ((bo >> 2) & 3)) << 4);
+    auto scaled = [](const float4 v, float s_) { return make_float4(v.x * s_, v.y * s_, v.z * s_, v.w * s_); };
+    auto store = [&](const Stage& r, int buf) {
+        unsigned char* base = lds + buf * STAGE;
+        float sc_ = sc;
+        asm volatile("" : "+v"(sc_));      // (the split stays behind the loads issued before it, as written)
+        split2_store4(scaled(r.a0, sc_), base + a_st, A_PLANE);
+        split2_store4(scaled(r.a1, sc_), base + TILE + a_st, A_PLANE);
+        *reinterpret_cast<uint4*>(base + b_st) = r.b0;
+        *reinterpret_cast<uint4*>(base + TILE + b_st) = r.b1;
     };
-    f32x16 acc0, acc1;
+    // waves 0..3 (one per SIMD) each own one (32-row block rb, 32-column block cb) of the 64 x 64 result; all eight stage
+    f32x16 acc, chain;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
-    const int arow = wave * 32 + l31, brow0 = l31, brow1 = 32 + l31;
-    const int a_sw = (arow >> 2) & 3, b_sw0 = (brow0 >> 2) & 3, b_sw1 = (brow1 >> 2) & 3;
-    const unsigned char* a_rd = lds + arow * 64;
-    const unsigned char* b_rd0 = lds + PJ_B_BASE + brow0 * 64;
-    const unsigned char* b_rd1 = lds + PJ_B_BASE + brow1 * 64;
-#define PJ_MMA_TILE()                                                                                    \
-    _Pragma("unroll") for (int st = 0; st < 2; ++st) {                                                   \
-        f16x8 a[2], b0[2], b1[2];                                                                        \
-        _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                  \
-            a[p] = *reinterpret_cast<const f16x8*>(a_rd + p * PJ_A_PLANE + (((2 * st + h) ^ a_sw) << 4));    \
-            b0[p] = *reinterpret_cast<const f16x8*>(b_rd0 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw0) << 4)); \
-            b1[p] = *reinterpret_cast<const f16x8*>(b_rd1 + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw1) << 4)); \
-        }                                                                                                \
-        mma3_f16(a, b0, acc0); mma3_f16(a, b1, acc1);                                                    \
+    for (int e = 0; e < 16; ++e) { acc[e] = 0.f; chain[e] = 0.f; }
+    const int rb = (wave >> 1) & 1, cb = wave & 1;
+    const int arow = rb * 32 + l31, brow = cb * 32 + l31;
+    const int a_sw = (arow >> 2) & 3, b_sw = (brow >> 2) & 3;
+    const int a_rd = arow * 64, b_rd = B_BASE + brow * 64;
+    const bool mma_wave = wave < 4 && rb < live;
+    // the column's power of two and the row's out again — as ONE exponent per element (ldexp: exact over the whole range;
+    // the two factors one after the other could overflow on the way): a slice's partial in S . W3R's own units
+    const int ec = f32_exponent(colinv[cb * 32 + l31]);
+    auto mma_tile = [&](const unsigned char* base) {      // one k-tile: the 256-row form's st = 0, 1, the same operand order
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            f16x8 a[2], b[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                a[p] = *reinterpret_cast<const f16x8*>(base + a_rd + p * A_PLANE + (((2 * st + h) ^ a_sw) << 4));
+                b[p] = *reinterpret_cast<const f16x8*>(base + b_rd + p * PJ_B_PLANE + (((2 * st + h) ^ b_sw) << 4));
+            }
+            mma3_f16(a, b, acc);
+        }
+    };
+    Stage R[NSET];
+    // LDS buffer i & 1 holds stage i, register set (i + 1) % NSET stage i + 1 (landed or landing), the set just stored is
+    // reloaded with stage i + NSET (past the end: the last stage again, an L2 hit that is never stored); ONE barrier per
+    // stage: the store below goes to the buffer every wave finished reading before the previous barrier
+    auto multiply = [&](int i, int buf) {
+        if (!mma_wave) return;
+        mma_tile(lds + buf * STAGE);
+        mma_tile(lds + buf * STAGE + TILE);
+        if (i + 1 == hs || i + 1 == 2 * hs || i + 1 == 3 * hs || i == last) {
+            // a slice's end (the s0 stage belongs to slice 127): K3's z = 0; z += p[es + 32 u] in slice order, as plain
+            // fp32 adds (the build has -ffp-contract=off; there is nothing to contract here anyway)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                chain[e] = chain[e] + ldexpf(acc[e], ec - rowexp[mfma32_row(e, h, rb * 32)]);
+                acc[e] = 0.f;
+            }
+        }
+    };
+    // whole rounds of NSET stages leave the loop at its bottom only (an exit in mid-round comes back to the loop's head as
+    // a path on which the newest loads are still on their way, and the vmcnt waits are counted for that path); the
+    // stages left over, at most NSET - 1, follow as straight-line code without loads
+    // (round -1 only fills the register sets and stores stage 0)
+    int i0 = -NSET;
+    for (; i0 + NSET <= last + 1; i0 += NSET) {
+#pragma unroll
+        for (int j = 0; j < NSET; ++j) {
+            load(R[j]);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i0 >= 0) multiply(i0 + j, j & 1);
+            if (i0 >= 0 || j == NSET - 1) {
+                store(R[(j + 1) % NSET], (j + 1) & 1);      // (behind the last stage: that stage again, never multiplied)
+                __syncthreads();
+            }
+        }
     }
-    const bool rows_live = wave < live;
-    Tile P, Q;
-    // (as project_kernel: nk even, every load unconditional, two K-tiles in flight per thread)
-    const int last = nk - 1;
-    load(P, 0);
-    load(Q, 1);
-    store(P);
-    __syncthreads();
-    for (int kt = 0;; kt += 2) {
-        load(P, min(kt + 2, last));
-        __builtin_amdgcn_sched_barrier(0);
-        if (rows_live) { PJ_MMA_TILE() }
-        __syncthreads();
-        store(Q);
-        __syncthreads();
-        load(Q, min(kt + 3, last));
-        __builtin_amdgcn_sched_barrier(0);
-        if (rows_live) { PJ_MMA_TILE() }
-        if (kt + 2 >= nk) break;
-        __syncthreads();
-        store(P);
-        __syncthreads();
-    }
-#undef PJ_MMA_TILE
-    // the row's and the column's powers of two out again — as ONE exponent per element (ldexp: exact over the whole range;
-    // the two factors one after the other could overflow on the way): the partials K3 adds are in S . W3R's own units
-    const int ec0 = f32_exponent(colinv[l31]), ec1 = f32_exponent(colinv[32 + l31]);
-    float* Po = part + (size_t)slice * part_stride;
+#pragma unroll
+    for (int j = 0; j < NSET - 1; ++j)
+        if (i0 + j <= last) {      // (the same for the whole workgroup)
+            multiply(i0 + j, j & 1);
+            store(R[j + 1], (j + 1) & 1);
+            __syncthreads();
+        }
+    if (!mma_wave) return;
+    float* Po = part + (size_t)es * part_stride + cb * 32 + l31;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int ml = mfma32_row(e, h, wave * 32), m = first + ml;
-        if (m < cnt) {
-            const int er = rowexp[ml];
-            Po[(size_t)(row0 + m) * 64 + l31] = ldexpf(acc0[e], ec0 - er);
-            Po[(size_t)(row0 + m) * 64 + 32 + l31] = ldexpf(acc1[e], ec1 - er);
-        }
+        const int m = mfma32_row(e, h, first + rb * 32);
+        if (m < cnt) Po[(size_t)(row0 + m) * 64] = chain[e];
     }
 }
 
@@ -860,9 +903,9 @@ __global__ __launch_bounds__(256) void project_f32_kernel(const float* __restric
 // ---------------------------------------------------------------- K3: slices + root + bias + mean + act
 // One workgroup (32 chains x 16 lanes) per destination: chain es adds K slices es, es+32, .. in that order, the 32
 // chains are added in chain order through LDS; the root product is split over the chains the same way.  Every load
-// depends on the destination's index only (one round trip).
-constexpr int FN_CHAINS = 32;
-
+// depends on the destination's index only (one round trip).  PPC = partials per chain in `part`: 4 behind the kernels
+// that store slice partials, 1 behind project_f16_kernel, which has added a chain's slices already (part[es] = the chain).
+template <int PPC>
 __global__ __launch_bounds__(FN_CHAINS * 16) void finish_kernel(const float* __restrict__ part, long long part_stride,
                                                                 const int* __restrict__ row_ptr, const float* __restrict__ x,
                                                                 const float* __restrict__ root, const float* __restrict__ bias,
@@ -886,14 +929,17 @@ __global__ __launch_bounds__(FN_CHAINS * 16) void finish_kernel(const float* __r
         }
     }
     if (bias != nullptr && es == 0) biasv = *reinterpret_cast<const float4*>(bias + 4 * q);
+    static_assert(PPC == 1 || PPC == PJ_SLICES / FN_CHAINS, "finish_kernel: chain partials or slice partials");
     float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    {
-        float4 v[PJ_SLICES / FN_CHAINS];
+    if (PPC == 1) {
+        z = *reinterpret_cast<const float4*>(part + (size_t)es * part_stride + (size_t)t * 64 + 4 * q);
+    } else {
+        float4 v[PPC];
 #pragma unroll
-        for (int u = 0; u < PJ_SLICES / FN_CHAINS; ++u)
+        for (int u = 0; u < PPC; ++u)
             v[u] = *reinterpret_cast<const float4*>(part + (size_t)(es + u * FN_CHAINS) * part_stride + (size_t)t * 64 + 4 * q);
 #pragma unroll
-        for (int u = 0; u < PJ_SLICES / FN_CHAINS; ++u) { z.x += v[u].x; z.y += v[u].y; z.z += v[u].z; z.w += v[u].w; }
+        for (int u = 0; u < PPC; ++u) { z.x += v[u].x; z.y += v[u].y; z.z += v[u].z; z.w += v[u].w; }
     }
     float4 racc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -1059,17 +1105,21 @@ int moment_conv(const float* x, const float* h2, const int* row_ptr, const int* 
                 hipLaunchKernelGGL(project_f32_kernel, dim3(((cnt + 127) / 128) * PJ_SLICES), dim3(256), 0, s, (const float*)f.s,
                                    (const float*)f.w3r, f.part, ker_width, cnt, r0, f.part_stride);
             else if (f16)
-                hipLaunchKernelGGL(project_f16_kernel, dim3(((cnt + 255) / 256) * PJ_SLICES), dim3(512), 0, s, (const float*)f.s,
+                hipLaunchKernelGGL(project_f16_kernel, dim3(((cnt + PJ_CHAIN_ROWS - 1) / PJ_CHAIN_ROWS) * FN_CHAINS), dim3(512), 0, s, (const float*)f.s,
                                    reinterpret_cast<const unsigned short*>(f.w3h), f.part, ker_width, cnt, r0, f.part_stride,
                                    (const float*)f.rowmax, nq, (const float*)f.colinv);
             else
                 hipLaunchKernelGGL(project_kernel<256>, dim3(((cnt + 255) / 256) * PJ_SLICES), dim3(512), 0, s, (const float*)f.s,
                                    (const float*)f.w3r, f.part, ker_width, cnt, r0, f.part_stride);
         }
-        {   // K3
+        {   // K3: behind the fp16 planes' K2 the 32 chain partials, behind the others the 128 slice partials
             TimedSection ts(KID_NNCONV_COMBINE, s);
-            hipLaunchKernelGGL(finish_kernel, dim3(cnt), dim3(FN_CHAINS * 16), 0, s, (const float*)f.part, f.part_stride,
-                               row_ptr, x, root, bias, y, r0, aggr, relu, xm_out);
+            if (f16)
+                hipLaunchKernelGGL(finish_kernel<1>, dim3(cnt), dim3(FN_CHAINS * 16), 0, s, (const float*)f.part, f.part_stride,
+                                   row_ptr, x, root, bias, y, r0, aggr, relu, xm_out);
+            else
+                hipLaunchKernelGGL(finish_kernel<PJ_SLICES / FN_CHAINS>, dim3(cnt), dim3(FN_CHAINS * 16), 0, s, (const float*)f.part,
+                                   f.part_stride, row_ptr, x, root, bias, y, r0, aggr, relu, xm_out);
         }
     }
     return check_launch("moment_conv");

@@ -4,14 +4,14 @@
  * reference frame, and its row and column minima: the nearest reference frame of each produced frame (precision) and the
  * nearest produced frame of each reference frame, per member (coverage).  Additive, like mdno_ensemble.h: include/mdno.h,
  * include/mdno_train.h and their version numbers stay as they are, and no launch, captured graph or bit of an existing
- * entry point changes.  (This file is not part of the library's content hash: csrc/conformations.hip includes it, so a
- * declaration that drifts from its definition does not compile, and tests/test_conformations_host.py holds it to the ctypes
+ * entry point changes.  (This file is part of the library's content hash, and csrc/conformations.hip includes it, so a
+ * declaration that drifts from its definition does not compile; tests/test_cabi_tables.py holds it to the ctypes
  * table and the exports.)  Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a
  * hipStream_t passed as void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message).
  *
- * THE PREFIX.  The two entry points are named mdnoconf_*, not mdno_*: the tests of the earlier headers assert that every
- * export of the library whose name starts with mdno_ is declared in one of THEIR tables (mdnoens_ likewise in its own), and
- * they stay as they are.  The functions live in the same library, under the same content hash and the same
+ * THE PREFIX.  The two entry points are named mdnoconf_*, not mdno_*.  The prefix is kept because the names are
+ * ABI; nothing else asks for it (names need only be unique over all headers, which tests/test_cabi_tables.py checks).
+ * The functions live in the same library, under the same content hash and the same
  * mdno_abi_version().
  *
  * INPUTS.  A is f32 [S, M, N, 3], time-major and contiguous: the layout of a rollout's trajectory buffer, M members (a plain

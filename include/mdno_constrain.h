@@ -5,9 +5,9 @@
  * end of a rollout step (mdnocst_rollout_plan_set_constraints), so that the frame the next window and the next radius
  * graph read lies on the manifold the truth lives on.  Additive: include/mdno.h, include/mdno_train.h and their version
  * numbers stay as they are, and with no constraints given no launch, captured graph or bit of the library changes.  Every
- * name starts with mdnocst_, the plan's setter included: the tests of the older headers hold every mdno_ export to THEIR
- * tables (as mdno_ensemble.h says of mdnoens_).  This file is not part of the library's content hash; csrc/constrain.hip
- * and csrc/engine.hip include it, and tests/test_constrain_host.py holds it to the ctypes table and the exports.
+ * name starts with mdnocst_, the plan's setter included: the prefix is kept because the names are ABI, nothing else asks for
+ * it (as mdno_ensemble.h says of mdnoens_).  This file is part of the library's content hash; csrc/constrain.hip
+ * and csrc/engine.hip include it, and tests/test_cabi_tables.py holds it to the ctypes table and the exports.
  * Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as void*,
  * 0 or a negative MDNO_E* code (mdno_last_error() has the message).
  *

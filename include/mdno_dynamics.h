@@ -4,9 +4,9 @@
  * non-Gaussian parameter and the self part of the van Hove function, the velocity autocorrelation of finite-difference
  * velocities, and a companion that unwraps frames which arrive wrapped into a periodic box.  Additive, like
  * mdno_observe.h: include/mdno.h, include/mdno_train.h and their version numbers stay as they are, and no launch,
- * captured graph or bit of an existing entry point changes.  (This file is not part of the library's content hash:
- * csrc/dynamics.hip includes it, so a declaration that drifts from its definition does not compile, and
- * tests/test_dynamics_host.py holds it to the ctypes table and the exports.)  Conventions as in mdno.h: device pointers
+ * captured graph or bit of an existing entry point changes.  (This file is part of the library's content hash, and
+ * csrc/dynamics.hip includes it, so a declaration that drifts from its definition does not compile;
+ * tests/test_cabi_tables.py holds it to the ctypes table and the exports.)  Conventions as in mdno.h: device pointers
  * owned by the caller, explicit sizes, `stream` a hipStream_t passed as void*, 0 or a negative MDNO_E* code
  * (mdno_last_error() has the message).
  *

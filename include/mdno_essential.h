@@ -5,15 +5,15 @@
  * frames at a time lag (lag 0: the covariance PCA diagonalises; lag > 0: the time-lagged matrix of TICA), and project the
  * frames onto chosen directions.  The eigen-solves themselves are the host's (forecast.py: pca, tica).  Additive, like
  * mdno_conformations.h: include/mdno.h, include/mdno_train.h and their version numbers stay as they are, and no launch,
- * captured graph or bit of an existing entry point changes.  (This file is not part of the library's content hash:
- * csrc/essential.hip includes it, so a declaration that drifts from its definition does not compile, and
- * tests/test_essential_host.py holds it to the ctypes table and the exports.)  Conventions as in mdno.h: device pointers
+ * captured graph or bit of an existing entry point changes.  (This file is part of the library's content hash, and
+ * csrc/essential.hip includes it, so a declaration that drifts from its definition does not compile;
+ * tests/test_cabi_tables.py holds it to the ctypes table and the exports.)  Conventions as in mdno.h: device pointers
  * owned by the caller, explicit sizes, `stream` a hipStream_t passed as void*, 0 or a negative MDNO_E* code
  * (mdno_last_error() has the message), every refusal before any device work.
  *
- * THE PREFIX.  The entry points are named mdnopca_*, not mdno_*: the tests of the earlier headers assert that every export
- * of the library whose name starts with mdno_ is declared in one of THEIR tables (mdnoens_ and mdnoconf_ likewise in their
- * own), and they stay as they are.  The functions live in the same library, under the same content hash and the same
+ * THE PREFIX.  The entry points are named mdnopca_*, not mdno_*.  The prefix is kept because the names are ABI;
+ * nothing else asks for it (names need only be unique over all headers, which tests/test_cabi_tables.py checks).
+ * The functions live in the same library, under the same content hash and the same
  * mdno_abi_version().
  *
  * ARITHMETIC.  Everything in fp64 on the fp32 inputs, no FMA contraction outside the matrix instruction, no floating-point

@@ -5,14 +5,14 @@
  * histogram of such a matrix.  These features do not depend on a reference frame: a rigid rotation or translation of a
  * frame changes them by rounding only.  Additive, like mdno_markov.h: include/mdno.h, include/mdno_train.h and their
  * version numbers stay as they are, and no launch, captured graph or bit of an existing entry point changes.  (This file
- * is not part of the library's content hash: csrc/internal.hip includes it, so a declaration that drifts from its
- * definition does not compile, and tests/test_internal_host.py holds it to the ctypes table and the exports.)  Conventions
+ * is part of the library's content hash, and csrc/internal.hip includes it, so a declaration that drifts from its
+ * definition does not compile; tests/test_cabi_tables.py holds it to the ctypes table and the exports.)  Conventions
  * as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as void*, 0 or a negative
  * MDNO_E* code (mdno_last_error() has the message), every refusal before any device work.
  *
- * THE PREFIX.  The entry points are named mdnoic_*, not mdno_*: the tests of the earlier headers assert that every export
- * of the library whose name starts with mdno_ (mdnoens_, mdnoconf_, mdnopca_, mdnomsm_) is declared in one of THEIR tables,
- * and they stay as they are.  The functions live in the same library, under the same content hash and the same
+ * THE PREFIX.  The entry points are named mdnoic_*, not mdno_*.  The prefix is kept because the names are ABI;
+ * nothing else asks for it (names need only be unique over all headers, which tests/test_cabi_tables.py checks).
+ * The functions live in the same library, under the same content hash and the same
  * mdno_abi_version().
  *
  * FEATURES (mdnoic_features).  frames f32 [F, N, 3]; index arrays i32 on the device: pairs [P, 2], triples [A, 3],

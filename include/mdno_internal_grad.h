@@ -5,15 +5,15 @@
  * forecast.internal_coordinates differentiable and training.StructureLoss a training signal.  Additive, like
  * mdno_internal.h: include/mdno.h, include/mdno_train.h and their version numbers stay as they are, and no launch, captured
  * graph or bit of an existing entry point changes (csrc/internal.hip takes its bond, dot and cross product from
- * csrc/internal_rule.h now, the same text in another file).  This file is not part of the library's content hash:
- * csrc/internal_grad.hip includes it, so a declaration that drifts from its definition does not compile, and
- * tests/test_internal_grad_host.py holds it to the ctypes table and the exports.  Conventions as in mdno.h: device pointers
+ * csrc/internal_rule.h now, the same text in another file).  This file is part of the library's content hash, and
+ * csrc/internal_grad.hip includes it, so a declaration that drifts from its definition does not compile;
+ * tests/test_cabi_tables.py holds it to the ctypes table and the exports.  Conventions as in mdno.h: device pointers
  * owned by the caller, explicit sizes, `stream` a hipStream_t passed as void*, 0 or a negative MDNO_E* code
  * (mdno_last_error() has the message), every refusal before any device work.
  *
- * THE PREFIX.  The entry point is named mdnoicg_*, neither mdno_* nor mdnoic_*: tests/test_internal_host.py asserts that
- * the library's exports starting with mdnoic_ are exactly the two of mdno_internal.h, and the tests of the earlier headers
- * own mdno_, mdnoens_, mdnoconf_, mdnopca_ and mdnomsm_ in the same way; they all stay as they are.  The function lives in
+ * THE PREFIX.  The entry point is named mdnoicg_*, neither mdno_* nor mdnoic_*.  The prefix is kept because the name
+ * is ABI; nothing else asks for it (names need only be unique over all headers, which tests/test_cabi_tables.py checks).
+ * The function lives in
  * the same library, under the same content hash and the same mdno_abi_version().  The element types, the forms,
  * MDNO_IC_WORKGROUP, MDNO_IC_LDS_ATOMS and MDNO_IC_FRAMES_PER_GROUP(N) are mdno_internal.h's.
  *

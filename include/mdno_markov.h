@@ -5,14 +5,14 @@
  * transitions between the states at a set of lags.  The models themselves (active set, transition matrix, spectrum,
  * Chapman–Kolmogorov) are the host's (forecast.py: markov_model).  Additive, like mdno_essential.h: include/mdno.h,
  * include/mdno_train.h and their version numbers stay as they are, and no launch, captured graph or bit of an existing
- * entry point changes.  (This file is not part of the library's content hash: csrc/markov.hip includes it, so a declaration
- * that drifts from its definition does not compile, and tests/test_markov_host.py holds it to the ctypes table and the
+ * entry point changes.  (This file is part of the library's content hash, and csrc/markov.hip includes it, so a declaration
+ * that drifts from its definition does not compile; tests/test_cabi_tables.py holds it to the ctypes table and the
  * exports.)  Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed
  * as void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message), every refusal before any device work.
  *
- * THE PREFIX.  The entry points are named mdnomsm_*, not mdno_*: the tests of the earlier headers assert that every export
- * of the library whose name starts with mdno_ is declared in one of THEIR tables (mdnoens_, mdnoconf_ and mdnopca_ likewise
- * in their own), and they stay as they are.  The functions live in the same library, under the same content hash and the
+ * THE PREFIX.  The entry points are named mdnomsm_*, not mdno_*.  The prefix is kept because the names are ABI;
+ * nothing else asks for it (names need only be unique over all headers, which tests/test_cabi_tables.py checks).
+ * The functions live in the same library, under the same content hash and the
  * same mdno_abi_version().
  *
  * ARITHMETIC.  Everything in fp64, no FMA contraction outside the matrix instruction, no floating-point atomics (the only

@@ -3,9 +3,9 @@
  * csrc/noise.hip).  Additive: include/mdno.h, include/mdno_train.h and their version numbers stay
  * as they are.  (A header of its own, like mdno_train.h, because the set of entry points of mdno.h that write caller
  * memory is pinned, name by name, by that header's guard-band table in tests/test_gpu_bounds.py; these three have
- * their table in tests/test_gpu_noise.py.  This file is not part of the library's content hash, which lists mdno.h
- * and mdno_train.h: csrc/noise.hip and csrc/engine.hip include it, so a declaration that drifts from its definition
- * does not compile, and tests/test_noise_host.py holds it to the ctypes table and the exports.)
+ * their table in tests/test_gpu_noise.py.  This file is part of the library's content hash, as every header
+ * under include/ is, and csrc/noise.hip and csrc/engine.hip include it, so a declaration that drifts from its definition
+ * does not compile; tests/test_cabi_tables.py holds it to the ctypes table and the exports.)
  * Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as
  * void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message).
  *

@@ -3,8 +3,8 @@
  * memory (csrc/observe.hip) — the histogram of pair distances of every frame, from which g(r) of a
  * periodic box and p(r) of a protein are formed, and the per-frame radius of gyration.  Additive, like mdno_pbc.h:
  * include/mdno.h, include/mdno_train.h and their version numbers stay as they are, and no launch, captured graph or bit
- * of an existing entry point changes.  (This file is not part of the library's content hash: csrc/observe.hip includes
- * it, so a declaration that drifts from its definition does not compile, and tests/test_observe_host.py holds it to
+ * of an existing entry point changes.  (This file is part of the library's content hash, and csrc/observe.hip includes
+ * it, so a declaration that drifts from its definition does not compile; tests/test_cabi_tables.py holds it to
  * the ctypes table and the exports.)  Conventions as in mdno.h: device pointers owned by the caller, explicit sizes,
  * `stream` a hipStream_t passed as void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message).
  *

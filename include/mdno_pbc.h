@@ -3,9 +3,9 @@
  * DESIGN.md §4.12).  Additive: include/mdno.h, include/mdno_train.h and their version numbers stay as they are, and
  * with no box given every launch, captured graph and bit of the library is what it was.  (A header of its own, like
  * mdno_noise.h: the entry points of mdno.h that write caller memory are pinned, name by name, by that header's
- * guard-band table in tests/test_gpu_bounds.py; these have their table in tests/test_gpu_pbc.py.  This file is not part
- * of the library's content hash: csrc/pbc.hip, csrc/engine.hip and csrc/forecast.hip include it, so a declaration that
- * drifts from its definition does not compile, and tests/test_pbc_host.py holds it to the ctypes table and the exports.)
+ * guard-band table in tests/test_gpu_bounds.py; these have their table in tests/test_gpu_pbc.py.  This file is part of
+ * the library's content hash, and csrc/pbc.hip, csrc/engine.hip and csrc/forecast.hip include it, so a declaration that
+ * drifts from its definition does not compile; tests/test_cabi_tables.py holds it to the ctypes table and the exports.)
  * Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as
  * void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message).
  *

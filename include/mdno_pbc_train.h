@@ -2,10 +2,10 @@
  * mdno_pbc_train.h — public header of libmdno.so for TRAINING under an orthorhombic periodic box (csrc/pbc_train.hip;
  * DESIGN.md §4.12 "Training under a box").  Additive: include/mdno.h, include/mdno_train.h, include/mdno_pbc.h and the
  * two version numbers stay as they are, and with no box given every launch, captured graph and bit of the library is
- * what it was.  This file is not part of the library's content hash: csrc/pbc_train.hip includes it, so a declaration
- * that drifts from its definition does not compile, and tests/test_pbc_train_host.py holds it to the ctypes table
- * (_lib.PBC_TRAIN_SIGNATURES) and the exports.  The name starts with mdnopbt_, not mdno_: the host tests of the older
- * headers hold every mdno_ export to THEIR tables.  The guard-band table of this header is in
+ * what it was.  This file is part of the library's content hash, and csrc/pbc_train.hip includes it, so a declaration
+ * that drifts from its definition does not compile; tests/test_cabi_tables.py holds it to the ctypes table
+ * (_lib.PBC_TRAIN_SIGNATURES) and the exports.  The name starts with mdnopbt_, not mdno_: the prefix is kept because the
+ * name is ABI, nothing else asks for it.  The guard-band table of this header is in
  * tests/test_gpu_pbc_train.py.
  * Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as
  * void*, 0 or a negative MDNO_E* code (mdno_last_error() has the message), arguments validated before any device work.

@@ -2,8 +2,8 @@
  * mdno_unroll.h — fourth public header of libmdno.so: gradients with respect to the model's INPUTS (window frames and
  * edge attributes) and the pieces an unrolled training step needs (csrc/input_grad.hip, csrc/train_nodes.hip;
  * DESIGN.md §4.11).  Additive, like mdno_noise.h: include/mdno.h, include/mdno_train.h and their version numbers stay
- * as they are, this file is not part of the library's content hash (csrc/input_grad.hip and csrc/train_nodes.hip
- * include it, so a declaration that drifts from its definition does not compile; tests/test_unroll_host.py holds it
+ * as they are; this file is part of the library's content hash (and csrc/input_grad.hip and csrc/train_nodes.hip
+ * include it, so a declaration that drifts from its definition does not compile; tests/test_cabi_tables.py holds it
  * to the ctypes table and the exports; the entries that write caller memory have their guard-band table in
  * tests/test_gpu_unroll.py).
  * Conventions as in mdno.h: device pointers owned by the caller, explicit sizes, `stream` a hipStream_t passed as

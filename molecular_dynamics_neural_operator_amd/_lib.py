@@ -45,7 +45,10 @@ _L = C.c_int64
 _SZ = C.c_size_t
 _D = C.c_double
 
-# name -> (restype, argtypes); kept in step with include/mdno.h (tests/test_cabi.py checks both ways)
+# One table per public header, name -> (restype, argtypes); TABLES below pairs each with its header and states the
+# contract they all keep.  Beside a table stands only what is particular to it.
+
+# include/mdno.h
 SIGNATURES = {
     "mdno_abi_version": (_I, []),
     "mdno_last_error": (C.c_char_p, []),
@@ -147,8 +150,7 @@ SIGNATURES = {
     "mdno_contact_maps": (_I, [_P, _L, _I, _D, _P, _P]),
 }
 
-# include/mdno_train.h (training on dense graphs, its own version number): name -> (restype, argtypes), kept in step
-# with that header (tests/test_train_cabi.py checks both ways)
+# include/mdno_train.h: training on dense graphs, with a version number of its own
 TRAIN_ABI_VERSION = 1
 TRAIN_SIGNATURES = {
     "mdno_train_abi_version": (_I, []),
@@ -161,8 +163,7 @@ TRAIN_SIGNATURES = {
                                    _SZ, _P]),
 }
 
-# include/mdno_noise.h (seeded Gaussian noise on the device; additive, no version number of its own): name ->
-# (restype, argtypes), kept in step with that header (tests/test_noise_host.py checks both ways)
+# include/mdno_noise.h: seeded Gaussian noise on the device
 _U64 = C.c_uint64
 _F = C.c_float
 NOISE_PURPOSES = {"rollout": 0, "train_window": 1}
@@ -172,8 +173,7 @@ NOISE_SIGNATURES = {
     "mdno_rollout_plan_set_noise": (_I, [_P, _F, _U64, _P]),
 }
 
-# include/mdno_unroll.h (gradients w.r.t. the model's inputs, targets of an unrolled step; additive, no version number
-# of its own): name -> (restype, argtypes), kept in step with that header (tests/test_unroll_host.py checks both ways)
+# include/mdno_unroll.h: gradients w.r.t. the model's inputs, targets of an unrolled step
 UNROLL_SIGNATURES = {
     "mdno_edge_mlp_input_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P, _P]),
     "mdno_edge_attr_from_pos": (_I, [_P, _P, _P, _P, _L, _I, _P, _P]),
@@ -183,9 +183,8 @@ UNROLL_SIGNATURES = {
     "mdno_collate_targets": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),
 }
 
-# include/mdno_pbc.h (orthorhombic periodic boundary conditions; additive, no version number of its own): name ->
-# (restype, argtypes), kept in step with that header (tests/test_pbc_host.py checks both ways).  `box` is a HOST
-# pointer to three doubles (ops.box_arg).
+# include/mdno_pbc.h: orthorhombic periodic boundary conditions.  `box` is a HOST pointer to three doubles
+# (ops.box_arg).
 PBC_SIGNATURES = {
     "mdno_radius_graph_pbc": (_I, [_P, _I, _I, _D, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
     "mdno_rollout_plan_set_box": (_I, [_P, _P, _P]),
@@ -193,19 +192,16 @@ PBC_SIGNATURES = {
     "mdno_contact_maps_pbc": (_I, [_P, _L, _I, _D, _P, _P, _P]),
 }
 
-# include/mdno_observe.h (pair-distance histograms and the radius of gyration of frames on the device; additive, no
-# version number of its own): name -> (restype, argtypes), kept in step with that header (tests/test_observe_host.py
-# checks both ways).  `box` is a HOST pointer to three doubles or NULL.
+# include/mdno_observe.h: pair-distance histograms and the radius of gyration of frames on the device.  `box` is a HOST
+# pointer to three doubles or NULL.
 OBSERVE_SIGNATURES = {
     "mdno_pair_histogram_workspace_bytes": (_SZ, [_L, _I, _I, _I]),
     "mdno_pair_histogram": (_I, [_P, _L, _I, _D, _I, _P, _P, _I, _P, _SZ, _P]),
     "mdno_radius_of_gyration": (_I, [_P, _L, _I, _P, _P]),
 }
 
-# include/mdno_dynamics.h (displacement statistics, velocity autocorrelation and unwrapping of a trajectory on the
-# device; additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
-# (tests/test_dynamics_host.py checks both ways).  `lags` is a HOST pointer to n_lags int32, `box` a HOST pointer to three
-# doubles.
+# include/mdno_dynamics.h: displacement statistics, velocity autocorrelation and unwrapping of a trajectory on the
+# device.  `lags` is a HOST pointer to n_lags int32, `box` a HOST pointer to three doubles.
 DYNAMICS_SIGNATURES = {
     "mdno_displacement_stats_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "mdno_displacement_stats": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _D, _I, _P, _P, _P, _P, _SZ, _P]),
@@ -214,29 +210,23 @@ DYNAMICS_SIGNATURES = {
     "mdno_unwrap_frames": (_I, [_P, _I, _I, _I, _P, _P, _P]),
 }
 
-# include/mdno_ensemble.h (ensemble verification: error of the mean, spread, CRPS sums and the rank histogram per step;
-# additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
-# (tests/test_ensemble_host.py checks both ways).  The names start with mdnoens_, not mdno_: the tests of the seven tables
-# above hold every mdno_ export to THEIR tables (the header says so too).
+# include/mdno_ensemble.h: ensemble verification (error of the mean, spread, CRPS sums and the rank histogram per step).
+# Prefix mdnoens_.
 ENSEMBLE_FORMS = {"auto": 0, "registers": 1, "lds": 2}
 ENSEMBLE_SIGNATURES = {
     "mdnoens_score_workspace_bytes": (_SZ, [_I, _I, _I]),
     "mdnoens_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _SZ, _P]),
 }
 
-# include/mdno_conformations.h (structural coverage: the superposed RMSD of every frame against every reference frame, its
-# row and per-member column minima; additive, no version number of its own): name -> (restype, argtypes), kept in step
-# with that header (tests/test_conformations_host.py checks both ways).  The names start with mdnoconf_, for the reason
-# mdnoens_ has (the header says so too).
+# include/mdno_conformations.h: structural coverage (the superposed RMSD of every frame against every reference frame, its
+# row and per-member column minima).  Prefix mdnoconf_.
 CONFORMATIONS_SIGNATURES = {
     "mdnoconf_cross_rmsd_workspace_bytes": (_SZ, [_I, _I, _I, _L, _I]),
     "mdnoconf_cross_rmsd": (_I, [_P, _I, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
-# include/mdno_essential.h (essential dynamics: superposition onto one reference with the rotated frames handed back,
-# column sums, the feature x feature second-moment matrix at a time lag, projection; additive, no version number of its
-# own): name -> (restype, argtypes), kept in step with that header (tests/test_essential_host.py checks both ways).  The
-# names start with mdnopca_, for the reason mdnoens_ has (the header says so too).
+# include/mdno_essential.h: essential dynamics (superposition onto one reference with the rotated frames handed back,
+# column sums, the feature x feature second-moment matrix at a time lag, projection).  Prefix mdnopca_.
 ESSENTIAL_SIGNATURES = {
     "mdnopca_superpose": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "mdnopca_feature_sums": (_I, [_P, _L, _I, _P, _P, _P]),
@@ -245,10 +235,8 @@ ESSENTIAL_SIGNATURES = {
     "mdnopca_project": (_I, [_P, _L, _I, _P, _P, _I, _P, _P]),
 }
 
-# include/mdno_markov.h (Markov state models: nearest-centre assignment, k-centres seeding, per-state row sums, transition
-# counts at a set of lags; additive, no version number of its own): name -> (restype, argtypes), kept in step with that
-# header (tests/test_markov_host.py checks both ways).  The names start with mdnomsm_, for the reason mdnoens_ has (the
-# header says so too).  `lags` is a HOST pointer to n_lags int32.
+# include/mdno_markov.h: Markov state models (nearest-centre assignment, k-centres seeding, per-state row sums, transition
+# counts at a set of lags).  Prefix mdnomsm_.  `lags` is a HOST pointer to n_lags int32.
 MARKOV_DTYPES = {"float32": 0, "float64": 1}
 MARKOV_SIGNATURES = {
     "mdnomsm_assign_workspace_bytes": (_SZ, [_L, _I, _I]),
@@ -259,10 +247,8 @@ MARKOV_SIGNATURES = {
     "mdnomsm_transition_counts": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
 }
 
-# include/mdno_internal.h (internal coordinates: pair distances, angle cosines and dihedral (cos, sin) per frame as a feature
-# matrix, and a per-column histogram of one; additive, no version number of its own): name -> (restype, argtypes), kept in
-# step with that header (tests/test_internal_host.py checks both ways).  The names start with mdnoic_, for the reason
-# mdnoens_ has (the header says so too).  `box`, `lo` and `hi` are HOST pointers to doubles.
+# include/mdno_internal.h: internal coordinates (pair distances, angle cosines and dihedral (cos, sin) per frame as a feature
+# matrix, and a per-column histogram of one).  Prefix mdnoic_.  `box`, `lo` and `hi` are HOST pointers to doubles.
 INTERNAL_DTYPES = {"float32": 0, "float64": 1}
 INTERNAL_FORMS = {"auto": 0, "lds": 1, "global": 2}
 INTERNAL_RADIANS = 1
@@ -271,20 +257,17 @@ INTERNAL_SIGNATURES = {
     "mdnoic_column_histogram": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
-# include/mdno_internal_grad.h (the adjoint of mdnoic_features in its default mode: the gradient with respect to the features
-# -> the gradient with respect to the positions; additive, no version number of its own): name -> (restype, argtypes), kept
-# in step with that header (tests/test_internal_grad_host.py checks both ways).  The name starts with mdnoicg_, because
-# tests/test_internal_host.py holds the mdnoic_ exports to the table above (the header says so too).  `box` is a HOST
-# pointer to doubles; the element types and forms are INTERNAL_DTYPES and INTERNAL_FORMS.
+# include/mdno_internal_grad.h: the adjoint of mdnoic_features in its default mode (the gradient with respect to the
+# features -> the gradient with respect to the positions).  Prefix mdnoicg_.  `box` is a HOST pointer to doubles; the
+# element types and forms are INTERNAL_DTYPES and INTERNAL_FORMS.
 INTERNAL_GRAD_MAX_ITEMS = 1 << 29
 INTERNAL_GRAD_SIGNATURES = {
     "mdnoicg_features_bwd": (_I, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P, _I, _P, _I, _P, _I, _I, _P]),
 }
 
-# include/mdno_constrain.h (distance-constraint projection of frames, and of the frame a rollout step produces; additive, no
-# version number of its own): name -> (restype, argtypes), kept in step with that header (tests/test_constrain_host.py
-# checks both ways).  The names start with mdnocst_, the plan's setter included, for the reason mdnoens_ has (the header says
-# so too).  `box` is a HOST pointer to three doubles; the table (pairs, lo, hi, colour_ptr, weights) lies on the device.
+# include/mdno_constrain.h: distance-constraint projection of frames, and of the frame a rollout step produces.  Prefix
+# mdnocst_, the plan's setter included.  `box` is a HOST pointer to three doubles; the table (pairs, lo, hi, colour_ptr,
+# weights) lies on the device.
 CONSTRAIN_MAX_ATOMS = 6144          # MDNOCST_MAX_ATOMS: the largest N (the state of a frame lies in LDS as fp64)
 CONSTRAIN_MAX_CONSTRAINTS = 1 << 26  # MDNOCST_MAX_CONSTRAINTS
 CONSTRAIN_SIGNATURES = {
@@ -292,30 +275,71 @@ CONSTRAIN_SIGNATURES = {
     "mdnocst_rollout_plan_set_constraints": (_I, [_P, _P, _P, _P, _L, _P, _I, _P, _I, _D, _P, _P, _P]),
 }
 
-# include/mdno_pbc_train.h (training under a periodic box: edge attributes as a function of positions on the minimum
-# image; additive, no version number of its own): name -> (restype, argtypes), kept in step with that header
-# (tests/test_pbc_train_host.py checks both ways).  The name starts with mdnopbt_, for the reason mdnoens_ has (the
-# header says so too).  `box` is a HOST pointer to three doubles.
+# include/mdno_pbc_train.h: training under a periodic box (edge attributes as a function of positions on the minimum
+# image).  Prefix mdnopbt_.  `box` is a HOST pointer to three doubles.
 PBC_TRAIN_SIGNATURES = {
     "mdnopbt_edge_attr_from_pos": (_I, [_P, _P, _P, _P, _L, _I, _D, _P, _P, _P]),
 }
 
+# THE REGISTRY of the C ABI: every header under include/ with its table.  The contract, for all of them alike:
+#   * a header's declarations are its table's names, with the table's arities, and every one is exported by libmdno.so;
+#     the library exports no other name that starts with mdno;
+#   * a name stands in ONE table (the merge below raises otherwise), so a new header may use any free name: mdno_ is
+#     fine.  The prefixes mdnoens_ ... mdnopbt_ of the later tables are kept because they are ABI, not because
+#     anything still asks for them;
+#   * mdno.h and mdno_train.h carry a version number each (ABI_VERSION, TRAIN_ABI_VERSION); the others are additive
+#     and carry none;
+#   * every header here is part of the library's build id (source_build_id), and include/ holds no other header.
+# tests/test_cabi_tables.py checks all of it, per header and once over the whole.  A new header is: the header, its table,
+# one line here.
+TABLES = (
+    ("mdno.h", SIGNATURES),
+    ("mdno_train.h", TRAIN_SIGNATURES),
+    ("mdno_noise.h", NOISE_SIGNATURES),
+    ("mdno_unroll.h", UNROLL_SIGNATURES),
+    ("mdno_pbc.h", PBC_SIGNATURES),
+    ("mdno_observe.h", OBSERVE_SIGNATURES),
+    ("mdno_dynamics.h", DYNAMICS_SIGNATURES),
+    ("mdno_ensemble.h", ENSEMBLE_SIGNATURES),
+    ("mdno_conformations.h", CONFORMATIONS_SIGNATURES),
+    ("mdno_essential.h", ESSENTIAL_SIGNATURES),
+    ("mdno_markov.h", MARKOV_SIGNATURES),
+    ("mdno_internal.h", INTERNAL_SIGNATURES),
+    ("mdno_internal_grad.h", INTERNAL_GRAD_SIGNATURES),
+    ("mdno_constrain.h", CONSTRAIN_SIGNATURES),
+    ("mdno_pbc_train.h", PBC_TRAIN_SIGNATURES),
+)
+
+
+def merge_tables(tables=TABLES) -> dict:
+    """name -> (header, restype, argtypes) over all tables; a name in two of them is an error."""
+    merged = {}
+    for header, table in tables:
+        for name, (res, args) in table.items():
+            if name in merged:
+                raise MdnoError(f"{name} stands in the tables of {merged[name][0]} and of {header}")
+            merged[name] = (header, res, args)
+    return merged
+
+
+BINDINGS = merge_tables()
+
 _lib = None
 
 
-def source_build_id() -> str | None:
-    """The id csrc/build.sh compiles into the library, recomputed from the tree: sha256 over csrc/*.{hip,h,sh},
-    include/mdno.h and include/mdno_train.h (bytes, C-locale name order), first 16 hex digits.  None where the sources are not beside the
-    package (a binary-only install)."""
+def source_build_id(root: Path | None = None) -> str | None:
+    """The id csrc/build.sh compiles into the library, recomputed from the tree (or from a copy of it at `root`): sha256
+    over csrc/*.{hip,h,sh}, then over every header of TABLES under include/ (bytes, C-locale name order each), first 16
+    hex digits.  None where any of them is not beside the package (a binary-only install)."""
     import hashlib
-    csrc = _HERE / "csrc"
-    header = _HERE.parent / "include" / "mdno.h"
-    train_header = header.with_name("mdno_train.h")
-    if not csrc.is_dir() or not header.exists() or not train_header.exists():
+    root = _HERE.parent if root is None else Path(root)
+    csrc = root / _HERE.name / "csrc"
+    headers = [root / "include" / name for name in sorted((h for h, _ in TABLES), key=str.encode)]
+    if not csrc.is_dir() or not all(f.exists() for f in headers):
         return None
     files = sorted([f for f in csrc.iterdir() if f.suffix in (".hip", ".h", ".sh")], key=lambda f: str(f).encode())
     h = hashlib.sha256()
-    for f in files + [header, train_header]:
+    for f in files + headers:
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
 
@@ -330,12 +354,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP library is not built. Run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (or molecular_dynamics_neural_operator_amd/csrc/build.sh). There is no CPU fallback.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + \
-            list(UNROLL_SIGNATURES.items()) + list(PBC_SIGNATURES.items()) + list(OBSERVE_SIGNATURES.items()) + \
-            list(DYNAMICS_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(CONFORMATIONS_SIGNATURES.items()) + \
-            list(ESSENTIAL_SIGNATURES.items()) + list(MARKOV_SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + \
-            list(INTERNAL_GRAD_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()) + \
-            list(PBC_TRAIN_SIGNATURES.items()):
+    for name, (_, res, args) in BINDINGS.items():
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -348,7 +367,7 @@ def load() -> C.CDLL:
     # (an experimental build — scripts/micro/build_exp.sh, loaded through MDNO_LIB — says so in its build id; MDNO_LIB
     # pointing at any other library, the in-tree one included, does not switch the check off)
     if want is not None and have != want and have != "experimental":
-        raise MdnoError(f"{LIB_PATH} was built from other sources (build id {have}, the tree is {want}): run "
+        raise MdnoError(f"{LIB_PATH} was built from other sources (build id {have}; csrc/ and include/ of the tree give {want}): run "
                         f"molecular_dynamics_neural_operator_amd/csrc/build.sh — a stale library is never used")
     _lib = lib
     return lib

@@ -40,7 +40,7 @@ class GuardError(AssertionError):
 
 
 def header_functions(header: Path = HEADER):
-    """include/mdno.h parsed the way tests/test_cabi.py does: name -> [(type, parameter name), ...]."""
+    """include/mdno.h parsed the way tests/cabi.py does, keeping the parameters: name -> [(type, parameter name), ...]."""
     text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
     out = {}
     for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):

@@ -1,20 +1,17 @@
 """Distance-constraint projection without a GPU (include/mdno_constrain.h): the greedy colouring of
-the package against the restatement's (tests/constrain_ref.py) and the colour counts it must give; the header, the ctypes
-table and the library's exports agree; the entry points and the Python layer validate before any device work; and the
+the package against the restatement's (tests/constrain_ref.py) and the colour counts it must give; what is particular
+to the header and its ctypes table (that header, table and exports agree is tests/test_cabi_tables.py's); the entry points and the Python layer validate before any device work; and the
 properties the restatement itself must have, since the device is held to it bit for bit (tests/test_gpu_constrain.py)."""
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import constrain_ref as R
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_constrain.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_constrain.h"
 NAMES = {"mdnocst_project", "mdnocst_rollout_plan_set_constraints"}
 
 
@@ -103,42 +100,10 @@ def test_host_validation_raises():
 
 
 # ------------------------------------------------------------------------------------------------ header, table, exports
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdnocst_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_constrain_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.CONSTRAIN_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES) | set(_lib.UNROLL_SIGNATURES) | \
-        set(_lib.PBC_SIGNATURES) | set(_lib.OBSERVE_SIGNATURES) | set(_lib.DYNAMICS_SIGNATURES) | set(_lib.ENSEMBLE_SIGNATURES) | \
-        set(_lib.CONFORMATIONS_SIGNATURES) | set(_lib.ESSENTIAL_SIGNATURES) | set(_lib.MARKOV_SIGNATURES) | \
-        set(_lib.INTERNAL_SIGNATURES) | set(_lib.INTERNAL_GRAD_SIGNATURES)
-    assert not set(decls) & others and not any(n.startswith("mdnocst_") for n in others)
-    assert not any(n.startswith(("mdno_", "mdnoens_", "mdnoconf_", "mdnopca_", "mdnomsm_", "mdnoic_", "mdnoicg_")) for n in decls)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_constrain.h but not exported"
-        assert len(_lib.CONSTRAIN_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
-        assert getattr(lib, name).argtypes == _lib.CONSTRAIN_SIGNATURES[name][1]              # bound by load()
-    assert {n for n in exported if n.startswith("mdnocst_")} == set(decls)                    # and nothing exported undeclared
+    assert set(_lib.CONSTRAIN_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == _lib.ABI_VERSION == 15 and lib.mdno_train_abi_version() == _lib.TRAIN_ABI_VERSION == 1
     assert (CSRC / "constrain.hip").exists()                                                  # inside the library's content hash
     text = HEADER.read_text()

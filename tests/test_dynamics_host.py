@@ -1,46 +1,24 @@
-"""Dynamical scoring without a GPU: include/mdno_dynamics.h, the ctypes table and the library's exports agree and are
-disjoint from the other six tables; every refusal of the header comes back as MDNO_EINVAL, or is raised as MdnoError,
+"""Dynamical scoring without a GPU: what is particular to include/mdno_dynamics.h and its ctypes table (that header,
+table and exports agree is tests/test_cabi_tables.py's); every refusal of the header comes back as MDNO_EINVAL, or is raised as MdnoError,
 before any device work; the workspace sizes are monotone; the numpy restatement of the rules (tests/dynamics_ref.py) has
 the properties the GPU tests lean on; and the arithmetic of forecast.DisplacementStats holds against closed forms."""
 import ctypes as C
 import math
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import dynamics_ref as ref
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_dynamics.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_dynamics.h"
 NAMES = {"mdno_displacement_stats_workspace_bytes", "mdno_displacement_stats", "mdno_velocity_autocorrelation_workspace_bytes",
          "mdno_velocity_autocorrelation", "mdno_unwrap_frames"}
 BAD_BOXES = [(-1.0, 20.0, 20.0), (20.0, float("nan"), 20.0), (20.0, 20.0, float("inf")), (-0.5, 0.0, 0.0)]
 FAKE = 0x10000          # a made-up address: nothing may dereference it
 BIG = 1 << 30
-
-
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
 
 
 def box3(*v):
@@ -52,19 +30,9 @@ def lag_array(*v):
 
 
 def test_dynamics_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.DYNAMICS_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES) | set(_lib.UNROLL_SIGNATURES) | \
-        set(_lib.PBC_SIGNATURES) | set(_lib.OBSERVE_SIGNATURES)
-    assert not set(decls) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_dynamics.h but not exported"
-        assert len(_lib.DYNAMICS_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
-    declared_everywhere = others | set(decls)
-    assert {n for n in exported if n.startswith("mdno_")} <= declared_everywhere          # and nothing exported undeclared
+    assert set(_lib.DYNAMICS_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 == _lib.ABI_VERSION and lib.mdno_train_abi_version() == 1          # additive: both stay
     assert (CSRC / "dynamics.hip").exists()                                            # inside the library's content hash
     text = HEADER.read_text()

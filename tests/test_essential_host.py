@@ -1,12 +1,10 @@
-"""Essential dynamics without a GPU: include/mdno_essential.h, the ctypes table and the library's exports agree and are
-disjoint from the other nine tables; every refusal of the header comes back before any device work; the workspace size is
+"""Essential dynamics without a GPU: what is particular to include/mdno_essential.h and its ctypes table (that header,
+table and exports agree is tests/test_cabi_tables.py's); every refusal of the header comes back before any device work; the workspace size is
 monotone and independent of the row count; the row-split rule of ops.covariance_row_split obeys the header's bounds; and
 forecast.Covariance, pca, tica, rmsip and free_energy hold on closed-form toys fed from the numpy restatement
 (tests/essential_ref.py) on CPU tensors."""
 import math
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,51 +12,19 @@ import torch
 
 import cross_rmsd_ref as cref
 import essential_ref as ref
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_essential.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_essential.h"
 NAMES = {"mdnopca_superpose", "mdnopca_feature_sums", "mdnopca_covariance_workspace_bytes", "mdnopca_covariance", "mdnopca_project"}
 FAKE = 0x10000          # a made-up address: nothing may dereference it
 BIG = 1 << 62
 IMAX = (1 << 31) - 1
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdnopca_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_essential_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.ESSENTIAL_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES) | set(_lib.UNROLL_SIGNATURES) | \
-        set(_lib.PBC_SIGNATURES) | set(_lib.OBSERVE_SIGNATURES) | set(_lib.DYNAMICS_SIGNATURES) | set(_lib.ENSEMBLE_SIGNATURES) | \
-        set(_lib.CONFORMATIONS_SIGNATURES)
-    assert not set(decls) & others and not any(n.startswith("mdnopca_") for n in others)
-    assert not any(n.startswith(("mdno_", "mdnoens_", "mdnoconf_")) for n in decls)       # the other headers' tests own those
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_essential.h but not exported"
-        assert len(_lib.ESSENTIAL_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
-        assert getattr(lib, name).argtypes == _lib.ESSENTIAL_SIGNATURES[name][1]          # bound by load()
-    assert {n for n in exported if n.startswith("mdnopca_")} == set(decls)                # and nothing exported undeclared
+    assert set(_lib.ESSENTIAL_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 == _lib.ABI_VERSION and lib.mdno_train_abi_version() == 1 == _lib.TRAIN_ABI_VERSION
     assert (CSRC / "essential.hip").exists()                                              # inside the library's content hash
     text = HEADER.read_text()

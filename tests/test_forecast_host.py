@@ -11,16 +11,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from cabi import lib  # noqa: F401  (the fixture)
 from conftest import load_golden, write_golden_trajectory
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
 
 
 def test_c_entries_refuse_bad_arguments_without_a_device(lib):

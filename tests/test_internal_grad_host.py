@@ -1,5 +1,5 @@
-"""The gradient of the internal coordinates without a GPU: include/mdno_internal_grad.h, the ctypes table and the library's
-exports agree (only the mdnoicg_ names are looked at); every refusal of the header comes back before any device work;
+"""The gradient of the internal coordinates without a GPU: what is particular to include/mdno_internal_grad.h and its ctypes
+table (that header, table and exports agree is tests/test_cabi_tables.py's); every refusal of the header comes back before any device work;
 forecast.Featurizer.incidence builds the table the header describes; the numpy restatement (tests/internal_grad_ref.py) is
 held to an independent formulation — torch autograd in fp64 of a plain restatement of the FEATURES — and keeps the skip rules;
 training.StructureLoss validates on the host.
@@ -18,8 +18,6 @@ atom's chain mixes them.  The chains keep internal_ref.conditioning >= 0.05 for 
 seeds are the first six of 0, 1, 2, ... that do, open and under the box."""
 import ctypes as C
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -27,10 +25,9 @@ import torch
 
 import internal_grad_ref as gref
 import internal_ref as ref
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_internal_grad.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_internal_grad.h"
 NAMES = {"mdnoicg_features_bwd"}
 FAKE = 0x10000          # a made-up address: nothing may dereference it
 SEEDS = (0, 1, 3, 6, 7, 8)
@@ -38,41 +35,14 @@ K_GATE = {"distances": 5.4, "angles": 305.0, "dihedrals": 731.0}
 BOX = (7.0, 0.0, 9.5)
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdnoicg_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.INTERNAL_GRAD_SIGNATURES) == NAMES
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_internal_grad.h but not exported"
-        assert len(_lib.INTERNAL_GRAD_SIGNATURES[name][1]) == nargs == 20, f"{name}: binding arity != header"
-        assert getattr(lib, name).argtypes == _lib.INTERNAL_GRAD_SIGNATURES[name][1]          # bound by load()
-    assert {n for n in exported if n.startswith("mdnoicg_")} == set(decls)                    # and nothing exported undeclared
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.INTERNAL_SIGNATURES) | set(_lib.MARKOV_SIGNATURES)
-    assert not set(decls) & others and not any(n.startswith("mdnoicg_") for n in others)
+    assert set(_lib.INTERNAL_GRAD_SIGNATURES) == NAMES
+    assert len(_lib.INTERNAL_GRAD_SIGNATURES["mdnoicg_features_bwd"][1]) == 20
     assert set(_lib.INTERNAL_SIGNATURES) == {"mdnoic_features", "mdnoic_column_histogram"}    # that table stays as it is
     assert lib.mdno_abi_version() == _lib.ABI_VERSION and lib.mdno_train_abi_version() == _lib.TRAIN_ABI_VERSION
-    head = (REPO / "include" / "mdno.h").read_text() + (REPO / "include" / "mdno_train.h").read_text()
+    head = (INCLUDE / "mdno.h").read_text() + (INCLUDE / "mdno_train.h").read_text()
     assert f"#define MDNO_ABI_VERSION {_lib.ABI_VERSION}" in head and f"#define MDNO_TRAIN_ABI_VERSION {_lib.TRAIN_ABI_VERSION}" in head
     assert (CSRC / "internal_grad.hip").exists() and (CSRC / "internal_rule.h").exists()      # inside the library's content hash
     text = HEADER.read_text()
@@ -80,7 +50,7 @@ def test_header_table_and_exports_agree(lib):
         m = re.search(rf"#define MDNO_ICG_{name} (\S.*)", text)
         assert m and (value is None or int(m.group(1)) == value), name
     assert "(1 << 29)" in text and ops.ICG_MAX_ITEMS == 1 << 29 == _lib.INTERNAL_GRAD_MAX_ITEMS
-    assert "mdnoicg_" in text and "THE PREFIX" in text and "test_internal_host.py" in text   # the header says why the names differ
+    assert "mdnoicg_" in text and "THE PREFIX" in text and "is ABI" in text                  # the header says why the names differ
     assert '#include "mdno_internal.h"' in text                                               # dtypes, forms and G are that header's
     src = (CSRC / "internal_grad.hip").read_text()
     assert '#include "../../include/mdno_internal_grad.h"' in src and '#include "internal_rule.h"' in src

@@ -1,56 +1,27 @@
-"""Internal coordinates without a GPU: include/mdno_internal.h, the ctypes table and the library's exports agree (only the
-mdnoic_ names are looked at); every refusal of the header comes back before any device work; the numpy restatement
+"""Internal coordinates without a GPU: what is particular to include/mdno_internal.h and its ctypes table (that header,
+table and exports agree is tests/test_cabi_tables.py's); every refusal of the header comes back before any device work; the numpy restatement
 (tests/internal_ref.py) gives the known values on known geometry and is invariant under rigid motion to first order;
 forecast.Featurizer counts, names and validates on the host; discretize(featurizer=None) takes the path it always took."""
 import ctypes as C
 import math
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import internal_ref as ref
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_internal.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_internal.h"
 NAMES = {"mdnoic_features", "mdnoic_column_histogram"}
 FAKE = 0x10000          # a made-up address: nothing may dereference it
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdnoic_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_internal_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.INTERNAL_SIGNATURES) == NAMES
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_internal.h but not exported"
-        assert len(_lib.INTERNAL_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
-        assert getattr(lib, name).argtypes == _lib.INTERNAL_SIGNATURES[name][1]               # bound by load()
-    assert {n for n in exported if n.startswith("mdnoic_")} == set(decls)                     # and nothing exported undeclared
+    assert set(_lib.INTERNAL_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == _lib.ABI_VERSION and lib.mdno_train_abi_version() == _lib.TRAIN_ABI_VERSION
     assert (CSRC / "internal.hip").exists()                                                   # inside the library's content hash
     text = HEADER.read_text()

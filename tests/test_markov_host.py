@@ -1,22 +1,19 @@
-"""Markov state models without a GPU: include/mdno_markov.h, the ctypes table and the library's exports agree and are
-disjoint from the other ten tables; every refusal of the header comes back before any device work; the workspace sizes are
+"""Markov state models without a GPU: what is particular to include/mdno_markov.h and its ctypes table (that header,
+table and exports agree is tests/test_cabi_tables.py's); every refusal of the header comes back before any device work; the workspace sizes are
 monotone; forecast.MarkovModel holds on closed-form chains; and the bookkeeping of the transition counts is checked on
 the numpy restatement (tests/markov_ref.py) fed through forecast.TransitionCounts on CPU tensors."""
 import ctypes as C
 import math
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import markov_ref as ref
+from cabi import CSRC, INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_markov.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+HEADER = INCLUDE / "mdno_markov.h"
 NAMES = {"mdnomsm_assign_workspace_bytes", "mdnomsm_assign", "mdnomsm_kcenters_workspace_bytes", "mdnomsm_kcenters",
          "mdnomsm_centroid_sums", "mdnomsm_transition_counts"}
 FAKE = 0x10000          # a made-up address: nothing may dereference it
@@ -25,41 +22,10 @@ IMAX = (1 << 31) - 1
 SIZE_MAX = (1 << 64) - 1
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdnomsm_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_markov_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib, ops
-    decls = declared_functions()
-    assert set(decls) == set(_lib.MARKOV_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES) | set(_lib.UNROLL_SIGNATURES) | \
-        set(_lib.PBC_SIGNATURES) | set(_lib.OBSERVE_SIGNATURES) | set(_lib.DYNAMICS_SIGNATURES) | set(_lib.ENSEMBLE_SIGNATURES) | \
-        set(_lib.CONFORMATIONS_SIGNATURES) | set(_lib.ESSENTIAL_SIGNATURES)
-    assert not set(decls) & others and not any(n.startswith("mdnomsm_") for n in others)
-    assert not any(n.startswith(("mdno_", "mdnoens_", "mdnoconf_", "mdnopca_")) for n in decls)   # the other headers' tests own those
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_markov.h but not exported"
-        assert len(_lib.MARKOV_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
-        assert getattr(lib, name).argtypes == _lib.MARKOV_SIGNATURES[name][1]                 # bound by load()
-    assert {n for n in exported if n.startswith("mdnomsm_")} == set(decls)                    # and nothing exported undeclared
+    assert set(_lib.MARKOV_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 == _lib.ABI_VERSION and lib.mdno_train_abi_version() == 1 == _lib.TRAIN_ABI_VERSION
     assert (CSRC / "markov.hip").exists()                                                     # inside the library's content hash
     text = HEADER.read_text()

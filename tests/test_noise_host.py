@@ -1,20 +1,15 @@
 """csrc/philox.h without a GPU: the numpy restatement (tests/philox_ref.py) reproduces the published Philox4x32-10
-known-answer vectors; philox.h compiled for the host gives the restatement's words bit for bit; include/mdno_noise.h,
-the ctypes table and the library's exports agree, and the new entry points validate before any device work."""
+known-answer vectors; philox.h compiled for the host gives the restatement's words bit for bit; the names of
+include/mdno_noise.h's table are pinned (tests/test_cabi_tables.py holds header, table and exports together), and the entry points validate before any device work."""
 import os
-import re
 import shutil
 import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import philox_ref as P
-
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_noise.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+from cabi import CSRC, lib  # noqa: F401  (lib: the fixture)
 
 # Random123's kat_vectors for philox4x32 with 10 rounds: counter, key, expected
 KAT = [
@@ -111,36 +106,10 @@ def test_philox_header_compiled_for_the_host(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ header, table, exports
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_noise_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib
-    decls = declared_functions()
-    assert set(decls) == set(_lib.NOISE_SIGNATURES) == {"mdno_noise_fill", "mdno_noise_add_window",
-                                                        "mdno_rollout_plan_set_noise"}
-    assert not set(decls) & (set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES))
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_noise.h but not exported"
-        assert len(_lib.NOISE_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
+    assert set(_lib.NOISE_SIGNATURES) == {"mdno_noise_fill", "mdno_noise_add_window", "mdno_rollout_plan_set_noise"}
     assert lib.mdno_abi_version() == 15 and lib.mdno_train_abi_version() == 1          # additive: both stay
     assert (CSRC / "philox.h").exists() and (CSRC / "noise.hip").exists()              # inside the library's content hash
 

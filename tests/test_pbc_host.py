@@ -1,42 +1,19 @@
-"""Periodic boxes without a GPU: include/mdno_pbc.h, the ctypes table and the library's exports agree and are disjoint
-from the other four tables; every refusal of the rule (a periodic axis shorter than 2 * cutoff, a negative, NaN or Inf
+"""Periodic boxes without a GPU: what is particular to include/mdno_pbc.h and its ctypes table (that header, table and
+exports agree is tests/test_cabi_tables.py's); every refusal of the rule (a periodic axis shorter than 2 * cutoff, a negative, NaN or Inf
 length, a null plan, a null attribute buffer with a periodic axis, ker_in != 6) comes back as MDNO_EINVAL, or is raised
 as MdnoError, before any device work; and the numpy restatement of the rule (tests/test_gpu_pbc.py) has the properties
 the GPU tests lean on."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_pbc.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+from cabi import CSRC, lib  # noqa: F401  (lib: the fixture)
+
 NAMES = {"mdno_radius_graph_pbc", "mdno_rollout_plan_set_box", "mdno_forecast_score_pbc", "mdno_contact_maps_pbc"}
 BAD_BOXES = [(15.9, 20.0, 20.0), (20.0, 20.0, 1e-3), (-1.0, 20.0, 20.0), (20.0, float("nan"), 20.0),
              (20.0, 20.0, float("inf")), (-0.5, 0.0, 0.0)]
-
-
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
 
 
 def box3(*v):
@@ -44,16 +21,9 @@ def box3(*v):
 
 
 def test_pbc_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib
-    decls = declared_functions()
-    assert set(decls) == set(_lib.PBC_SIGNATURES) == NAMES
-    others = set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES) | set(_lib.UNROLL_SIGNATURES)
-    assert not set(decls) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_pbc.h but not exported"
-        assert len(_lib.PBC_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
+    assert set(_lib.PBC_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 and lib.mdno_train_abi_version() == 1          # additive: both stay
     assert (CSRC / "pbc.h").exists() and (CSRC / "pbc.hip").exists()                   # inside the library's content hash
 

@@ -1,42 +1,18 @@
-"""Training under a periodic box without a GPU: include/mdno_pbc_train.h, the ctypes table and the library's exports
-agree and are disjoint from every other table; the entry refuses what the other periodic entries refuse, before any
+"""Training under a periodic box without a GPU: what is particular to include/mdno_pbc_train.h and its ctypes table (that
+header, table and exports agree is tests/test_cabi_tables.py's); the entry refuses what the other periodic entries refuse, before any
 launch; the Python layers raise MdnoError on the same boxes and on ker_in != 6 without touching a device; and the numpy
 restatement of the attribute rule, and the fp64 replica the GPU tests compare with (tests/test_gpu_pbc_train.py), have the
 properties those tests lean on."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
+from cabi import CSRC, lib  # noqa: F401  (lib: the fixture)
 from test_pbc_host import BAD_BOXES
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_pbc_train.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
 NAMES = {"mdnopbt_edge_attr_from_pos"}
-
-
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
 
 
 def box3(*v):
@@ -44,19 +20,9 @@ def box3(*v):
 
 
 def test_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib
-    decls = declared_functions()
-    assert set(decls) == set(_lib.PBC_TRAIN_SIGNATURES) == NAMES
-    others = set()
-    for name in dir(_lib):
-        if name.endswith("SIGNATURES") and name != "PBC_TRAIN_SIGNATURES":
-            others |= set(getattr(_lib, name))
-    assert len(others) > 100 and not set(decls) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert {n for n in exported if n.startswith("mdnopbt_")} == NAMES
-    for name, nargs in decls.items():
-        assert len(_lib.PBC_TRAIN_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
+    assert set(_lib.PBC_TRAIN_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 and lib.mdno_train_abi_version() == 1          # additive: both stay
     assert (CSRC / "pbc_train.hip").exists()                                           # inside the library's content hash
     assert '#include "pbc.h"' in (CSRC / "pbc_train.hip").read_text()                  # the rule is included, not restated

@@ -1,47 +1,17 @@
-"""include/mdno_train.h — the second public header of libmdno.so (training on dense graphs): its declarations, the
-ctypes table `_lib.TRAIN_SIGNATURES` and the library's exports agree, and `train_conv_mode="factored"` is refused on
+"""include/mdno_train.h — the second public header of libmdno.so (training on dense graphs): what is particular to it
+(that header, table and exports agree is tests/test_cabi_tables.py's), and `train_conv_mode="factored"` is refused on
 a CPU model, before any device work, where the factored training path does not apply.  No GPU needed."""
-import re
-import subprocess
-from pathlib import Path
-
 import pytest
 import torch
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_train.h"
+from cabi import INCLUDE, lib  # noqa: F401  (lib: the fixture)
 
-
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = REPO / "molecular_dynamics_neural_operator_amd" / "csrc" / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+HEADER = INCLUDE / "mdno_train.h"
 
 
 def test_train_header_table_and_exports_agree(lib):
     from molecular_dynamics_neural_operator_amd import _lib
-    decls = declared_functions()
-    assert len(decls) == 6 and all(n.startswith("mdno_train_") for n in decls)
-    assert set(decls) == set(_lib.TRAIN_SIGNATURES)
-    assert not set(decls) & set(_lib.SIGNATURES)
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_train.h but not exported"
-        assert len(_lib.TRAIN_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
+    assert len(_lib.TRAIN_SIGNATURES) == 6 and all(n.startswith("mdno_train_") for n in _lib.TRAIN_SIGNATURES)
     assert lib.mdno_train_abi_version() == _lib.TRAIN_ABI_VERSION == 1
     assert "#define MDNO_TRAIN_ABI_VERSION 1" in HEADER.read_text()
 
@@ -57,19 +27,6 @@ def test_train_entry_points_validate_before_device_work(lib):
     assert rc == _lib.EINVAL and b"null pointer" in lib.mdno_last_error()
     rc = lib.mdno_train_moment_bwd(*([None] * 7), 1, 1, 128, 1, 0, *([None] * 10), 0, None)
     assert rc == _lib.EINVAL and b"null pointer" in lib.mdno_last_error()
-
-
-def test_library_id_covers_the_train_header(lib, tmp_path, monkeypatch):
-    """The content hash that ties libmdno.so to the tree reads include/mdno_train.h too."""
-    import hashlib
-    from molecular_dynamics_neural_operator_amd import _lib
-    csrc = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
-    files = sorted([f for f in csrc.iterdir() if f.suffix in (".hip", ".h", ".sh")], key=lambda f: str(f).encode())
-    h = hashlib.sha256()
-    for f in files + [REPO / "include" / "mdno.h", HEADER]:
-        h.update(f.read_bytes())
-    assert _lib.source_build_id() == h.hexdigest()[:16] == lib.mdno_build_id().decode()
-    assert "mdno_train.h" in (csrc / "build.sh").read_text()
 
 
 @pytest.mark.parametrize("case", ["bf16", "ker_width_100", "width_32"])

@@ -1,50 +1,20 @@
-"""include/mdno_unroll.h without a GPU: the header, the ctypes table (`_lib.UNROLL_SIGNATURES`) and the library's
-exports agree; every new entry point validates its arguments before any device work; the Python layer refuses what
+"""include/mdno_unroll.h without a GPU: the names of its ctypes table (`_lib.UNROLL_SIGNATURES`) are pinned (that
+header, table and exports agree is tests/test_cabi_tables.py's); every new entry point validates its arguments before any device work; the Python layer refuses what
 an unrolled step cannot do (horizon != 1, targets past the data, bf16 storage, host-collated lists) on the host."""
-import re
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
 
-REPO = Path(__file__).resolve().parents[1]
-HEADER = REPO / "include" / "mdno_unroll.h"
-CSRC = REPO / "molecular_dynamics_neural_operator_amd" / "csrc"
+from cabi import CSRC, lib  # noqa: F401  (lib: the fixture)
+
 NAMES = {"mdno_edge_mlp_input_bwd", "mdno_edge_attr_from_pos", "mdno_edge_attr_pos_bwd", "mdno_node_prologue_bwd_frames",
          "mdno_collate_targets"}
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"^(?:int|size_t|const char\*)\s+(mdno_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return decls
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from molecular_dynamics_neural_operator_amd import _lib
-    stamp = CSRC / "build" / "BUILD_ID"
-    if not _lib.LIB_PATH.exists() or not stamp.exists() or stamp.read_text().split()[0] != _lib.source_build_id():
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
 def test_unroll_header_table_and_exports_agree(lib):
+    """What is particular to this header; that header, table and exports agree is tests/test_cabi_tables.py's."""
     from molecular_dynamics_neural_operator_amd import _lib
-    decls = declared_functions()
-    assert set(decls) == set(_lib.UNROLL_SIGNATURES) == NAMES
-    assert not set(decls) & (set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.NOISE_SIGNATURES))
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name, nargs in decls.items():
-        assert name in exported, f"{name} declared in mdno_unroll.h but not exported"
-        assert len(_lib.UNROLL_SIGNATURES[name][1]) == nargs, f"{name}: binding arity != header"
+    assert set(_lib.UNROLL_SIGNATURES) == NAMES
     assert lib.mdno_abi_version() == 15 and lib.mdno_train_abi_version() == 1          # additive: both stay
     assert (CSRC / "input_grad.hip").exists()                                          # inside the library's content hash
 

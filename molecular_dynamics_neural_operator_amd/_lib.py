@@ -281,6 +281,17 @@ PBC_TRAIN_SIGNATURES = {
     "mdnopbt_edge_attr_from_pos": (_I, [_P, _P, _P, _P, _L, _I, _D, _P, _P, _P]),
 }
 
+# include/mdno_contacts.h: contact statistics over time (per-pair counts and distance sums per time block, the contact bits
+# of a pair list, their autocorrelation).  Prefix mdnocm_.  `box` is a HOST pointer to three doubles, `lags` a HOST pointer
+# to L int32; `pairs` and `cut` lie on the device.
+CONTACTS_TILE = 64                  # MDNOCM_TILE
+CONTACTS_MAX_LAGS = 1024            # MDNOCM_MAX_LAGS
+CONTACTS_SIGNATURES = {
+    "mdnocm_pair_statistics": (_I, [_P, _I, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
+    "mdnocm_contact_bits": (_I, [_P, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "mdnocm_contact_correlation": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
+}
+
 # THE REGISTRY of the C ABI: every header under include/ with its table.  The contract, for all of them alike:
 #   * a header's declarations are its table's names, with the table's arities, and every one is exported by libmdno.so;
 #     the library exports no other name that starts with mdno;
@@ -308,6 +319,7 @@ TABLES = (
     ("mdno_internal_grad.h", INTERNAL_GRAD_SIGNATURES),
     ("mdno_constrain.h", CONSTRAIN_SIGNATURES),
     ("mdno_pbc_train.h", PBC_TRAIN_SIGNATURES),
+    ("mdno_contacts.h", CONTACTS_SIGNATURES),
 )
 
 

@@ -103,6 +103,20 @@ walked colour by colour; include/mdno_constrain.h has the rule):
     cons = DistanceConstraints.from_frames(truth, ft, margin=0.1)  # every listed pair inside the truth's own range
     frames, rep = project_constraints(frames, cons, iterations=8)  # ConstraintReport: sweeps i32, viol_in, viol_out f64 [S, M]
     RolloutEngine(model, M, N, W, constraints=cons)                # the same projection at the end of every step
+
+Contact statistics.  The three pictures a fast folder is judged by — the contact-probability map of the run beside the
+truth's, the fraction of native contacts Q(t) against a native set fixed ONCE, and how long a contact lives — need the
+reduction over time, not one dense map per frame (csrc/contacts.hip: per-pair accumulators in registers over blocks of
+steps, one bit per (member, pair, step); include/mdno_contacts.h has the rule):
+
+    st = eng.pair_statistics(block_len=64)                      # PairStatistics: count i32, sum_r, sum_r2 f64 [Bk, M, N, N]
+    tr = pair_statistics(truth[:, None], eng.threshold)         # the truth as one member
+    st.total().map_error(tr.total(), min_separation=3)          # f64 [M]: mean |P_run - P_truth| over the pairs
+    native = ContactPairs.native(folded, 8.0, factor=1.2)       # or ContactPairs.from_statistics(tr): P >= 0.5 in the truth
+    cs = eng.contact_series(native)                             # ContactSeries: bits [M, P, S / 64], per_frame i32 [S, M]
+    cs.fraction()                                               # Q(t), f64 [S, M]
+    cc = cs.correlation()                                       # ContactCorrelation over ~33 log-spaced lags
+    cc.survival(), cc.lifetime(dt)                              # f64 [M, L]: P(contact at t + lag | contact at t); f64 [M]
 """
 from __future__ import annotations
 
@@ -1573,6 +1587,325 @@ def project_constraints(frames: torch.Tensor, constraints: DistanceConstraints, 
     res, sweeps, vin, vout = ops.project_constraints(frames.detach(), t.pairs, t.lo, t.hi, t.colour_ptr, t.weights, box=box,
                                                      iterations=iterations, tol=tol, out=out)
     return res, ConstraintReport(sweeps, vin, vout)
+
+
+# ------------------------------------------------------------------------------------------------
+# Contact statistics over time (csrc/contacts.hip, include/mdno_contacts.h has the rule)
+def _nan_ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """num / den in f64 (broadcast), NaN where den == 0; a NaN or Inf in num passes through."""
+    num, den = torch.broadcast_tensors(num.to(torch.float64), den.to(torch.float64))
+    return torch.where(den == 0, torch.full_like(den, float("nan")), num / torch.where(den == 0, torch.ones_like(den), den))
+
+
+@dataclass
+class PairStatistics:
+    """Per-pair statistics over blocks of consecutive steps (ops.pair_statistics): `count` i32 [Bk, M, N, N], the frames of
+    the block in which the pair is closer than `threshold`; `sum_r`, `sum_r2` f64 of the same shape (None without the
+    moments), the sums of the distance and of its square; `n_frames` i64 [Bk], the frames of every block.  Full symmetric
+    maps, diagonal included.  After `total()` the block axis is gone: [M, N, N] and a 0-dim `n_frames`.  Every method runs in
+    fp64 on the device of `count` and reads nothing back."""
+    count: torch.Tensor
+    sum_r: Optional[torch.Tensor]
+    sum_r2: Optional[torch.Tensor]
+    n_frames: torch.Tensor
+    threshold: float
+    box: Optional[Tuple[float, float, float]] = None
+
+    def _n(self) -> torch.Tensor:
+        return self.n_frames.to(torch.float64).reshape(self.n_frames.shape + (1, 1, 1))
+
+    def _moments(self, what: str):
+        if self.sum_r is None or self.sum_r2 is None:
+            raise MdnoError(f"{what}: these statistics were taken without the moments (moments=False)")
+        return self.sum_r, self.sum_r2
+
+    def total(self) -> "PairStatistics":
+        """The statistics of all blocks together: the blocks added in ASCENDING order, one elementwise add per block, so the
+        bits of the two sums are defined (those of the restatement with the same block_len).  No block: zero maps, 0 frames."""
+        if self.count.dim() == 3:
+            return self
+        Bk = self.count.shape[0]
+
+        def fold(t, dtype):
+            if t is None:
+                return None
+            if Bk == 0:
+                return torch.zeros(t.shape[1:], dtype=dtype, device=t.device)
+            acc = t[0].clone()
+            for b in range(1, Bk):
+                acc = acc + t[b]
+            return acc
+        return PairStatistics(fold(self.count, torch.int32), fold(self.sum_r, torch.float64), fold(self.sum_r2, torch.float64),
+                              self.n_frames.sum(), self.threshold, self.box)
+
+    def probability(self) -> torch.Tensor:
+        """count / n_frames: f64 [..., M, N, N], the contact-probability map; NaN for a block without frames."""
+        return _nan_ratio(self.count, self._n())
+
+    def mean_distance(self) -> torch.Tensor:
+        """sum_r / n_frames: f64 [..., M, N, N]; NaN for a block without frames or a pair with a non-finite distance."""
+        return _nan_ratio(self._moments("mean_distance")[0], self._n())
+
+    def distance_std(self) -> torch.Tensor:
+        """sqrt(max(sum_r2 / n - (sum_r / n)^2, 0)): f64 [..., M, N, N], the population standard deviation of the distance."""
+        sr, sr2 = self._moments("distance_std")
+        mean = _nan_ratio(sr, self._n())
+        var = _nan_ratio(sr2, self._n()) - mean * mean
+        return torch.sqrt(torch.where(var < 0, torch.zeros_like(var), var))          # (a NaN fails the test and stays)
+
+    def difference(self, other: "PairStatistics") -> torch.Tensor:
+        """probability() - other.probability(): the delta-probability map.  `other` may hold one member (the truth), which
+        is broadcast against this one's M."""
+        if not isinstance(other, PairStatistics):
+            raise MdnoError(f"difference: other is a {type(other).__name__}")
+        a, b = self.probability(), other.probability()
+        members = {a.shape[-3], b.shape[-3]}
+        if a.dim() != b.dim() or a.shape[-1] != b.shape[-1] or a.shape[:-3] != b.shape[:-3] or (len(members) == 2 and 1 not in members):
+            raise MdnoError(f"difference: maps of shape {tuple(a.shape)} and {tuple(b.shape)}")
+        return a - b
+
+    def map_error(self, other: "PairStatistics", min_separation: int = 0) -> torch.Tensor:
+        """The mean of |difference(other)| over the ordered pairs with |i - j| >= min_separation: f64 [..., M]; NaN where
+        no pair is that far apart."""
+        if isinstance(min_separation, bool) or not isinstance(min_separation, int) or min_separation < 0:
+            raise MdnoError(f"map_error: min_separation={min_separation!r}: expected an integer >= 0")
+        d = self.difference(other).abs()
+        idx = torch.arange(d.shape[-1], device=d.device)
+        keep = ((idx[:, None] - idx[None, :]).abs() >= min_separation).to(torch.float64)
+        return _nan_ratio((d * keep).sum((-2, -1)), keep.sum().expand(d.shape[:-2]))
+
+    def cpu(self) -> "PairStatistics":
+        return PairStatistics(self.count.cpu(), None if self.sum_r is None else self.sum_r.cpu(),
+                              None if self.sum_r2 is None else self.sum_r2.cpu(), self.n_frames.cpu(), self.threshold, self.box)
+
+    @staticmethod
+    def cat(parts: Sequence["PairStatistics"]) -> "PairStatistics":
+        """Statistics of disjoint member ranges of the same steps and blocks, members in order."""
+        p = parts[0]
+        join = lambda ts: None if ts[0] is None else torch.cat(ts, -3)      # noqa: E731
+        return PairStatistics(join([q.count for q in parts]), join([q.sum_r for q in parts]), join([q.sum_r2 for q in parts]),
+                              p.n_frames, p.threshold, p.box)
+
+
+def pair_statistics(frames: torch.Tensor, threshold: float = 8.0, box=None, block_len: int = 64, moments: bool = True) -> PairStatistics:
+    """frames f32 [S, M, N, 3] (device) -> `PairStatistics` over blocks of `block_len` steps: per pair the frames in contact
+    (closer than `threshold`, strictly) and, with `moments`, the sums of the distance and of its square, reduced over time on
+    the device (include/mdno_contacts.h has the rule) — the contact-probability map of a run without a dense map per frame.
+    `box` = (Lx, Ly, Lz), 0 for an open axis: distances by the minimum image; every periodic axis must be >= 2 * threshold.
+    Asynchronous on the current stream; CPU tensors and bad arguments raise `MdnoError` before any device work."""
+    threshold, box, block_len = ops.check_contact_args(threshold, box, block_len)
+    count, sum_r, sum_r2 = ops.pair_statistics(frames, threshold, box, block_len, bool(moments))
+    S = int(frames.shape[0])
+    n = [min(block_len, S - b * block_len) for b in range(count.shape[0])]
+    return PairStatistics(count, sum_r, sum_r2, torch.tensor(n, dtype=torch.int64, device=count.device), threshold, box)
+
+
+def _rule_distances(x: torch.Tensor, box) -> torch.Tensor:
+    """r f64 [N, N] of ONE host frame by the rule of include/mdno_contacts.h, in torch on the CPU (every operation rounded
+    once: elementwise kernels are not contracted): r[i, j] from d = x_j - x_i."""
+    x = x.detach().cpu().to(torch.float32).to(torch.float64)
+    d = x[None, :, :] - x[:, None, :]
+    sq = []
+    for a in range(3):
+        da = d[..., a]
+        L = 0.0 if box is None else float(box[a])
+        if L > 0.0:
+            da = da - torch.round(da * (1.0 / L)) * L          # (torch.round: half to even, as rint)
+        sq.append(da * da)
+    return torch.sqrt((sq[0] + sq[1]) + sq[2])
+
+
+@dataclass
+class ContactPairs:
+    """A list of pairs with one contact cutoff each — a native-contact definition: `pairs` i32 [P, 2], `cut` f64 [P],
+    `cut_max` (a Python float: the largest cutoff, what a periodic box is checked against), for frames of `n_atoms` atoms
+    (None: any frame that holds the largest index, `top`).  Built and validated on the host by `of`, `native` and
+    `from_statistics`; `.to(device)` moves the tensors."""
+    pairs: torch.Tensor
+    cut: torch.Tensor
+    cut_max: float
+    n_atoms: Optional[int] = None
+    top: int = -1
+
+    @staticmethod
+    def of(pairs, cut, n_atoms: Optional[int] = None) -> "ContactPairs":
+        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
+            raise MdnoError(f"ContactPairs: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        p = _index_array(pairs, 2, n_atoms, "pairs")
+        n_p = int(p.shape[0])
+        try:      # (Python numbers straight to f64)
+            c = cut.detach().cpu().to(torch.float64) if torch.is_tensor(cut) else torch.as_tensor(cut, dtype=torch.float64)
+            c = c.reshape(-1)
+        except (TypeError, ValueError, RuntimeError):
+            raise MdnoError("ContactPairs: cut is not an array of numbers") from None
+        if c.numel() == 1 and n_p != 1:
+            c = c.expand(n_p)
+        if c.numel() != n_p:
+            raise MdnoError(f"ContactPairs: {c.numel()} cutoffs for {n_p} pairs")
+        c = c.contiguous().clone()
+        if n_p and not (bool(torch.isfinite(c).all()) and bool((c >= 0).all())):
+            raise MdnoError("ContactPairs: cut must be finite and >= 0")
+        cut_max = float(c.max()) if n_p else 0.0
+        if n_p and not cut_max > 0.0:
+            raise MdnoError("ContactPairs: every cutoff is 0, no pair can be in contact")
+        return ContactPairs(p, c, cut_max, n_atoms, int(p.max()) if n_p else -1)
+
+    @staticmethod
+    def _separated(n: int, min_separation) -> Tuple[torch.Tensor, torch.Tensor]:
+        if isinstance(min_separation, bool) or not isinstance(min_separation, int) or min_separation < 0:
+            raise MdnoError(f"ContactPairs: min_separation={min_separation!r}: expected an integer >= 0")
+        i, j = torch.triu_indices(n, n, 1)
+        far = (j - i) >= min_separation
+        return i[far], j[far]
+
+    @staticmethod
+    def native(reference_frame, threshold: float = 8.0, min_separation: int = 3, factor: float = 1.0, box=None) -> "ContactPairs":
+        """The native contacts of ONE frame f32 [N, 3] (host or device; evaluated on the host by the rule): the pairs i < j with
+        j - i >= min_separation and d0 < threshold.  Each pair's cutoff is factor * d0 where factor != 1 (the usual
+        definition of Q: a native pair counts while it is closer than e.g. 1.2 x its native distance), else `threshold`."""
+        threshold, box, _ = ops.check_contact_args(threshold, box, 1, "ContactPairs.native")
+        factor = float(factor)
+        if not (math.isfinite(factor) and factor > 0.0):
+            raise MdnoError(f"ContactPairs.native: factor={factor}: expected a finite number > 0")
+        x = reference_frame if torch.is_tensor(reference_frame) else torch.as_tensor(reference_frame)
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise MdnoError(f"ContactPairs.native: reference_frame has shape {tuple(x.shape)}, expected ONE frame [N, 3]")
+        n = int(x.shape[0])
+        i, j = ContactPairs._separated(n, min_separation)
+        d0 = _rule_distances(x, box)[i, j]
+        keep = d0 < threshold
+        i, j, d0 = i[keep], j[keep], d0[keep]
+        cut = factor * d0 if factor != 1.0 else torch.full_like(d0, threshold)
+        return ContactPairs.of(torch.stack([i, j], 1), cut, n)
+
+    @staticmethod
+    def from_statistics(stats: PairStatistics, min_probability: float = 0.5, min_separation: int = 3) -> "ContactPairs":
+        """The pairs i < j with j - i >= min_separation whose contact probability over ALL of `stats` (one member: the truth)
+        is >= min_probability, each with the statistics' threshold as its cutoff.  One read-back of the probability map."""
+        if not isinstance(stats, PairStatistics):
+            raise MdnoError(f"ContactPairs.from_statistics: stats is a {type(stats).__name__}")
+        prob = stats.total().probability()
+        if prob.shape[0] != 1:
+            raise MdnoError(f"ContactPairs.from_statistics: the statistics hold {prob.shape[0]} members, expected one (the truth)")
+        prob = prob[0].cpu()
+        n = int(prob.shape[-1])
+        i, j = ContactPairs._separated(n, min_separation)
+        keep = prob[i, j] >= float(min_probability)
+        i, j = i[keep], j[keep]
+        return ContactPairs.of(torch.stack([i, j], 1), torch.full((int(i.numel()),), float(stats.threshold), dtype=torch.float64), n)
+
+    def __len__(self) -> int:
+        return int(self.pairs.shape[0])
+
+    def to(self, device) -> "ContactPairs":
+        return ContactPairs(self.pairs.to(device), self.cut.to(device), self.cut_max, self.n_atoms, self.top)
+
+    def check_frames(self, n_atoms: int) -> None:
+        if (self.n_atoms is not None and n_atoms != self.n_atoms) or self.top >= n_atoms:
+            want = f"{self.n_atoms}" if self.n_atoms is not None else f"more than {self.top}"
+            raise MdnoError(f"the contact pairs were built for frames of {want} atoms, these have {n_atoms}")
+
+
+@dataclass
+class ContactCorrelation:
+    """Contact autocorrelation counts (ops.contact_correlation): `origins`, `both` i32 [M, P, L] per member, pair and lag —
+    the steps t < S - lag in contact, and those in contact at t and at t + lag; `lags` i64 [L].  Every method runs in fp64
+    on the device of the counts and reads nothing back."""
+    origins: torch.Tensor
+    both: torch.Tensor
+    lags: torch.Tensor
+
+    def survival(self) -> torch.Tensor:
+        """sum_p both / sum_p origins: f64 [M, L], P(contact at t + lag | contact at t) pooled over the pairs; NaN where no
+        pair was ever in contact."""
+        return _nan_ratio(self.both.sum(1, dtype=torch.int64), self.origins.sum(1, dtype=torch.int64))
+
+    def per_pair(self) -> torch.Tensor:
+        """both / origins: f64 [M, P, L]; NaN for a pair that was never in contact at an origin."""
+        return _nan_ratio(self.both, self.origins)
+
+    def lifetime(self, dt: float = 1.0) -> torch.Tensor:
+        """The trapezoid sum of survival() over the given lags times `dt`: f64 [M], a contact lifetime (in steps for dt = 1)
+        up to the largest lag.  Fewer than two lags: 0."""
+        s = self.survival()
+        w = (self.lags[1:] - self.lags[:-1]).to(torch.float64) * float(dt)
+        return (0.5 * (s[:, 1:] + s[:, :-1]) * w).sum(1)
+
+    def total_variation(self, other: "ContactCorrelation") -> torch.Tensor:
+        """|survival() - other.survival()| per lag: f64 [M, L] (`other` with one member is broadcast).  Same lags."""
+        if not isinstance(other, ContactCorrelation) or not torch.equal(other.lags.cpu(), self.lags.cpu()):
+            raise MdnoError("total_variation: the two correlations must have the same lags")
+        return (self.survival() - other.survival()).abs()
+
+    def cpu(self) -> "ContactCorrelation":
+        return ContactCorrelation(self.origins.cpu(), self.both.cpu(), self.lags.cpu())
+
+    @staticmethod
+    def cat(parts: Sequence["ContactCorrelation"]) -> "ContactCorrelation":
+        """Correlations of disjoint member ranges of the same pairs and lags, members in order."""
+        return ContactCorrelation(torch.cat([q.origins for q in parts], 0), torch.cat([q.both for q in parts], 0), parts[0].lags)
+
+
+@dataclass
+class ContactSeries:
+    """The contact indicator of a pair list at every step (ops.contact_bits): `bits` int64 [M, P, ceil(S / 64)] holding the
+    words of the header's u64 (bit s % 64 of word s / 64 = pair p of member m in contact at step s), `per_frame` i32 [S, M]
+    the listed pairs in contact per frame, `n_steps` = S and the `pairs` they belong to."""
+    bits: torch.Tensor
+    per_frame: torch.Tensor
+    n_steps: int
+    pairs: ContactPairs
+
+    def fraction(self) -> torch.Tensor:
+        """per_frame / P: f64 [S, M], the fraction of the listed (native) contacts present — Q(t); NaN for an empty list."""
+        return _nan_ratio(self.per_frame, torch.full((), len(self.pairs), dtype=torch.float64, device=self.per_frame.device))
+
+    def series(self) -> torch.Tensor:
+        """The bits unpacked: bool [M, P, S]."""
+        k = torch.arange(64, dtype=torch.int64, device=self.bits.device)
+        M, P, Wd = self.bits.shape
+        return (((self.bits[..., None] >> k) & 1) != 0).reshape(M, P, Wd * 64)[..., :self.n_steps]
+
+    def correlation(self, lags=None) -> ContactCorrelation:
+        """origins and both per member, pair and lag (`lags`: integers in 0 .. S - 1, default `default_lags(S)`) from shifted
+        words, AND and population count on the device -> `ContactCorrelation`."""
+        if lags is None:
+            lags = default_lags(self.n_steps) if self.n_steps > 0 else []
+        vals = ops.check_contact_lags(lags, self.n_steps)
+        origins, both = ops.contact_correlation(self.bits, self.n_steps, vals)
+        return ContactCorrelation(origins, both, torch.tensor(vals, dtype=torch.int64, device=self.bits.device))
+
+    def cpu(self) -> "ContactSeries":
+        return ContactSeries(self.bits.cpu(), self.per_frame.cpu(), self.n_steps, self.pairs.to("cpu"))
+
+    @staticmethod
+    def cat(parts: Sequence["ContactSeries"]) -> "ContactSeries":
+        """Series of disjoint member ranges of the same steps and pairs, members in order."""
+        p = parts[0]
+        return ContactSeries(torch.cat([q.bits for q in parts], 0), torch.cat([q.per_frame for q in parts], 1), p.n_steps, p.pairs)
+
+
+def contact_series(frames: torch.Tensor, contact_pairs: ContactPairs, box=None) -> ContactSeries:
+    """frames f32 [S, M, N, 3] (device) and a `ContactPairs` -> `ContactSeries`: one bit per (member, pair, step) and the
+    number of listed pairs in contact per frame (include/mdno_contacts.h (b)).  `box`: distances by the minimum image, every
+    periodic axis >= 2 * contact_pairs.cut_max.  Asynchronous on the current stream, nothing is read back; CPU tensors and
+    bad arguments raise `MdnoError` before any device work."""
+    if not isinstance(contact_pairs, ContactPairs):
+        raise MdnoError(f"contact_series: contact_pairs is a {type(contact_pairs).__name__}")
+    if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise MdnoError("contact_series: frames must be [S, M, N, 3]")
+    contact_pairs.check_frames(int(frames.shape[-2]))
+    if not frames.is_cuda:
+        raise MdnoError("frames is a CPU tensor: the contact kernels run on the GPU only (no CPU fallback exists)")
+    if contact_pairs.pairs.device != frames.device:
+        contact_pairs = contact_pairs.to(frames.device)
+    S, M = int(frames.shape[0]), int(frames.shape[1])
+    if len(contact_pairs) == 0:        # (no pair, no cutoff to check a box against: nothing to launch)
+        ops.check_box(box, 0.0)
+        return ContactSeries(torch.zeros((M, 0, -(-S // 64)), dtype=torch.int64, device=frames.device),
+                             torch.zeros((S, M), dtype=torch.int32, device=frames.device), S, contact_pairs)
+    bits, per_frame = ops.contact_bits(frames, contact_pairs.pairs, contact_pairs.cut, contact_pairs.cut_max, box)
+    return ContactSeries(bits, per_frame, S, contact_pairs)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -2210,3 +2210,130 @@ def project_constraints(frames: torch.Tensor, pairs: torch.Tensor, lo: torch.Ten
                               ptr(sweeps) if F else None, ptr(viol_in) if F else None, ptr(viol_out) if F else None,
                               stream_ptr(dev)), "mdnocst_project")
     return out, sweeps, viol_in, viol_out
+
+
+# ------------------------------------------------------------------------------------------------
+# Contact statistics over time (include/mdno_contacts.h, csrc/contacts.hip)
+CM_TILE = _lib.CONTACTS_TILE        # MDNOCM_TILE: atoms per side of a pair tile
+CM_MAX_LAGS = _lib.CONTACTS_MAX_LAGS
+
+
+def check_contact_args(threshold, box=None, block_len=1, what: str = "pair_statistics"):
+    """(threshold as float, box as check_box returns it, block_len as int) or MdnoError: threshold finite and > 0, every
+    periodic axis of the box >= 2 * threshold, block_len an integer >= 1 (include/mdno_contacts.h).  Host only."""
+    import math
+    try:
+        cut = float(threshold)
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}: threshold={threshold!r}: expected a number") from None
+    if not (math.isfinite(cut) and cut > 0.0):
+        raise MdnoError(f"{what}: threshold {cut} is not a finite positive number")
+    if isinstance(block_len, bool) or not isinstance(block_len, int) or not 1 <= block_len < 2 ** 31:
+        raise MdnoError(f"{what}: block_len={block_len!r}: expected an integer >= 1")
+    return cut, check_box(box, cut), block_len
+
+
+def _contact_frames(frames, what: str):
+    frames = _device_frames(frames, "frames", (4,))
+    S, M, N = frames.shape[:3]
+    if max(S, M, N) >= 2 ** 31:
+        raise MdnoError(f"{what}: frames has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
+    return frames, S, M, N
+
+
+def pair_statistics(frames: torch.Tensor, threshold: float = 8.0, box=None, block_len: int = 64, moments: bool = True):
+    """frames f32 [S, M, N, 3] -> (count i32, sum_r f64, sum_r2 f64), each [Bk, M, N, N] with Bk = ceil(S / block_len): per
+    pair (both triangles and the diagonal) and block of `block_len` consecutive steps, the frames in which the pair is closer
+    than `threshold`, the sum of the distance and the sum of its square, each sum one sequential fp64 chain in step order
+    (include/mdno_contacts.h has the rule; mdnocm_pair_statistics).  `moments` False: only the counts (the two sums are
+    None, and the kernel takes no square root).  `box` = (Lx, Ly, Lz), 0 for an open axis: distances by the minimum image,
+    every periodic axis >= 2 * threshold.  Asynchronous on the current stream, nothing is read back."""
+    threshold, box, block_len = check_contact_args(threshold, box, block_len)
+    frames, S, M, N = _contact_frames(frames, "pair_statistics")
+    lib = _lib.load()
+    dev = frames.device
+    Bk = -(-S // block_len)
+    shape = (Bk, M, N, N)
+    count = torch.empty(shape, dtype=torch.int32, device=dev)
+    sum_r = torch.empty(shape, dtype=torch.float64, device=dev) if moments else None
+    sum_r2 = torch.empty(shape, dtype=torch.float64, device=dev) if moments else None
+    work = S * M * N > 0
+    check(lib.mdnocm_pair_statistics(ptr(frames) if work else None, S, M, N, threshold, box_arg(box) if box else None, block_len,
+                                     ptr(count) if work else None, ptr(sum_r) if work and moments else None,
+                                     ptr(sum_r2) if work and moments else None, stream_ptr(dev)), "mdnocm_pair_statistics")
+    return count, sum_r, sum_r2
+
+
+def contact_bits(frames: torch.Tensor, pairs: torch.Tensor, cut: torch.Tensor, cut_max: float, box=None):
+    """frames f32 [S, M, N, 3], pairs i32 [P, 2] and cut f64 [P] on the same device -> (bits u64-as-int64 [M, P, Wd],
+    per_frame i32 [S, M]), Wd = ceil(S / 64): bit s % 64 of word s / 64 says whether pair p of member m is closer than
+    min(cut[p], cut_max) at step s, and per_frame counts the listed pairs in contact per frame (include/mdno_contacts.h (b);
+    mdnocm_contact_bits).  torch has no unsigned 64-bit arithmetic: the words are handed back as int64 with the same bits.
+    An index outside 0 .. N - 1 is never in contact and reads nothing.  `box`: every periodic axis >= 2 * cut_max.
+    Asynchronous on the current stream, nothing is read back."""
+    cut_max, box, _ = check_contact_args(cut_max, box, 1, "contact_bits")
+    frames, S, M, N = _contact_frames(frames, "contact_bits")
+    dev = frames.device
+    pairs = _ic_indices(pairs, 2, "pairs", dev)
+    P = pairs.shape[0]
+    if not torch.is_tensor(cut) or cut.dtype != torch.float64 or tuple(cut.shape) != (P,) or cut.device != dev:
+        raise MdnoError(f"cut: expected float64 [{P}] on {dev}")
+    cut = cut.contiguous()
+    lib = _lib.load()
+    Wd = -(-S // 64)
+    bits = torch.empty((M, P, Wd), dtype=torch.int64, device=dev)
+    work = S * M * P > 0
+    per_frame = torch.empty((S, M), dtype=torch.int32, device=dev) if work else torch.zeros((S, M), dtype=torch.int32, device=dev)
+    check(lib.mdnocm_contact_bits(ptr(frames) if work and N else None, S, M, N, ptr(pairs) if work else None,
+                                  ptr(cut) if work else None, P, cut_max, box_arg(box) if box else None,
+                                  ptr(bits) if work else None, ptr(per_frame) if work else None, stream_ptr(dev)),
+          "mdnocm_contact_bits")
+    return bits, per_frame
+
+
+def check_contact_lags(lags, S: int, what: str = "contact_correlation"):
+    """`lags` as a list of Python ints: at most CM_MAX_LAGS integers in 0 .. S - 1, or MdnoError.  Host only."""
+    if torch.is_tensor(lags):
+        lags = lags.detach().cpu().reshape(-1).tolist()
+    try:
+        lags = list(lags)
+        vals = [int(v) for v in lags]
+        same = all(v == w for v, w in zip(vals, lags))
+    except (TypeError, ValueError):
+        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
+    if not same:
+        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
+    if len(vals) > CM_MAX_LAGS:
+        raise MdnoError(f"{what}: {len(vals)} lags, expected at most {CM_MAX_LAGS}")
+    for v in vals:
+        if not 0 <= v < S:
+            raise MdnoError(f"{what}: lag {v} is outside 0 .. {S - 1} (S={S})")
+    return vals
+
+
+def contact_correlation(bits: torch.Tensor, S: int, lags):
+    """bits int64 [M, P, ceil(S / 64)] (ops.contact_bits) and integer lags in 0 .. S - 1 -> (origins, both) i32 [M, P, L]:
+    for every member, pair and lag the steps t < S - lag at which the pair is in contact, and those at which it is in
+    contact at t and at t + lag (include/mdno_contacts.h (c); mdnocm_contact_correlation).  Integers, exact.  Asynchronous
+    on the current stream, nothing is read back."""
+    if not torch.is_tensor(bits):
+        raise MdnoError(f"bits must be a torch tensor, got {type(bits).__name__}")
+    if not bits.is_cuda:
+        raise MdnoError("bits is a CPU tensor: the contact kernels run on the GPU only (no CPU fallback exists)")
+    if isinstance(S, bool) or not isinstance(S, int) or not 0 <= S < 2 ** 31:
+        raise MdnoError(f"contact_correlation: S={S!r}: expected an integer >= 0")
+    if bits.dtype != torch.int64 or bits.dim() != 3 or bits.shape[2] != -(-S // 64):
+        raise MdnoError(f"bits is {bits.dtype} {tuple(bits.shape)}: expected int64 [M, P, {-(-S // 64)}] for S={S}")
+    vals = check_contact_lags(lags, S)
+    bits = bits.contiguous()
+    M, P, _ = bits.shape
+    L = len(vals)
+    lib = _lib.load()
+    dev = bits.device
+    work = S * M * P * L > 0
+    origins = torch.empty((M, P, L), dtype=torch.int32, device=dev)
+    both = torch.empty((M, P, L), dtype=torch.int32, device=dev)
+    check(lib.mdnocm_contact_correlation(ptr(bits) if work else None, S, M, P, _lag_arg(vals) if L else None, L,
+                                         ptr(origins) if work else None, ptr(both) if work else None, stream_ptr(dev)),
+          "mdnocm_contact_correlation")
+    return origins, both

@@ -575,6 +575,23 @@ class RolloutEngine:
         from .forecast import internal_coordinates
         return internal_coordinates(self._observed(first_step, steps), featurizer, box=self.box, radians=radians, dtype=dtype)
 
+    def pair_statistics(self, threshold: Optional[float] = None, block_len: int = 64, moments: bool = True, first_step: int = 0,
+                        steps: Optional[int] = None):
+        """`forecast.pair_statistics` (per pair and block of `block_len` steps: frames in contact, sums of the distance and of
+        its square) of the produced frames of steps first_step .. first_step + steps - 1 (default: all) in the engine's own
+        box, at the engine's own threshold by default -> `forecast.PairStatistics`; the frames are read where they are, on
+        the current stream after the engine's enqueued steps (as `score`)."""
+        from .forecast import pair_statistics
+        threshold = self.threshold if threshold is None else threshold
+        ops.check_contact_args(threshold, self.box, block_len)
+        return pair_statistics(self._observed(first_step, steps), threshold, box=self.box, block_len=block_len, moments=moments)
+
+    def contact_series(self, contact_pairs, first_step: int = 0, steps: Optional[int] = None):
+        """`forecast.contact_series` (one bit per member, listed pair and step, and the listed pairs in contact per frame:
+        Q(t)) of the produced frames (same range arguments as `score`) in the engine's own box -> `forecast.ContactSeries`."""
+        from .forecast import contact_series
+        return contact_series(self._observed(first_step, steps), contact_pairs, box=self.box)
+
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):
         """`forecast.covariance` of the produced frames (same range arguments as `score`) after their superposition onto
@@ -797,6 +814,19 @@ class GroupedRolloutEngine:
         row depends on that frame alone, so these are the bits of
         `forecast.internal_coordinates(self.produced(first_step, steps), featurizer, box=self.box)`."""
         return torch.cat([e.internal_coordinates(featurizer, radians, dtype, first_step, steps) for e in self.engines], dim=1)
+
+    def pair_statistics(self, threshold: Optional[float] = None, block_len: int = 64, moments: bool = True, first_step: int = 0,
+                        steps: Optional[int] = None):
+        """`RolloutEngine.pair_statistics` for every group on its own frames, joined along the member axis: a member's maps
+        depend on its own frames alone, so these are the bits of the ungrouped engine."""
+        from .forecast import PairStatistics
+        return PairStatistics.cat([e.pair_statistics(threshold, block_len, moments, first_step, steps) for e in self.engines])
+
+    def contact_series(self, contact_pairs, first_step: int = 0, steps: Optional[int] = None):
+        """`RolloutEngine.contact_series` for every group on its own frames, joined along the member axis (integers: the
+        ungrouped engine's)."""
+        from .forecast import ContactSeries
+        return ContactSeries.cat([e.contact_series(contact_pairs, first_step, steps) for e in self.engines])
 
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):

@@ -33,10 +33,15 @@ Cartesian coordinates (INTEGRATION.md "Features that do not depend on a referenc
 step (include/mdno_constrain.h), and "constrained" holds, as [free run, constrained run], the diverged members, the RMSD,
 native-fraction and Jaccard series and the share of bond lengths outside the truth's range, with the mean violation before and
 after the projection and the mean sweep count per step (INTEGRATION.md "Keeping a rollout on the chain manifold" reads them).
+With `--contacts [MIN_SEP]` also the contact statistics over the run (forecast.PairStatistics, ContactSeries, ContactCorrelation;
+pairs at least MIN_SEP apart in sequence, default 3): per member the mean |dP| between its contact-probability map and the
+truth's, the share of the native contacts (truth P >= 0.5) it keeps at P >= 0.5 and the share of its own P >= 0.5 contacts that
+are not native, the mean Q over the run beside the truth's own, and the contact survival at a few lags beside the truth's
+(INTEGRATION.md "Contact maps over time" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
-                                    [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4] [--constrain 0.1]
+                                    [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4] [--constrain 0.1] [--contacts 3]
 """
 import argparse
 import json
@@ -89,7 +94,14 @@ def main() -> None:
                     help="run the free run a second time with distance constraints on the pseudo-bonds, each held inside the "
                          "truth's own range widened by MARGIN (default 0), and print the scores of both runs side by side")
     ap.add_argument("--constrain-iterations", type=int, default=8, help="with --constrain: sweeps per step at most")
+    ap.add_argument("--contacts", type=int, nargs="?", const=3, metavar="MIN_SEP", default=None,
+                    help="also the contact statistics over the run: per member the error of its contact-probability map against "
+                         "the truth's over pairs at least MIN_SEP apart (default 3), the share of native contacts it keeps and "
+                         "of its own contacts that are not native, the mean Q beside the truth's and the contact survival at a "
+                         "few lags beside the truth's")
     a = ap.parse_args()
+    if a.contacts is not None and a.contacts < 0:
+        ap.error("--contacts takes a MIN_SEP >= 0")
     if a.constrain is not None and not (a.constrain >= 0.0 and a.constrain_iterations >= 0):
         ap.error("--constrain takes a MARGIN >= 0 and --constrain-iterations a number >= 0")
     if a.internal is not None and (len(a.internal) not in (0, 2) or any(v < 1 for v in a.internal)):
@@ -193,6 +205,26 @@ def main() -> None:
         dist.update({"coverage_radius": a.coverage, "coverage_precision": finite(cr.precision(a.coverage).cpu()),
                      "coverage": finite(cr.coverage(a.coverage).cpu()),
                      "nearest_true_frame_rmsd_median": finite(cr.nearest.nanmedian(0).values.cpu())})
+
+    if a.contacts is not None and S > 0:
+        from molecular_dynamics_neural_operator_amd import forecast as fc
+        run = eng.pair_statistics(moments=False).total()                             # count i32 [M, N, N] over the run
+        tru = fc.pair_statistics(truth[:, None], a.threshold, box=eng.box, moments=False).total()
+        far = (torch.arange(N, device=dev)[:, None] - torch.arange(N, device=dev)[None, :]).abs() >= a.contacts
+        native_map = (tru.probability() >= 0.5) & far                                # [1, N, N]
+        own_map = (run.probability() >= 0.5) & far                                   # [M, N, N]
+        kept = fc._nan_ratio((own_map & native_map).sum((1, 2)), native_map.sum((1, 2)).expand(M))
+        spurious = fc._nan_ratio((own_map & ~native_map).sum((1, 2)), own_map.sum((1, 2)))
+        native = fc.ContactPairs.from_statistics(tru, 0.5, a.contacts)              # the one read-back
+        q_run, q_truth = eng.contact_series(native), fc.contact_series(truth[:, None], native, box=eng.box)
+        some = [l for l in (0, 1, 2, 5, 10, 20, 50, 100, 200, 500) if l < S]
+        s_run, s_truth = q_run.correlation(some).survival(), q_truth.correlation(some).survival()
+        dist.update({"contacts_min_separation": a.contacts, "contacts_native_pairs": len(native),
+                     "contact_map_error": finite(run.map_error(tru, a.contacts).cpu()),
+                     "native_contacts_kept": finite(kept.cpu()), "contacts_not_native": finite(spurious.cpu()),
+                     "q_mean": finite(q_run.fraction().mean(0).cpu()), "q_mean_truth": finite(q_truth.fraction().mean(0).cpu())[0],
+                     "contact_survival_lags": some, "contact_survival_mean": finite(s_run.nanmean(0).cpu()),
+                     "contact_survival_truth": finite(s_truth[0].cpu())})
 
     internal = None
     if a.internal is not None and S > 0:

@@ -18,7 +18,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib, ops
+from . import _lib, forecast, ops
 from ._lib import MdnoError, STATUS_EDGE_OVERFLOW, check, f32, ptr, raise_on_status, require_gpu
 
 
@@ -73,7 +73,154 @@ def probe_edges(last: torch.Tensor, M: int, N: int, threshold: float, box) -> Tu
     return int(g.num_edges.item()), bool(int(g.status.item()) & STATUS_EDGE_OVERFLOW)
 
 
-class RolloutEngine:
+def _join_members(parts, join):
+    """Results of disjoint member ranges of the same steps, members in order, as one.  `join` is the result's own rule: a
+    record's `cat`; for a plain tensor the member axis to `torch.cat` along; for a tuple of tensors one axis per element
+    (None: the element is the same for every range, taken from the first).  One range is its own result: nothing is copied
+    and nothing launched."""
+    if len(parts) == 1:
+        return parts[0]
+    if callable(join):
+        return join(parts)
+    if isinstance(join, int):
+        return torch.cat(parts, join)
+    return tuple(parts[0][i] if dim is None else torch.cat([p[i] for p in parts], dim) for i, dim in enumerate(join))
+
+
+class _ProducedFrames:
+    """What both engines offer on the frames they have produced: `run`, and the analyses of `forecast` / `ops` on the frames
+    of steps first_step .. first_step + steps - 1 (default: all produced).  Each is defined here once, against `self.box`,
+    `self.threshold`, `self.M` and one primitive an engine implements, `_member_views`, by a method that names its function
+    and one of two rules:
+
+    * per member (`_per_member`): the function runs on each part's frames and the results are joined along the member
+      axis.  A member's result depends on its own frames alone, so a grouped engine gives the bits of one engine holding
+      every member, and an engine of one part returns that part's result as it is.
+    * pooled over the members (`_pooled`): the parts' frames are concatenated along the member axis (one copy; one part is
+      taken as it is) and the function is called once.
+
+    The frames are read where they lie — views of the trajectory buffers, never written — on the current stream after the
+    engine's enqueued steps, without waiting on the host.  Arguments are refused on the host (`MdnoError`), in the engine's
+    own box, before anything is enqueued."""
+
+    _OWN_BOX = object()
+
+    def run(self, window: torch.Tensor, x_aminoacid: torch.Tensor, steps: int) -> torch.Tensor:
+        """reset + step + synchronize; returns the produced frames f32 [steps, M, N, 3] (`frames()`)."""
+        self.reset(window, x_aminoacid)
+        self.step(steps)
+        self.synchronize()
+        return self.frames()
+
+    def _member_views(self, first_step: int, steps: Optional[int]) -> List[Tuple[int, int, torch.Tensor]]:
+        """[(lo, hi, frames of members lo .. hi - 1: f32 [steps, hi - lo, N, 3]), ..] covering 0 .. M in member order, each a
+        view handed out after the range was validated and the current stream made to wait for the stream that produces it."""
+        raise NotImplementedError
+
+    def _per_member(self, fn, join, first_step: int, steps: Optional[int]):
+        return _join_members([fn(x) for _, _, x in self._member_views(first_step, steps)], join)
+
+    def _pooled(self, first_step: int, steps: Optional[int]) -> torch.Tensor:
+        return _join_members([x for _, _, x in self._member_views(first_step, steps)], 1)
+
+    def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
+              threshold: Optional[float] = None, box=_OWN_BOX):
+        """Per member: `forecast.score_forecast` against truth f32 [steps, N, 3] (every member against the same frames) or
+        [steps, M, N, 3] (each part against its own members' slice) -> `forecast.ForecastScore`.  `threshold`: the contact
+        cutoff, the engine's own by default.  `box`: the periodic cell the contacts are counted in, the engine's own by
+        default (None: open)."""
+        per_member = torch.is_tensor(truth) and truth.dim() == 4
+        if per_member and truth.shape[1] != self.M:
+            raise MdnoError(f"truth shape {tuple(truth.shape)}: expected {self.M} members")
+        threshold = self.threshold if threshold is None else threshold
+        box = self.box if box is _ProducedFrames._OWN_BOX else ops.check_box(box, threshold)
+        views = self._member_views(first_step, steps)
+        whole = len(views) == 1 or not per_member
+        return _join_members([forecast.score_forecast(x, truth if whole else truth[:, lo:hi].contiguous(), threshold, box=box)
+                              for lo, hi, x in views], forecast.ForecastScore.cat)
+
+    def pair_histogram(self, r_max: float, n_bins: int = 200, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.pair_histogram` in the engine's own box -> `forecast.PairHistogram`, counts i64
+        [steps, M, n_bins]."""
+        ops.check_histogram_args(r_max, n_bins, self.box)
+        return self._per_member(lambda x: forecast.pair_histogram(x, r_max, n_bins, box=self.box),
+                                forecast.PairHistogram.cat, first_step, steps)
+
+    def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
+        """Per member: `ops.radius_of_gyration` -> f64 [steps, M]."""
+        return self._per_member(ops.radius_of_gyration, 1, first_step, steps)
+
+    def displacement_stats(self, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None, n_bins: int = 0,
+                           first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.displacement_stats` (MSD, non-Gaussian parameter, self van Hove histogram per member and
+        lag) -> `forecast.DisplacementStats`."""
+        return self._per_member(lambda x: forecast.displacement_stats(x, lags, origin_stride, remove_com, r_max, n_bins),
+                                forecast.DisplacementStats.cat, first_step, steps)
+
+    def velocity_autocorrelation(self, lags=None, origin_stride: int = 1, remove_com: bool = False,
+                                 normalized: bool = False, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.velocity_autocorrelation` -> (C f64 [M, L], lags i64 [L]; the lags are every part's)."""
+        return self._per_member(lambda x: forecast.velocity_autocorrelation(x, lags, origin_stride, remove_com, normalized),
+                                (0, None), first_step, steps)
+
+    def ensemble_score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """Pooled: `forecast.ensemble_score` (error of the ensemble mean, spread, CRPS sums and rank histogram per step) of
+        ALL the engine's M members taken as ONE ensemble, against truth f32 [steps, N, 3] -> `forecast.EnsembleScore`.
+        Unlike the per-member statistics this cannot be merged from per-group results — the pair term
+        sum_{m<k} |x_m - x_k| and the ranks run across the groups — so it is the bits of
+        `forecast.ensemble_score(self.produced(first_step, steps), truth)`."""
+        return forecast.ensemble_score(self._pooled(first_step, steps), truth)
+
+    def cross_rmsd(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None, matrix: bool = True):
+        """Per member: `forecast.cross_rmsd` against reference f32 [Fb, N, 3] (superposed RMSD of every produced frame
+        against every reference frame, the nearest reference frame per frame and the nearest produced frame per member and
+        reference frame) -> `forecast.CrossRmsd`.  Rows and per-member columns never cross members and an element's bits
+        depend on its two frames alone."""
+        return self._per_member(lambda x: forecast.cross_rmsd(x, reference, matrix), forecast.CrossRmsd.cat, first_step, steps)
+
+    def superpose(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.superpose` onto reference f32 [N, 3] -> (aligned f32 [steps, M, N, 3], rmsd f64 [steps, M]);
+        a frame's outputs depend on that frame and the reference alone."""
+        return self._per_member(lambda x: forecast.superpose(x, reference), (1, 1), first_step, steps)
+
+    def assign(self, discretization, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.Discretization.assign` -> `forecast.Assignment`, labels i32 and dist2 f64 [steps, M]: the
+        state of every frame in a partition built from the truth (`forecast.discretize`)."""
+        return self._per_member(discretization.assign, forecast.Assignment.cat, first_step, steps)
+
+    def internal_coordinates(self, featurizer, radians: bool = False, dtype=torch.float32, first_step: int = 0,
+                             steps: Optional[int] = None) -> torch.Tensor:
+        """Per member: `forecast.internal_coordinates` in the engine's own box -> features [steps, M, D]: distances, angle
+        cosines and dihedral (cos, sin) that do not depend on a reference frame."""
+        return self._per_member(lambda x: forecast.internal_coordinates(x, featurizer, box=self.box, radians=radians, dtype=dtype),
+                                1, first_step, steps)
+
+    def pair_statistics(self, threshold: Optional[float] = None, block_len: int = 64, moments: bool = True, first_step: int = 0,
+                        steps: Optional[int] = None):
+        """Per member: `forecast.pair_statistics` (per pair and block of `block_len` steps: frames in contact, sums of the
+        distance and of its square) in the engine's own box, at the engine's own threshold by default ->
+        `forecast.PairStatistics`."""
+        threshold = self.threshold if threshold is None else threshold
+        ops.check_contact_args(threshold, self.box, block_len)
+        return self._per_member(lambda x: forecast.pair_statistics(x, threshold, box=self.box, block_len=block_len, moments=moments),
+                                forecast.PairStatistics.cat, first_step, steps)
+
+    def contact_series(self, contact_pairs, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.contact_series` (one bit per member, listed pair and step, and the listed pairs in contact
+        per frame: Q(t)) in the engine's own box -> `forecast.ContactSeries`."""
+        return self._per_member(lambda x: forecast.contact_series(x, contact_pairs, box=self.box),
+                                forecast.ContactSeries.cat, first_step, steps)
+
+    def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
+                   steps: Optional[int] = None):
+        """Pooled: `forecast.covariance` over the 3 N coordinates after the superposition onto reference f32 [N, 3] ->
+        `forecast.Covariance`.  The sums run across the members, so `superpose` runs per member, its aligned frames are
+        joined and ONE covariance call follows: the bits of
+        `forecast.covariance(forecast.superpose(self.produced(first_step, steps), reference)[0], mean, lag)`."""
+        return forecast.covariance(self.superpose(reference, first_step, steps)[0], mean, lag)
+
+
+class RolloutEngine(_ProducedFrames):
     """Owns the trajectory buffer [W+max_steps, M, N, 3], the workspace and the captured step.
 
     noise_sigma > 0: a stochastic rollout (include/mdno_noise.h mdno_rollout_plan_set_noise) —
@@ -465,13 +612,6 @@ class RolloutEngine:
             raise MdnoError(f"radius graph exceeded edge_cap={self.edge_cap}; construct the engine with a larger cap")
         raise_on_status(st, "rollout")
 
-    def run(self, window: torch.Tensor, x_aminoacid: torch.Tensor, steps: int) -> torch.Tensor:
-        """reset + step + synchronize; returns the produced frames f32 [steps, M, N, 3] (a view)."""
-        self.reset(window, x_aminoacid)
-        self.step(steps)
-        self.synchronize()
-        return self.frames()
-
     def frames(self) -> torch.Tensor:
         return self.traj[self.W:self.W + self.steps_done]
 
@@ -487,118 +627,10 @@ class RolloutEngine:
                             f"{self.steps_done} produced")
         return first_step, steps
 
-    _OWN_BOX = object()
-
-    def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
-              threshold: Optional[float] = None, box=_OWN_BOX):
-        """Score the produced frames of steps first_step .. first_step + steps - 1 (default: all) against
-        truth f32 [steps, N, 3] (every member against the same frames) or [steps, M, N, 3] -> `forecast.ForecastScore`.
-        The frames are read where they are (a view of the trajectory buffer, untouched); the scoring kernels run on
-        the current stream after the engine's enqueued steps, without waiting on the host.  `threshold`: the contact
-        cutoff, the engine's own by default.  `box`: the periodic cell the contacts are counted in, the engine's own by
-        default (None: open)."""
-        from .forecast import score_forecast
-        first_step, steps = self._score_range(first_step, steps)
-        threshold = self.threshold if threshold is None else threshold
-        box = self.box if box is RolloutEngine._OWN_BOX else ops.check_box(box, threshold)
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        return score_forecast(self.produced(first_step, steps), truth, threshold, box=box)
-
-    def _observed(self, first_step: int, steps: Optional[int]) -> torch.Tensor:
+    def _member_views(self, first_step: int, steps: Optional[int]):
         first_step, steps = self._score_range(first_step, steps)
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        return self.produced(first_step, steps)
-
-    def pair_histogram(self, r_max: float, n_bins: int = 200, first_step: int = 0, steps: Optional[int] = None):
-        """Pair-distance histograms of the produced frames of steps first_step .. first_step + steps - 1 (default: all)
-        in the engine's own box -> `forecast.PairHistogram`, counts i64 [steps, M, n_bins]; the frames are read where
-        they are, on the current stream after the engine's enqueued steps (as `score`)."""
-        from .forecast import pair_histogram
-        ops.check_histogram_args(r_max, n_bins, self.box)
-        return pair_histogram(self._observed(first_step, steps), r_max, n_bins, box=self.box)
-
-    def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
-        """Radius of gyration of the produced frames (same range arguments as `score`): f64 [steps, M]."""
-        return ops.radius_of_gyration(self._observed(first_step, steps))
-
-    def displacement_stats(self, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None, n_bins: int = 0,
-                           first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.displacement_stats` (MSD, non-Gaussian parameter, self van Hove histogram per member and lag) of the
-        produced frames of steps first_step .. first_step + steps - 1 (default: all), read where they are on the current
-        stream after the engine's enqueued steps (as `score`)."""
-        from .forecast import displacement_stats
-        return displacement_stats(self._observed(first_step, steps), lags, origin_stride, remove_com, r_max, n_bins)
-
-    def velocity_autocorrelation(self, lags=None, origin_stride: int = 1, remove_com: bool = False,
-                                 normalized: bool = False, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.velocity_autocorrelation` of the produced frames (same range arguments as `score`):
-        (C f64 [M, L], lags i64 [L])."""
-        from .forecast import velocity_autocorrelation
-        return velocity_autocorrelation(self._observed(first_step, steps), lags, origin_stride, remove_com, normalized)
-
-    def ensemble_score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.ensemble_score` (error of the ensemble mean, spread, CRPS sums and rank histogram per step) of the
-        produced frames of steps first_step .. first_step + steps - 1 (default: all), taken as ONE ensemble of the engine's
-        M members, against truth f32 [steps, N, 3]; the frames are read where they are, on the current stream after the
-        engine's enqueued steps (as `score`)."""
-        from .forecast import ensemble_score
-        return ensemble_score(self._observed(first_step, steps), truth)
-
-    def cross_rmsd(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None, matrix: bool = True):
-        """`forecast.cross_rmsd` (superposed RMSD of every produced frame against every reference frame, the nearest
-        reference frame per frame and the nearest produced frame per member and reference frame) of the produced frames of
-        steps first_step .. first_step + steps - 1 (default: all) against reference f32 [Fb, N, 3]; the frames are read where
-        they are, on the current stream after the engine's enqueued steps (as `score`)."""
-        from .forecast import cross_rmsd
-        return cross_rmsd(self._observed(first_step, steps), reference, matrix)
-
-    def superpose(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.superpose` of the produced frames of steps first_step .. first_step + steps - 1 (default: all) onto
-        reference f32 [N, 3] -> (aligned f32 [steps, M, N, 3], rmsd f64 [steps, M]); the frames are read where they are, on
-        the current stream after the engine's enqueued steps (as `score`)."""
-        from .forecast import superpose
-        return superpose(self._observed(first_step, steps), reference)
-
-    def assign(self, discretization, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.Discretization.assign` of the produced frames of steps first_step .. first_step + steps - 1 (default:
-        all) -> `forecast.Assignment`, labels i32 and dist2 f64 [steps, M]: the state of every frame in a partition built
-        from the truth (`forecast.discretize`); the frames are read where they are, on the current stream after the
-        engine's enqueued steps (as `score`)."""
-        return discretization.assign(self._observed(first_step, steps))
-
-    def internal_coordinates(self, featurizer, radians: bool = False, dtype=torch.float32, first_step: int = 0,
-                             steps: Optional[int] = None) -> torch.Tensor:
-        """`forecast.internal_coordinates` of the produced frames of steps first_step .. first_step + steps - 1 (default:
-        all) in the engine's own box -> features [steps, M, D]: distances, angle cosines and dihedral (cos, sin) that do not
-        depend on a reference frame; the frames are read where they are, on the current stream after the engine's enqueued
-        steps (as `score`)."""
-        from .forecast import internal_coordinates
-        return internal_coordinates(self._observed(first_step, steps), featurizer, box=self.box, radians=radians, dtype=dtype)
-
-    def pair_statistics(self, threshold: Optional[float] = None, block_len: int = 64, moments: bool = True, first_step: int = 0,
-                        steps: Optional[int] = None):
-        """`forecast.pair_statistics` (per pair and block of `block_len` steps: frames in contact, sums of the distance and of
-        its square) of the produced frames of steps first_step .. first_step + steps - 1 (default: all) in the engine's own
-        box, at the engine's own threshold by default -> `forecast.PairStatistics`; the frames are read where they are, on
-        the current stream after the engine's enqueued steps (as `score`)."""
-        from .forecast import pair_statistics
-        threshold = self.threshold if threshold is None else threshold
-        ops.check_contact_args(threshold, self.box, block_len)
-        return pair_statistics(self._observed(first_step, steps), threshold, box=self.box, block_len=block_len, moments=moments)
-
-    def contact_series(self, contact_pairs, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.contact_series` (one bit per member, listed pair and step, and the listed pairs in contact per frame:
-        Q(t)) of the produced frames (same range arguments as `score`) in the engine's own box -> `forecast.ContactSeries`."""
-        from .forecast import contact_series
-        return contact_series(self._observed(first_step, steps), contact_pairs, box=self.box)
-
-    def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
-                   steps: Optional[int] = None):
-        """`forecast.covariance` of the produced frames (same range arguments as `score`) after their superposition onto
-        reference f32 [N, 3], pooled over the members -> `forecast.Covariance` over the 3 N coordinates: the bits of
-        `forecast.covariance(forecast.superpose(self.produced(...), reference)[0], mean, lag)`."""
-        from .forecast import covariance
-        return covariance(self.superpose(reference, first_step, steps)[0], mean, lag)
+        return [(0, self.M, self.produced(first_step, steps))]
 
     def close(self) -> None:
         if self.plan:
@@ -613,7 +645,7 @@ class RolloutEngine:
             pass
 
 
-class GroupedRolloutEngine:
+class GroupedRolloutEngine(_ProducedFrames):
     """The members of a shard as `groups` independent `RolloutEngine`s (contiguous member ranges), each with its own
     stream and its own captured step, stepped together.  Members never interact and conv_mode "auto" is resolved ONCE,
     on the graph of the whole shard, and given to every group (a group deciding on its own members could take the other
@@ -625,7 +657,8 @@ class GroupedRolloutEngine:
     may run different formulations — `conv_mode` then reads "mixed:..", every group's `mode_changes` says where — and
     the one-engine equivalence holds to fp32 reassociation only.  What changes is the schedule: one group's edge-MLP (matrix-pipe-bound) and launch tails run
     beside another group's convs (fabric-bound) — 5 % at 8 x 504 atoms, 3 % at 64 (EXPERIMENTS.md section 0.2b).  Same
-    reset / step / synchronize / run / frames interface; `traj` and `edges_per_step` are assembled on access."""
+    reset / step / synchronize / run / frames interface and the same analyses of the produced frames (`_ProducedFrames`: one
+    part per group); `traj` and `edges_per_step` are assembled on access."""
 
     def __init__(self, model, members: int, n_atoms: int, window: int, threshold: float = 8.0, max_steps: int = 1000,
                  edge_cap: Optional[int] = None, device=None, use_graph: bool = True, groups: int = 2,
@@ -633,6 +666,7 @@ class GroupedRolloutEngine:
                  constraint_iterations: int = 8, constraint_tol: float = 0.0):
         self.box = check_rollout_box(model, box, threshold)      # one box for every group
         self.M, self.N, self.W = int(members), int(n_atoms), int(window)
+        self.threshold = float(threshold)
         ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
         if len(ids) != self.M:
             raise MdnoError(f"member_ids: expected {self.M} ids, got {len(ids)}")
@@ -682,7 +716,7 @@ class GroupedRolloutEngine:
         want = None
         if any(e._auto for e in self.engines):      # the rule one engine holding every member would apply
             e0 = self.engines[0]
-            n_e, over = probe_edges(f32(window[self.W - 1].to(self.device)), self.M, self.N, e0.threshold, self.box)
+            n_e, over = probe_edges(f32(window[self.W - 1].to(self.device)), self.M, self.N, self.threshold, self.box)
             if over:
                 n_e = max(n_e, self.M * max(AUTO_FACTORED_MIN_DEGREE * self.N, AUTO_FACTORED_MIN_EDGES))
             want = {v: k for k, v in _lib.CONV_MODES.items()}[
@@ -727,12 +761,6 @@ class GroupedRolloutEngine:
         for e in self.engines:
             e.synchronize()
 
-    def run(self, window: torch.Tensor, x_aminoacid: torch.Tensor, steps: int) -> torch.Tensor:
-        self.reset(window, x_aminoacid)
-        self.step(steps)
-        self.synchronize()
-        return self.frames()
-
     @property
     def traj(self) -> torch.Tensor:
         return torch.cat([e.traj for e in self.engines], dim=1)
@@ -745,97 +773,8 @@ class GroupedRolloutEngine:
         these frames are copied — `traj` concatenates the groups' whole buffers)."""
         return torch.cat([e.produced(first_step, steps) for e in self.engines], dim=1)
 
-    def score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None,
-              threshold: Optional[float] = None, box=RolloutEngine._OWN_BOX):
-        """`RolloutEngine.score` for every group on its own frames, members in order: the bits of
-        `score_forecast(self.frames(), truth)` without assembling the trajectory (`box`: the engines' own by default)."""
-        from .forecast import ForecastScore
-        if torch.is_tensor(truth) and truth.dim() == 4 and truth.shape[1] != self.M:
-            raise MdnoError(f"truth shape {tuple(truth.shape)}: expected {self.M} members")
-        per_member = torch.is_tensor(truth) and truth.dim() == 4
-        return ForecastScore.cat([e.score(truth[:, lo:hi].contiguous() if per_member else truth, first_step, steps, threshold, box)
-                                  for e, (lo, hi) in zip(self.engines, self.bounds)])
-
-    def pair_histogram(self, r_max: float, n_bins: int = 200, first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.pair_histogram` for every group on its own frames, members in order."""
-        from .forecast import PairHistogram
-        return PairHistogram.cat([e.pair_histogram(r_max, n_bins, first_step, steps) for e in self.engines])
-
-    def radius_of_gyration(self, first_step: int = 0, steps: Optional[int] = None) -> torch.Tensor:
-        """`RolloutEngine.radius_of_gyration` for every group, members in order: f64 [steps, M]."""
-        return torch.cat([e.radius_of_gyration(first_step, steps) for e in self.engines], dim=1)
-
-    def displacement_stats(self, lags=None, origin_stride: int = 1, remove_com: bool = False, r_max=None, n_bins: int = 0,
-                           first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.displacement_stats` for every group on its own frames, members in order."""
-        from .forecast import DisplacementStats
-        return DisplacementStats.cat([e.displacement_stats(lags, origin_stride, remove_com, r_max, n_bins, first_step, steps)
-                                      for e in self.engines])
-
-    def velocity_autocorrelation(self, lags=None, origin_stride: int = 1, remove_com: bool = False,
-                                 normalized: bool = False, first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.velocity_autocorrelation` for every group, members in order: (C f64 [M, L], lags)."""
-        parts = [e.velocity_autocorrelation(lags, origin_stride, remove_com, normalized, first_step, steps)
-                 for e in self.engines]
-        return torch.cat([c for c, _ in parts], dim=0), parts[0][1]
-
-    def ensemble_score(self, truth: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
-        """`forecast.ensemble_score` of ALL groups' members as one ensemble.  Unlike the per-member statistics above this
-        cannot be merged from per-group results — the pair term sum_{m<k} |x_m - x_k| and the ranks run across the
-        groups — so the groups' frames of the asked steps are concatenated along the member axis (one copy) and scored
-        once: the bits of `forecast.ensemble_score(self.produced(first_step, steps), truth)`."""
-        from .forecast import ensemble_score
-        return ensemble_score(torch.cat([e._observed(first_step, steps) for e in self.engines], dim=1), truth)
-
-    def cross_rmsd(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None, matrix: bool = True):
-        """`forecast.cross_rmsd` per group, joined along the member axis: a row and a per-member column never cross members
-        and an element's bits depend on its two frames alone, so unlike `ensemble_score` no copy of the frames is needed
-        and the result is that of all members scored at once."""
-        from .forecast import CrossRmsd
-        return CrossRmsd.cat([e.cross_rmsd(reference, first_step, steps, matrix) for e in self.engines])
-
-    def superpose(self, reference: torch.Tensor, first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.superpose` for every group on its own frames, joined along the member axis: a frame's outputs
-        depend on that frame and the reference alone, so these are the bits of
-        `forecast.superpose(self.produced(first_step, steps), reference)`."""
-        parts = [e.superpose(reference, first_step, steps) for e in self.engines]
-        return torch.cat([a for a, _ in parts], dim=1), torch.cat([r for _, r in parts], dim=1)
-
-    def assign(self, discretization, first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.assign` for every group on its own frames, joined along the member axis: a frame's label depends
-        on that frame and the discretization alone, so these are the bits of
-        `discretization.assign(self.produced(first_step, steps))` whatever the grouping."""
-        from .forecast import Assignment
-        return Assignment.cat([e.assign(discretization, first_step, steps) for e in self.engines])
-
-    def internal_coordinates(self, featurizer, radians: bool = False, dtype=torch.float32, first_step: int = 0,
-                             steps: Optional[int] = None) -> torch.Tensor:
-        """`RolloutEngine.internal_coordinates` for every group on its own frames, joined along the member axis: a frame's
-        row depends on that frame alone, so these are the bits of
-        `forecast.internal_coordinates(self.produced(first_step, steps), featurizer, box=self.box)`."""
-        return torch.cat([e.internal_coordinates(featurizer, radians, dtype, first_step, steps) for e in self.engines], dim=1)
-
-    def pair_statistics(self, threshold: Optional[float] = None, block_len: int = 64, moments: bool = True, first_step: int = 0,
-                        steps: Optional[int] = None):
-        """`RolloutEngine.pair_statistics` for every group on its own frames, joined along the member axis: a member's maps
-        depend on its own frames alone, so these are the bits of the ungrouped engine."""
-        from .forecast import PairStatistics
-        return PairStatistics.cat([e.pair_statistics(threshold, block_len, moments, first_step, steps) for e in self.engines])
-
-    def contact_series(self, contact_pairs, first_step: int = 0, steps: Optional[int] = None):
-        """`RolloutEngine.contact_series` for every group on its own frames, joined along the member axis (integers: the
-        ungrouped engine's)."""
-        from .forecast import ContactSeries
-        return ContactSeries.cat([e.contact_series(contact_pairs, first_step, steps) for e in self.engines])
-
-    def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
-                   steps: Optional[int] = None):
-        """`forecast.covariance` of ALL groups' members pooled: the covariance sums run across the members, so each group
-        is superposed on its own, the aligned frames are concatenated along the member axis and ONE covariance call
-        follows: the bits of `forecast.covariance(forecast.superpose(self.produced(first_step, steps), reference)[0], mean,
-        lag)`."""
-        from .forecast import covariance
-        return covariance(self.superpose(reference, first_step, steps)[0], mean, lag)
+    def _member_views(self, first_step: int, steps: Optional[int]):
+        return [(lo, hi, x) for e, (lo, hi) in zip(self.engines, self.bounds) for _, _, x in e._member_views(first_step, steps)]
 
     @property
     def edges_per_step(self) -> torch.Tensor:

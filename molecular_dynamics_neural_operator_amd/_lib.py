@@ -166,11 +166,19 @@ TRAIN_SIGNATURES = {
 # include/mdno_noise.h: seeded Gaussian noise on the device
 _U64 = C.c_uint64
 _F = C.c_float
-NOISE_PURPOSES = {"rollout": 0, "train_window": 1}
+NOISE_PURPOSES = {"rollout": 0, "train_window": 1, "train_motion": 2}
 NOISE_SIGNATURES = {
     "mdno_noise_fill": (_I, [_U64, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P]),
     "mdno_noise_add_window": (_I, [_U64, _P, _P, _I, _I, _L, _I, _L, _F, _P, _P, _P]),
     "mdno_rollout_plan_set_noise": (_I, [_P, _F, _U64, _P]),
+}
+
+# include/mdno_augment.h: random rigid motions of training samples (the generator's third purpose, "train_motion")
+AUGMENT_LAST_ELEMENT = 65
+AUGMENT_SIGNATURES = {
+    "mdnoaug_motions": (_I, [_U64, _P, _I, _L, _I, _D, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "mdnoaug_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "mdnoaug_edge_attr": (_I, [_P, _P, _L, _L, _P, _P]),
 }
 
 # include/mdno_unroll.h: gradients w.r.t. the model's inputs, targets of an unrolled step
@@ -320,6 +328,7 @@ TABLES = (
     ("mdno_constrain.h", CONSTRAIN_SIGNATURES),
     ("mdno_pbc_train.h", PBC_TRAIN_SIGNATURES),
     ("mdno_contacts.h", CONTACTS_SIGNATURES),
+    ("mdno_augment.h", AUGMENT_SIGNATURES),
 )
 
 

@@ -7,8 +7,9 @@
 //     counter  (stream_id, index_lo, element >> 2, purpose_word)
 //       stream_id     global ensemble member (rollout) or the sample's index in its dataset (training)
 //       index         absolute step number (rollout) or epoch (training), 0 <= index < 2^48
-//       element       atom * 3 + component (rollout), (frame_in_window * N + atom) * 3 + component (training window)
-//       purpose_word  purpose | second << 8 | index_hi << 16: purpose NOISE_ROLLOUT / NOISE_TRAIN_WINDOW (< 256),
+//       element       atom * 3 + component (rollout), (frame_in_window * N + atom) * 3 + component (training window),
+//                     the draw's number (a training sample's rigid motion: rigid_rule.h)
+//       purpose_word  purpose | second << 8 | index_hi << 16: purpose NOISE_ROLLOUT / NOISE_TRAIN_WINDOW / NOISE_TRAIN_MOTION (< 256),
 //                     second = 0 for the block u1 is taken from and 1 for u2's, index_hi = index >> 32 (0 for every
 //                     index below 2^32, so the word is then just purpose, or purpose | 0x100)
 //     the element uses word (element & 3) of both blocks:
@@ -27,7 +28,7 @@
 
 namespace mdno {
 
-enum NoisePurpose { NOISE_ROLLOUT = 0, NOISE_TRAIN_WINDOW = 1 };
+enum NoisePurpose { NOISE_ROLLOUT = 0, NOISE_TRAIN_WINDOW = 1, NOISE_TRAIN_MOTION = 2 };
 constexpr long long kNoiseMaxIndex = 1ll << 48;
 
 MDNO_HD uint32_t philox_mulhi(uint32_t a, uint32_t b) {

@@ -246,11 +246,14 @@ class DataParallelTrainer:
         check_train_status(model)
         return combine_losses(vals.cpu().tolist() if per else [], sizes, size_average)
 
-    def train_epoch(self, batches, source=None, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0) -> Tuple[float, float]:
+    def train_epoch(self, batches, source=None, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0,
+                    augment=None) -> Tuple[float, float]:
         """One training pass over the global batch list (lists of PairData, or lists of sample indices into `source`,
         a DeviceTrajectory) -> (avg relative-L2 loss, avg MSE), the same numbers on every rank.
         noise_std > 0 (index batches only): `source.batch(..., noise_std, noise_seed, epoch)` — keyed by dataset index,
-        so a sample's noise is the same on whichever rank its shard falls."""
+        so a sample's noise is the same on whichever rank its shard falls.
+        augment = a `training.RigidAugment` (index batches only): `source.batch(..., augment=augment, epoch=epoch)` — the
+        motion is keyed by dataset index too, so a sample moves the same way on whichever rank it lands."""
         batches = list(batches)
         self._check_batches(batches, source)
         noise = None
@@ -258,6 +261,10 @@ class DataParallelTrainer:
             if source is None:
                 raise ValueError("noise_std needs batches of sample indices and `source` (a DeviceTrajectory)")
             noise = dict(noise_std=float(noise_std), noise_seed=int(noise_seed), epoch=int(epoch))
+        if augment is not None:
+            if source is None:
+                raise ValueError("augment needs batches of sample indices and `source` (a DeviceTrajectory)")
+            noise = dict(noise or {}, augment=augment, epoch=int(epoch))
         model, opt = self.model, self.optimizer
         sa = bool(self.loss_fn.size_average)
         model.train()

@@ -1143,6 +1143,86 @@ def noise_add_window(x_position: torch.Tensor, sample_ids, row_offsets: torch.Te
 
 
 # ------------------------------------------------------------------------------------------------
+# Random rigid motions of training samples (include/mdno_augment.h, csrc/rigid_rule.h, csrc/augment.hip)
+def rigid_motions(seed: int, sample_ids, epoch: int, rotate: bool = True, translate: float = 0.0,
+                  last_element: int = _lib.AUGMENT_LAST_ELEMENT, first_frame: Optional[torch.Tensor] = None,
+                  n_atoms: Optional[int] = None, device=None):
+    """One rigid motion per sample of `sample_ids` (ints or an integer tensor [B]: indices in the dataset), keyed by
+    (seed, sample, epoch) alone (mdnoaug_motions) -> (quaternion f64 [B,4] as (w,x,y,z), pivot f64 [B,3], shift f64 [B,3],
+    attempts i32 [B,2]).  An int32 tensor already on the device is taken as it is (no read-back to check its range).
+    first_frame f32 [B * n_atoms, 3]: the pivot is every sample's centroid in it; None: the origin.
+    last_element < 65 shortens the rejection loop (tests reach the identity fallback with it)."""
+    seed, epoch, last_element, translate = _noise_seed(seed), int(epoch), int(last_element), float(translate)
+    if not 2 <= last_element <= _lib.AUGMENT_LAST_ELEMENT:
+        raise MdnoError(f"last_element={last_element} outside [2, {_lib.AUGMENT_LAST_ELEMENT}]")
+    if not 0.0 <= translate < float("inf"):
+        raise MdnoError(f"translate={translate} must be finite and >= 0")
+    if not 0 <= epoch < 2 ** 48:
+        raise MdnoError(f"epoch={epoch} outside [0, 2^48)")
+    B = int(torch.as_tensor(sample_ids).numel())
+    if first_frame is not None:
+        n_atoms = int(n_atoms) if n_atoms is not None else 0
+        if n_atoms < 1 or first_frame.dim() != 2 or tuple(first_frame.shape) != (B * n_atoms, 3):
+            raise MdnoError(f"first_frame shape {tuple(first_frame.shape)}: expected [B * n_atoms, 3] = [{B * n_atoms}, 3]")
+        device = first_frame.device if device is None else device
+    lib = _lib.load()
+    dev = _lib.require_gpu(device)
+    if torch.is_tensor(sample_ids) and sample_ids.dtype == torch.int32 and sample_ids.device == dev:
+        ids = sample_ids.reshape(-1).contiguous()
+    else:
+        ids = _noise_ids(sample_ids, dev, "sample_ids")
+    frame = None if first_frame is None else f32(first_frame)
+    q = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    pivot = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    shift = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    attempts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    check(lib.mdnoaug_motions(seed, ptr(ids), B, epoch, int(bool(rotate)), translate, last_element, ptr(frame),
+                              int(n_atoms or 0), ptr(q), ptr(pivot), ptr(shift), ptr(attempts), stream_ptr(dev)),
+          "mdnoaug_motions")
+    return q, pivot, shift, attempts
+
+
+def rigid_apply(quaternion: torch.Tensor, pivot: torch.Tensor, shift: torch.Tensor, n_atoms: int, rows: torch.Tensor,
+                inverse: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The motions (inverse: their inverses) of `rows` f32 [..., B * N, 3] (mdnoaug_apply): sample b owns rows
+    b * N .. b * N + N - 1 of every frame.  A new tensor, or `out` (which may be `rows`: in place)."""
+    B, N = int(quaternion.shape[0]), int(n_atoms)
+    if tuple(quaternion.shape) != (B, 4) or tuple(pivot.shape) != (B, 3) or tuple(shift.shape) != (B, 3) or \
+            any(t.dtype != torch.float64 for t in (quaternion, pivot, shift)):
+        raise MdnoError("quaternion [B, 4], pivot [B, 3] and shift [B, 3] must be float64")
+    if rows.dim() < 2 or rows.shape[-1] != 3 or rows.shape[-2] != B * N:
+        raise MdnoError(f"rows shape {tuple(rows.shape)}: expected [..., B * N, 3] with B * N = {B} * {N}")
+    lib = _lib.load()
+    x = f32(rows)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device:
+        raise MdnoError("out must be a float32 tensor of the shape and device of rows")
+    F = x.numel() // max(B * N * 3, 1)
+    check(lib.mdnoaug_apply(ptr(quaternion), ptr(pivot), ptr(shift), B, N, F, int(bool(inverse)), ptr(x), ptr(out),
+                            stream_ptr(x.device)), "mdnoaug_apply")
+    return out
+
+
+def edge_attr_gather(x0: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    """edge_attr f32 [E, 6] of a collated batch gathered again from its first window frame x0 f32 [R, 3]
+    (mdnoaug_edge_attr): row e = (x0[edge_index[0][e]], x0[edge_index[1][e]]), NaN where an index lies outside [0, R)."""
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise MdnoError(f"edge_index shape {tuple(edge_index.shape)}: expected [2, E]")
+    if edge_index.dtype != torch.int64:
+        raise MdnoError(f"edge_index must be int64 (got {edge_index.dtype})")
+    if x0.dim() != 2 or x0.shape[1] != 3:
+        raise MdnoError(f"x0 shape {tuple(x0.shape)}: expected [R, 3]")
+    lib = _lib.load()
+    x = f32(x0)
+    E = int(edge_index.shape[1])
+    out = torch.empty((E, 6), dtype=torch.float32, device=x.device)
+    check(lib.mdnoaug_edge_attr(ptr(x), ptr(edge_index), E, int(x.shape[0]), ptr(out), stream_ptr(x.device)),
+          "mdnoaug_edge_attr")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 def lploss_rel_fwd(out: torch.Tensor, y: torch.Tensor, size_average: bool):
     """LpLoss.rel, p = 2, and the batch MSE in one pass (include/mdno.h mdno_lploss_rel_fwd): out, y f32 [B, D] ->
     (loss_mse f32 [2] = [loss, mse], stats f32 [B, 4] for the backward)."""

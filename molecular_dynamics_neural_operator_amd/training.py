@@ -319,7 +319,8 @@ class DeviceTrajectory:
         first = start + self.W + self.horizon - 1
         return self.pos[first:first + steps]
 
-    def batch(self, indices, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0, unroll: int = 1) -> PairData:
+    def batch(self, indices, noise_std: float = 0.0, noise_seed: int = 0, epoch: int = 0, unroll: int = 1,
+              augment=None) -> PairData:
         """unroll = K > 1: the batch also carries `y_unroll` f32 [K, B*N, 3], the true frames an unrolled step of K
         model steps is scored against (frame idx + W + k of every sample, k < K; one more launch: include/mdno_unroll.h
         mdno_collate_targets); `y` stays `y_unroll[0]`.  Needs horizon 1 (the window slides one frame per step) and
@@ -328,6 +329,10 @@ class DeviceTrajectory:
         noise_std * z(noise_seed, sample index, epoch, frame, atom, component) added on the device (include/mdno_noise.h
         mdno_noise_add_window).  The key is the sample's index in the dataset: a sample's noise does not depend on the
         batch it is in, the batch size or the rank.  The batch carries `sample_ids` / `rows_per_sample` either way.
+        augment = a `RigidAugment`: every sample is moved by its own random rigid motion, keyed by (augment.seed, sample
+        index, epoch) — `augment_batch(batch, augment, epoch)`: windows, `y`, `y_unroll` moved, `edge_attr` gathered again,
+        the batch carries `.motions`.  Noise, if asked for, is added after the motion with the values it always had.
+        None: not one launch, allocation or bit differs.  Not under a box (`MdnoError`).
         Under a box (`DeviceTrajectory(box=)`): `edge_index` [2, E] holds the sources in row 0 (sorted by target, sources
         ascending), `edge_attr` the imaged rows, and the batch carries `box` and `cutoff` (`_periodic_batch`)."""
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
@@ -342,6 +347,9 @@ class DeviceTrajectory:
             raise IndexError(f"unroll={K}: sample indices must lie in [0, {self.length - K}] (the last target is frame "
                              f"index + window + {K - 1})")
         B = int(idx.size)
+        if augment is not None and self.box is not None:
+            raise MdnoError("rigid augmentation under a periodic box is not supported: an orthorhombic cell is not "
+                            "rotation-invariant")
         if self.box is not None:
             return self._periodic_batch(idx, B, K, noise_std, noise_seed, epoch)
         cnt = self.counts[idx]
@@ -366,6 +374,8 @@ class DeviceTrajectory:
             out.y_unroll = ops.collate_targets(self.pos, meta_d, B, self.N, self.W, self.horizon, K)
         else:
             out.y_unroll = y.unsqueeze(0)
+        if augment is not None:
+            out = augment_batch(out, augment, epoch)
         if float(noise_std) != 0.0:
             out.x_position = add_window_noise(out, noise_std, noise_seed, epoch)
         return out
@@ -410,6 +420,164 @@ def add_window_noise(batch: PairData, noise_std: float, noise_seed: int = 0, epo
     n, dev = int(batch.rows_per_sample), batch.x_position.device
     offs = torch.arange(0, (len(ids) + 1) * n, n, dtype=torch.int32, device=dev)
     return ops.noise_add_window(batch.x_position, ids, offs, n, noise_std, noise_seed, epoch)
+
+
+# ------------------------------------------------------------------------------------------------
+# Random rigid motions of training samples (include/mdno_augment.h; the rule: csrc/rigid_rule.h)
+RIGID_PIVOTS = ("centroid", "origin")
+
+
+class RigidAugment:
+    """What `DeviceTrajectory.batch(augment=)`, `train_epoch(augment=)` and `augment_batch` draw a sample's motion
+    from: a uniform rotation (`rotate`) about the `pivot` — the centroid of the sample's first window frame, or the
+    origin — and a translation uniform in the cube [-translate, translate]^3 (Angstrom), keyed by (seed, the sample's
+    index in its dataset, epoch) and nothing else."""
+
+    def __init__(self, seed: int = 0, rotate: bool = True, translate: float = 0.0, pivot: str = "centroid"):
+        self.seed = ops._noise_seed(seed)
+        self.rotate = bool(rotate)
+        self.translate = float(translate)
+        if not 0.0 <= self.translate < float("inf"):
+            raise MdnoError(f"translate={translate} must be finite and >= 0")
+        if pivot not in RIGID_PIVOTS:
+            raise MdnoError(f"pivot={pivot!r}: expected one of {list(RIGID_PIVOTS)}")
+        self.pivot = pivot
+
+    def __repr__(self) -> str:
+        return f"RigidAugment(seed={self.seed}, rotate={self.rotate}, translate={self.translate}, pivot={self.pivot!r})"
+
+
+class RigidMotions:
+    """The motions of the B samples of one collated batch, on the batch's device: `quaternion` f64 [B,4] (w,x,y,z; not
+    normalised), `pivot` f64 [B,3], `shift` f64 [B,3], `attempts` i32 [B,2] (the accepted elements of the rejection
+    loop, -1 where the identity was taken instead) and `n_atoms`, the rows every sample owns."""
+
+    def __init__(self, quaternion, pivot, shift, attempts, n_atoms: int):
+        self.quaternion, self.pivot, self.shift, self.attempts = quaternion, pivot, shift, attempts
+        self.n_atoms = int(n_atoms)
+
+    def __len__(self) -> int:
+        return int(self.quaternion.shape[0])
+
+    @classmethod
+    def identity(cls, B: int, n_atoms: int, device) -> "RigidMotions":
+        q = torch.zeros((int(B), 4), dtype=torch.float64, device=device)
+        q[:, 0] = 1.0
+        zero = torch.zeros((int(B), 3), dtype=torch.float64, device=device)
+        return cls(q, zero, zero.clone(), torch.full((int(B), 2), -1, dtype=torch.int32, device=device), n_atoms)
+
+    def apply(self, rows: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+        """rows f32 [..., B*N, 3] -> the moved rows as a new tensor (mdnoaug_apply); inverse=True undoes `apply` up to
+        the two fp32 roundings.  Works on a window [W, B*N, 3], on targets [B*N, 3] and on the `[S, M*N, 3]` view of
+        an engine's frames alike."""
+        return ops.rigid_apply(self.quaternion, self.pivot, self.shift, self.n_atoms, rows, inverse=inverse)
+
+    def matrices(self) -> torch.Tensor:
+        """fp64 [B,3,3], the rule's nine entries written in torch (for users; the kernels form them themselves)."""
+        w, x, y, z = self.quaternion.unbind(1)
+        g = 2.0 / (((w * w + x * x) + y * y) + z * z)
+        rows = [1.0 - g * (y * y + z * z), g * (x * y - w * z), g * (x * z + w * y),
+                g * (x * y + w * z), 1.0 - g * (x * x + z * z), g * (y * z - w * x),
+                g * (x * z - w * y), g * (y * z + w * x), 1.0 - g * (x * x + y * y)]
+        return torch.stack(rows, dim=1).view(-1, 3, 3)
+
+
+def _augmentable(batch, what: str):
+    """(sample_ids, rows per sample) of a batch a motion can be drawn for."""
+    ids = getattr(batch, "sample_ids", None) if isinstance(batch, PairData) else None
+    if ids is None:
+        raise MdnoError(f"{what} needs batches from DeviceTrajectory.batch (they carry their samples' dataset "
+                        "indices); host-collated samples have none")
+    if getattr(batch, "box", None) is not None:
+        raise MdnoError(f"{what} under a periodic box is not supported: an orthorhombic cell is not rotation-invariant")
+    return ids, int(batch.rows_per_sample)
+
+
+def draw_motions(batch: PairData, augment: RigidAugment, epoch: int = 0) -> RigidMotions:
+    """The motions `augment` gives the samples of a `DeviceTrajectory.batch` at `epoch` (one launch: mdnoaug_motions)."""
+    if not isinstance(augment, RigidAugment):
+        raise MdnoError(f"augment must be a RigidAugment (got {type(augment).__name__})")
+    ids, n = _augmentable(batch, "rigid augmentation")
+    x = batch.x_position
+    frame = x[0] if augment.pivot == "centroid" else None
+    # the indices go up through pinned memory without blocking the host (a pageable source is copied synchronously:
+    # measured, that stall cost a training step more than the five launches)
+    ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31):
+        raise MdnoError("sample_ids must lie in [0, 2^31)")
+    if x.is_cuda:
+        ids = torch.from_numpy(ids.astype(np.int32)).pin_memory().to(x.device, non_blocking=True)
+    q, c, t, att = ops.rigid_motions(augment.seed, ids, epoch, augment.rotate, augment.translate, first_frame=frame,
+                                     n_atoms=n, device=x.device)
+    return RigidMotions(q, c, t, att, n)
+
+
+def move_batch(batch: PairData, motions: RigidMotions) -> PairData:
+    """A new collated batch, every sample moved by its motion: all window frames, `y` and every step of `y_unroll` by
+    `motions.apply`, `edge_attr` gathered again from the moved first window frame at `edge_index` (what collating the
+    moved samples gives); `edge_index` and `x_aminoacid` are the caller's tensors.  The caller's batch is untouched.
+    A batch put together by hand whose edge attributes hold the rows of another window frame (`construct_pairdata`
+    takes the newest) says so with `batch.edge_frame` (-1 there); a batch without targets has `y` None."""
+    _augmentable(batch, "rigid augmentation")
+    xp = motions.apply(batch.x_position)
+    edge_frame = int(getattr(batch, "edge_frame", 0))
+    out = PairData(batch.x_aminoacid, xp, None if batch.y is None else motions.apply(batch.y),
+                   ops.edge_attr_gather(xp[edge_frame], batch.edge_index), batch.edge_index)
+    if edge_frame:
+        out.edge_frame = edge_frame
+    out.num_graphs = getattr(batch, "num_graphs", len(motions))
+    out.sample_ids, out.rows_per_sample = batch.sample_ids, batch.rows_per_sample
+    yu = getattr(batch, "y_unroll", None)
+    if out.y is None:
+        out.y_unroll = None
+    elif yu is None or yu.shape[0] == 1:
+        out.y_unroll = out.y.unsqueeze(0)
+    else:
+        out.y_unroll = motions.apply(yu)
+    out.motions = motions
+    return out
+
+
+def augment_batch(batch: PairData, augment: RigidAugment, epoch: int = 0) -> PairData:
+    """`move_batch(batch, draw_motions(batch, augment, epoch))`: the batch `collate` would build from the moved samples.
+    It carries `.motions` (a `RigidMotions`: `motions.apply(out, inverse=True)` takes a prediction back)."""
+    return move_batch(batch, draw_motions(batch, augment, epoch))
+
+
+class EquivarianceError:
+    """`rms` f64 [B]: per sample, the root mean square over atoms of |f(g x) - g f(x)| in Angstrom; `step_rms` f64 [B]: the
+    same for |f(x) - x_last|, the size of the step the model takes, which sets the scale."""
+
+    def __init__(self, rms: torch.Tensor, step_rms: torch.Tensor):
+        self.rms, self.step_rms = rms, step_rms
+
+    def relative(self) -> torch.Tensor:
+        return self.rms / self.step_rms
+
+
+def _rms_over_atoms(u: torch.Tensor, v: torch.Tensor, B: int) -> torch.Tensor:
+    d = (u.double() - v.double()).view(B, -1, 3)          # (the difference is already an fp64 one)
+    return (d * d).sum(dim=(1, 2)).div(d.shape[1]).sqrt()
+
+
+def equivariance_error(model, batch: PairData, motions_or_augment, epoch: int = 0) -> EquivarianceError:
+    """How far `model` is from commuting with rigid motions on this batch: the inference forward (`model.eval()`, no
+    autograd) on the batch and on the moved batch, compared after moving the first prediction — f(g x) against g f(x).
+    `motions_or_augment`: a `RigidMotions` (`RigidMotions.identity` gives exactly 0) or a `RigidAugment`, drawn at
+    `epoch`.  A composition of the augmentation launches and two forwards; the reduction is fp64 torch."""
+    motions = motions_or_augment if isinstance(motions_or_augment, RigidMotions) else draw_motions(batch, motions_or_augment, epoch)
+    B = len(motions)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            out = model(batch)
+            moved = model(move_batch(batch, motions))
+            err = _rms_over_atoms(moved, motions.apply(out), B)
+            step = _rms_over_atoms(out, batch.x_position[-1], B)
+    finally:
+        model.train(was_training)
+    return EquivarianceError(err, step)
 
 
 # Longest window the prologue backward keeps per atom (csrc/train_nodes.hip MAX_W), largest embedding it handles
@@ -699,7 +867,8 @@ class Adam(torch.optim.Optimizer):
 
 
 def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = None, noise_std: float = 0.0,
-                noise_seed: int = 0, epoch: int = 0, unroll: int = 1, unroll_detach: bool = False, cutoff: float = 8.0):
+                noise_seed: int = 0, epoch: int = 0, unroll: int = 1, unroll_detach: bool = False, cutoff: float = 8.0,
+                augment=None):
     """One pass over `batches` — an iterable of lists of PairData (as the reference's DataListLoader yields)
     or of collated batches (`DeviceTrajectory.batch`): returns (avg relative-L2 loss, avg MSE) like train()
     (graph_kernel.py:445-474).  The per-batch losses stay on the device until the pass is over (the
@@ -708,6 +877,9 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
     noise_std > 0: every batch — collated by `DeviceTrajectory.batch` — trains on input windows perturbed by
     `add_window_noise(batch, noise_std, noise_seed, epoch)`; the caller's batches are left clean.  `validate_epoch`
     never adds noise.
+    augment = a `RigidAugment`: every batch — collated by `DeviceTrajectory.batch`, not periodic — trains on
+    `augment_batch(batch, augment, epoch)`, before any noise; the caller's batches are left as they are.  `validate_epoch`
+    never augments.  None: the pass runs as it always has.
     unroll = K > 1: every batch — collated by `DeviceTrajectory.batch(indices, unroll=K)`, which adds the K true frames
     `y_unroll` — trains on `unrolled_forward(model, batch, K, cutoff, detach=unroll_detach)`: the loss is the mean over
     the K steps of `loss_fn(out_k, y_k)`, and the returned pair is that mean and the mean MSE of the K steps.  unroll = 1
@@ -728,6 +900,8 @@ def train_epoch(model, batches, optimizer, loss_fn, batch_size: Optional[int] = 
         else:
             B = len(batch)
         optimizer.zero_grad()
+        if augment is not None:
+            batch = augment_batch(batch, augment, epoch)
         if float(noise_std) != 0.0:
             if not isinstance(batch, PairData):
                 raise MdnoError("noise_std needs collated batches from DeviceTrajectory.batch")

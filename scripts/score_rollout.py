@@ -37,11 +37,16 @@ With `--contacts [MIN_SEP]` also the contact statistics over the run (forecast.P
 pairs at least MIN_SEP apart in sequence, default 3): per member the mean |dP| between its contact-probability map and the
 truth's, the share of the native contacts (truth P >= 0.5) it keeps at P >= 0.5 and the share of its own P >= 0.5 contacts that
 are not native, the mean Q over the run beside the truth's own, and the contact survival at a few lags beside the truth's
-(INTEGRATION.md "Contact maps over time" reads them).
+(INTEGRATION.md "Contact maps over time" reads them).  With `--equivariance K` also how far the model is from commuting with
+rigid motions on the start windows (training.equivariance_error): K seeded motions (a uniform rotation about every member's
+centroid, plus `--equivariance-translate A`), the mean and the largest per-member RMS of |f(g x) - g f(x)| in Angstrom and the
+same relative to the size of the step |f(x) - x_last| (INTEGRATION.md "Training on rigid motions / how equivariant is the
+model?" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
                                     [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4] [--constrain 0.1] [--contacts 3]
+                                    [--equivariance 8]
 """
 import argparse
 import json
@@ -99,7 +104,14 @@ def main() -> None:
                          "the truth's over pairs at least MIN_SEP apart (default 3), the share of native contacts it keeps and "
                          "of its own contacts that are not native, the mean Q beside the truth's and the contact survival at a "
                          "few lags beside the truth's")
+    ap.add_argument("--equivariance", type=int, metavar="K", default=None,
+                    help="also the equivariance error of the model on the start windows: mean and max over K seeded rigid "
+                         "motions (and over the members) of the RMS of |f(g x) - g f(x)|, absolute and relative to the step")
+    ap.add_argument("--equivariance-translate", type=float, default=0.0, metavar="A",
+                    help="with --equivariance: also translate by up to A Angstrom per axis")
     a = ap.parse_args()
+    if a.equivariance is not None and (a.equivariance < 1 or not a.equivariance_translate >= 0.0):
+        ap.error("--equivariance takes K >= 1 (and --equivariance-translate A >= 0)")
     if a.contacts is not None and a.contacts < 0:
         ap.error("--contacts takes a MIN_SEP >= 0")
     if a.constrain is not None and not (a.constrain >= 0.0 and a.constrain_iterations >= 0):
@@ -225,6 +237,24 @@ def main() -> None:
                      "q_mean": finite(q_run.fraction().mean(0).cpu()), "q_mean_truth": finite(q_truth.fraction().mean(0).cpu())[0],
                      "contact_survival_lags": some, "contact_survival_mean": finite(s_run.nanmean(0).cpu()),
                      "contact_survival_truth": finite(s_truth[0].cpu())})
+
+    if a.equivariance is not None:
+        from molecular_dynamics_neural_operator_amd import ops
+        from molecular_dynamics_neural_operator_amd.dataset import PairData
+        from molecular_dynamics_neural_operator_amd.training import RigidAugment, equivariance_error
+        # the start windows as ONE collated batch of M samples, graph and attributes of the newest frame (construct_pairdata)
+        xw = torch.from_numpy(np.ascontiguousarray(wins.transpose(1, 0, 2, 3))).to(dev).reshape(W, M * N, 3)
+        ei = ops.radius_graph(xw[-1].contiguous(), N, a.threshold).to_edge_index()
+        start = PairData(torch.from_numpy(syn.amino_acids(N, seed=1)).to(dev).repeat(M), xw, None,
+                         torch.cat([xw[-1][ei[0]], xw[-1][ei[1]]], dim=1), ei)
+        start.num_graphs, start.sample_ids, start.rows_per_sample, start.edge_frame = M, np.arange(M), N, -1
+        aug = RigidAugment(seed=a.noise_seed, translate=a.equivariance_translate)
+        errs = [equivariance_error(model, start, aug, epoch=k) for k in range(a.equivariance)]
+        rms, rel = torch.stack([e_.rms for e_ in errs]), torch.stack([e_.relative() for e_ in errs])      # [K, M]
+        dist.update({"equivariance_motions": a.equivariance, "equivariance_translate": a.equivariance_translate,
+                     "equivariance_rms_mean": float(rms.mean()), "equivariance_rms_max": float(rms.max()),
+                     "equivariance_relative_mean": float(rel.mean()), "equivariance_relative_max": float(rel.max()),
+                     "equivariance_step_rms_mean": float(errs[0].step_rms.mean())})
 
     internal = None
     if a.internal is not None and S > 0:

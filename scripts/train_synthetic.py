@@ -2,6 +2,7 @@
 trajectory (N=28 C-alpha chain, Ornstein-Uhlenbeck jitter, contact maps at 8 A), 1 GPU.
 
   python scripts/train_synthetic.py [--frames 2000] [--batch-size 128] [--epochs 1] [--cpu-batches 1]
+                                    [--augment-rotate] [--augment-translate A] [--augment-seed S]
 
 Model, optimiser and loss as the reference's main() (graph_kernel.py:528-547): KernelNN(64, 1024, 6, 6, 7, 3,
 20, 4), Adam(lr, weight_decay=5e-4), StepLR(50, 0.8), LpLoss(size_average=False), partition split 0.8,
@@ -60,6 +61,12 @@ ap.add_argument("--box", type=float, nargs=3, metavar=("LX", "LY", "LZ"), defaul
                 help="train on a synthetic PERIODIC trajectory in this orthorhombic cell (0 = an open axis; every periodic "
                      "axis >= 16 A): synthetic.periodic_box_frame scaled to the cell plus ou_trajectory, batches from "
                      "DeviceTrajectory(box=); composes with --unroll, --noise-std and --structure-weight")
+ap.add_argument("--augment-rotate", action="store_true",
+                help="train every sample under a random rotation about its first frame's centroid, drawn anew every epoch "
+                     "(training.RigidAugment; device-collated batches, not under --box)")
+ap.add_argument("--augment-translate", type=float, default=0.0, metavar="A",
+                help="and / or under a random translation, uniform in [-A, A]^3 Angstrom")
+ap.add_argument("--augment-seed", type=int, default=0)
 ap.add_argument("--workdir", default="/tmp/mdno_train")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -87,6 +94,13 @@ n_train = int(len(dset) * 0.8)                                    # partition sp
 train_idx, valid_idx = list(range(n_train)), list(range(n_train, len(dset)))
 if a.unroll > 1 and a.host_collate:
     ap.error("--unroll needs device-collated batches (drop --host-collate)")
+augment = None
+if a.augment_rotate or a.augment_translate != 0.0:
+    from molecular_dynamics_neural_operator_amd.training import RigidAugment  # noqa: E402
+    if a.host_collate or a.cpu_batches or box is not None:
+        ap.error("--augment-rotate / --augment-translate move device-collated batches of an open system (drop --host-collate, "
+                 "--cpu-batches and --box)")
+    augment = RigidAugment(seed=a.augment_seed, rotate=a.augment_rotate, translate=a.augment_translate)
 B = a.batch_size
 traj_dev = None if a.host_collate else (DeviceTrajectory(dset, dev) if box is None else DeviceTrajectory(dset, dev, box=box))
 
@@ -160,6 +174,8 @@ summary["precision"] = a.precision
 if box is not None:
     summary["box"] = list(box)
 summary["unroll"], summary["unroll_detach"] = a.unroll, a.unroll_detach
+if augment is not None:
+    summary["augment"] = repr(augment)
 if step_loss is not loss_fn:
     summary.update(structure_weight=a.structure_weight, structure_min_sep=a.structure_min_sep, structure_stride=a.structure_stride,
                    structure_features=step_loss.featurizer.dim())
@@ -169,7 +185,7 @@ torch.cuda.reset_peak_memory_stats()
 for ep in range(a.epochs):
     t0 = time.perf_counter()
     tl, mse = train_epoch(model, batches, opt, step_loss, noise_std=a.noise_std, noise_seed=a.noise_seed, epoch=ep,
-                          unroll=a.unroll, unroll_detach=a.unroll_detach)
+                          unroll=a.unroll, unroll_detach=a.unroll_detach, augment=augment)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vl = validate()

@@ -891,6 +891,44 @@ def test_mdno_adam_matches_torch_adam(dev):
         torch.testing.assert_close(a_.detach(), b_.detach(), rtol=2e-6, atol=1e-7)
 
 
+def test_mdno_adam_more_tensors_than_one_launch_takes(dev):
+    """mdno_adam_step cuts its tensor list into launches of AD_MAX_TENSORS = 48 (csrc/optim.hip) and leaves empty tensors
+    out of each launch's table.  97 parameters of 1 .. 5,000 elements (4,096 and 4,097 around the 4,096-element
+    workgroup, 8,192 = two whole ones) with a zero-element tensor at list positions 0, 47, 48 and 96 — first and last
+    of the first launch, first of the second, alone in the third —; one parameter gets no gradient in the second step
+    (the list of that step is 96 long, and its step count then differs: two calls in the third step).  Three steps
+    against torch.optim.Adam in fp64, with the gates of test_mdno_adam_matches_torch_adam."""
+    from molecular_dynamics_neural_operator_amd.training import Adam as MdnoAdam
+    gen = torch.Generator().manual_seed(9)
+    sizes = torch.randint(1, 5001, (97,), generator=gen).tolist()
+    sizes[1], sizes[46], sizes[49], sizes[50], sizes[70], sizes[95] = 1, 4096, 4097, 5000, 3, 8192
+    for i in (0, 47, 48, 96):
+        sizes[i] = 0
+    init = [torch.randn(n, generator=gen) for n in sizes]
+    def make(dtype, device):
+        return [torch.nn.Parameter(t.detach().clone().to(device=device, dtype=dtype)) for t in init]
+    ours, theirs, exact = make(torch.float32, dev), make(torch.float32, dev), make(torch.float64, "cpu")
+    kw = dict(lr=3e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4)
+    opts = MdnoAdam(ours, **kw), torch.optim.Adam(theirs, **kw), torch.optim.Adam(exact, **kw)
+    for step in range(3):
+        grads = [torch.randn(n, generator=gen) * (10.0 ** (step - 1)) for n in sizes]
+        for plist, dt, dv in ((ours, torch.float32, dev), (theirs, torch.float32, dev), (exact, torch.float64, "cpu")):
+            for i, (p_, g_) in enumerate(zip(plist, grads)):
+                p_.grad = None if (i == 70 and step == 1) else g_.to(device=dv, dtype=dt)
+        for o in opts:
+            o.step()
+        for i, (a_, b_, c_) in enumerate(zip(ours, theirs, exact)):
+            assert a_.shape == c_.shape == (sizes[i],)
+            if sizes[i] == 0:
+                continue
+            ref = c_.detach()
+            assert not torch.equal(a_.detach().cpu(), init[i]), f"parameter {i} did not move"
+            err = float((a_.detach().cpu().double() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+            err_t = float((b_.detach().cpu().double() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+            assert err < 3e-6 and err <= 4 * err_t + 1e-7, (step, i, sizes[i], err, err_t)
+    assert float(opts[0].state[ours[70]]["step"]) == 2.0 and float(opts[0].state[ours[1]]["step"]) == 3.0
+
+
 @pytest.mark.parametrize("B,D,size_average", [(1, 84, False), (4, 84, True), (128, 84, False), (37, 1512, False), (300, 3, True)])
 def test_lploss_rel_on_device_vs_oracle(dev, O, B, D, size_average):
     """LpLoss.rel (p = 2) on device tensors runs in libmdno (csrc/loss.hip): loss, gradient and the batch MSE against

@@ -127,7 +127,14 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from ._args import INT_MAX, device_tensor, integer, on_device, tensor
 from ._lib import MdnoError
+
+
+def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """num / den in f64 (broadcast), NaN where den == 0 (no host read, no exception); a NaN or Inf in num passes through."""
+    num, den = torch.broadcast_tensors(num.to(torch.float64), den.to(torch.float64))
+    return torch.where(den == 0, torch.full_like(den, float("nan")), num / torch.where(den == 0, torch.ones_like(den), den))
 
 
 @dataclass
@@ -137,19 +144,15 @@ class ForecastScore:
     contacts: torch.Tensor            # i64 [S, M, 3]: forecast, truth, both
     first_nonfinite: torch.Tensor     # i32 [M]
 
-    @staticmethod
-    def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
-        """num / den as f64, NaN where den == 0 (no host read, no exception)."""
-        num, den = num.to(torch.float64), den.to(torch.float64)
-        return torch.where(den == 0, torch.full_like(den, float("nan")), num / den.clamp_min(1.0))
+    _ratio = staticmethod(_ratio)
 
     def precision(self) -> torch.Tensor:
         """Contacts in both / contacts in the forecast: f64 [S, M]."""
-        return self._ratio(self.contacts[..., 2], self.contacts[..., 0])
+        return _ratio(self.contacts[..., 2], self.contacts[..., 0])
 
     def recall(self) -> torch.Tensor:
         """Contacts in both / contacts in the truth: f64 [S, M]."""
-        return self._ratio(self.contacts[..., 2], self.contacts[..., 1])
+        return _ratio(self.contacts[..., 2], self.contacts[..., 1])
 
     def native_fraction(self) -> torch.Tensor:
         """The fraction of the true ("native") contacts the forecast keeps: both / truth, f64 [S, M]."""
@@ -158,7 +161,7 @@ class ForecastScore:
     def jaccard(self) -> torch.Tensor:
         """Contacts in both / contacts in either: f64 [S, M]."""
         c = self.contacts
-        return self._ratio(c[..., 2], c[..., 0] + c[..., 1] - c[..., 2])
+        return _ratio(c[..., 2], c[..., 0] + c[..., 1] - c[..., 2])
 
     def cpu(self) -> "ForecastScore":
         return ForecastScore(self.mse.cpu(), self.rmsd.cpu(), self.contacts.cpu(), self.first_nonfinite.cpu())
@@ -227,7 +230,7 @@ class PairHistogram:
         """counts / their total per row: f64 [..., n_bins], the distribution p(r) of the pair distances below r_max;
         NaN where the total is 0."""
         c = self.counts.to(torch.float64)
-        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+        return _ratio(c, c.sum(-1, keepdim=True).expand_as(c))
 
     def rdf(self) -> torch.Tensor:
         """The radial distribution function g(r) per bin: f64 [..., n_bins], counts over what an ideal gas of the same
@@ -294,13 +297,13 @@ class DisplacementStats:
 
     def msd(self) -> torch.Tensor:
         """Mean squared displacement <r^2>(lag): f64 [M, L]; NaN for a lag without samples."""
-        return ForecastScore._ratio(self.sum2, self._n())
+        return _ratio(self.sum2, self._n())
 
     def non_gaussian(self) -> torch.Tensor:
         """alpha_2(lag) = 3 <r^4> / (5 <r^2>^2) - 1: f64 [M, L], 0 for Gaussian displacements in three dimensions; NaN
         where <r^2> is 0 (lag 0) or there is no sample."""
         r2 = self.msd()
-        r4 = ForecastScore._ratio(self.sum4, self._n())
+        r4 = _ratio(self.sum4, self._n())
         return 3.0 * r4 / (5.0 * r2 * r2) - 1.0
 
     def _need_counts(self, what: str) -> torch.Tensor:
@@ -324,7 +327,7 @@ class DisplacementStats:
     def distribution(self) -> torch.Tensor:
         """counts / their total per (member, lag): f64 [M, L, n_bins]; NaN where the total is 0."""
         c = self._need_counts("distribution")
-        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+        return _ratio(c, c.sum(-1, keepdim=True).expand_as(c))
 
     def total_variation(self, other: "DisplacementStats") -> torch.Tensor:
         """0.5 * sum_b |p_b - q_b| of the two `distribution()`s per lag: f64 [M, L] (members broadcast, so a truth with
@@ -382,7 +385,7 @@ def displacement_stats(frames: torch.Tensor, lags=None, origin_stride: int = 1, 
     motion is subtracted.  `r_max`, `n_bins` > 0: also the histogram of the displacements (the self van Hove function).
     Asynchronous on the current stream; CPU tensors and bad arguments raise `MdnoError` before any device work."""
     if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
-        ops._trajectory(frames)           # raises with the shape message
+        device_tensor(frames, "frames", (3, 4), last=3)           # raises: no tensor, a CPU tensor or this shape
     S, N = int(frames.shape[0]), int(frames.shape[-2])
     lags = default_lags(S) if lags is None else ops.check_lags(lags, max(S, 1))
     stride = ops.check_origin_stride(origin_stride)
@@ -397,13 +400,13 @@ def velocity_autocorrelation(frames: torch.Tensor, lags=None, origin_stride: int
     v_i(t) . v_i(t + lag), v(t) = x(t + 1) - x(t) (divide by dt^2 for physical units).  `normalized`: C(lag) / C(0), which
     needs lag 0 among the lags (the default set has it).  Lags in 0 .. S - 2."""
     if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
-        ops._trajectory(frames)
+        device_tensor(frames, "frames", (3, 4), last=3)
     S, N = int(frames.shape[0]), int(frames.shape[-2])
     lags = default_lags(S, 1) if lags is None else ops.check_lags(lags, max(S, 2), 1, "velocity_autocorrelation")
     stride = ops.check_origin_stride(origin_stride, "velocity_autocorrelation")
     corr = ops.velocity_autocorrelation(frames, lags, stride, remove_com)
     lt, nt = _lag_tensors(lags, S, N, stride, 1, corr.device)
-    c = ForecastScore._ratio(corr, nt.to(torch.float64).expand_as(corr))
+    c = _ratio(corr, nt.to(torch.float64).expand_as(corr))
     if normalized:
         if 0 not in lags:
             raise MdnoError("velocity_autocorrelation: normalized=True needs lag 0 among the lags")
@@ -436,7 +439,7 @@ class EnsembleScore:
 
     def _mean(self, c: int) -> torch.Tensor:
         n = torch.full_like(self.sums[:, c], float(self.samples_per_step * self.n_steps))
-        return ForecastScore._ratio(self.sums[:, c], n)
+        return _ratio(self.sums[:, c], n)
 
     def rmse(self) -> torch.Tensor:
         """Root mean squared error of the ensemble mean: f64 [S]."""
@@ -465,7 +468,7 @@ class EnsembleScore:
     def rank_histogram(self) -> torch.Tensor:
         """rank_hist / its total per row (the valid samples): f64 [S, M + 1]; NaN where there is none."""
         c = self.rank_hist.to(torch.float64)
-        return ForecastScore._ratio(c, c.sum(-1, keepdim=True).expand_as(c))
+        return _ratio(c, c.sum(-1, keepdim=True).expand_as(c))
 
     def rank_flatness(self) -> torch.Tensor:
         """Total variation distance of `rank_histogram()` from the uniform 1 / (M + 1): f64 [S], 0 = flat."""
@@ -521,13 +524,13 @@ class CrossRmsd:
         """Is every produced frame close to SOME reference frame: per member the share of its valid frames with
         nearest <= radius, f64 [M]; NaN for a member without a valid frame (or without a valid reference)."""
         valid = self.nearest_index >= 0
-        return ForecastScore._ratio(((self.nearest <= radius) & valid).sum(0), valid.sum(0))
+        return _ratio(((self.nearest <= radius) & valid).sum(0), valid.sum(0))
 
     def coverage(self, radius: float) -> torch.Tensor:
         """Is every reference frame visited by the run: per member the share of the valid reference frames with
         cover <= radius, f64 [M]; NaN for a member without a valid step (or without a valid reference)."""
         valid = self.cover_step >= 0
-        return ForecastScore._ratio(((self.cover <= radius) & valid).sum(1), valid.sum(1))
+        return _ratio(((self.cover <= radius) & valid).sum(1), valid.sum(1))
 
     def to_reference(self, j: int) -> torch.Tensor:
         """Column j of the matrix, f64 [S, M]: the RMSD time series of every member to ONE structure (a folded state)."""
@@ -575,9 +578,7 @@ def _feature_rows(X: torch.Tensor, what: str = "X") -> Tuple[torch.Tensor, Tuple
     """(X as [S, M, D], its leading shape): [S, M, N, 3] -> D = 3 N; [F, N, 3] -> one member, D = 3 N; [S, M, D]; [F, D] -> one
     member.  A rank-3 tensor whose last dimension is 3 is taken as FRAMES [F, N, 3]: pass three features of M members as
     [S, M, 1, 3]."""
-    if not torch.is_tensor(X):
-        raise MdnoError(f"{what} must be a torch tensor, got {type(X).__name__}")
-    if X.dim() == 4 and X.shape[-1] == 3:
+    if tensor(X, what).dim() == 4 and X.shape[-1] == 3:
         return X.reshape(X.shape[0], X.shape[1], -1), tuple(X.shape[:2])
     if X.dim() == 3 and X.shape[-1] == 3:
         return X.reshape(X.shape[0], 1, -1), tuple(X.shape[:1])
@@ -674,12 +675,6 @@ class Components:
         return Components(self.values.cpu(), self.vectors.cpu(), self.mean.cpu(), self.total, self.lag)
 
 
-def _check_k(k, limit: int, what: str) -> int:
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= limit:
-        raise MdnoError(f"{what}: k = {k!r}, expected an integer in 1 .. {limit}")
-    return k
-
-
 def pca(cov: Covariance, k: int) -> Components:
     """The k leading principal components of a lag-0 `Covariance`: fp64 torch.linalg.eigh of cov.matrix() on the HOST copy
     (one read-back of D^2 doubles), eigenvalues descending, every vector's largest-magnitude entry positive (the lowest
@@ -687,7 +682,7 @@ def pca(cov: Covariance, k: int) -> Components:
     if cov.lag != 0:
         raise MdnoError(f"pca needs a lag-0 covariance, got lag {cov.lag}")
     D = cov.sums.shape[0]
-    k = _check_k(k, D, "pca")
+    k = integer(k, "pca: k", 1, D)
     m = cov.matrix().cpu()
     w, v = torch.linalg.eigh(0.5 * (m + m.transpose(0, 1)))
     w, v = w.flip(0)[:k], _fix_signs(v.flip(1)[:, :k].contiguous())
@@ -708,7 +703,7 @@ def tica(cov0: Covariance, cov_lag: Covariance, k: int, eps: float = 1e-10) -> C
     w, u = torch.linalg.eigh(c0)
     keep = w > eps * w[-1] if w.numel() and w[-1] > 0 else torch.zeros_like(w, dtype=torch.bool)
     r = int(keep.sum())
-    k = _check_k(k, r, f"tica ({r} of {w.numel()} dimensions above eps)") if r else _check_k(k, 0, "tica (C(0) has no positive eigenvalue)")
+    k = integer(k, f"tica ({r} of {w.numel()} dimensions above eps): k" if r else "tica (C(0) has no positive eigenvalue): k", 1, r)
     white = u[:, keep] / torch.sqrt(w[keep])
     lam, q = torch.linalg.eigh(white.transpose(0, 1) @ ct @ white)
     lam, q = lam.flip(0)[:k], q.flip(1)[:, :k]
@@ -733,8 +728,7 @@ def free_energy(P: torch.Tensor, i: int = 0, j: int = 1, bins: int = 50, range=N
     if not torch.is_tensor(P) or P.dim() < 1:
         raise MdnoError("free_energy: P must be a tensor [..., k]")
     k = P.shape[-1]
-    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 1:
-        raise MdnoError(f"free_energy: bins = {bins!r}, expected a positive integer")
+    bins = integer(bins, "free_energy: bins", 1, None)
     if not (0 <= i < k and 0 <= j < k):
         raise MdnoError(f"free_energy: components {i} and {j} of {k}")
     pts = [P[..., c].reshape(-1).to(torch.float64).contiguous() for c in (i, j)]
@@ -792,8 +786,8 @@ def _index_array(a, width: int, n_atoms: Optional[int], what: str) -> torch.Tens
     lo, hi = int(t.min()), int(t.max())
     if lo < 0:
         raise MdnoError(f"{what}: index {lo} is negative")
-    if hi >= (2 ** 31 - 1 if n_atoms is None else n_atoms):
-        raise MdnoError(f"{what}: index {hi} is outside 0 .. {(2 ** 31 - 1 if n_atoms is None else n_atoms) - 1}")
+    if hi >= (INT_MAX if n_atoms is None else n_atoms):
+        raise MdnoError(f"{what}: index {hi} is outside 0 .. {(INT_MAX if n_atoms is None else n_atoms) - 1}")
     return t.to(torch.int32).contiguous()
 
 
@@ -812,8 +806,8 @@ class Featurizer:
 
     @staticmethod
     def of(pairs=None, triples=None, quads=None, n_atoms: Optional[int] = None, device=None) -> "Featurizer":
-        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
-            raise MdnoError(f"Featurizer: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        if n_atoms is not None:
+            integer(n_atoms, "Featurizer: n_atoms", 0, None)
         arrays = [_index_array(a, w, n_atoms, what) for a, w, what in ((pairs, 2, "pairs"), (triples, 3, "triples"), (quads, 4, "quads"))]
         top = max([int(t.max()) for t in arrays if t.numel()], default=-1)
         f = Featurizer(arrays[0], arrays[1], arrays[2], n_atoms, top)
@@ -837,8 +831,7 @@ class Featurizer:
         (i, j) of the atoms 0, stride, 2 stride, ... with j - i >= min_separation, the n - 2 pseudo-angles and the n - 3
         pseudo-dihedrals."""
         for name, v, low in (("n_atoms", n_atoms, 0), ("min_separation", min_separation, 1), ("stride", stride, 1)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < low:
-                raise MdnoError(f"Featurizer.backbone: {name} = {v!r}, expected an integer >= {low}")
+            integer(v, f"Featurizer.backbone: {name}", low, None)
         n = n_atoms
         idx = torch.arange(n, dtype=torch.int64)
         bonds = torch.stack([idx[:-1], idx[1:]], 1) if n > 1 else torch.zeros((0, 2), dtype=torch.int64)
@@ -890,8 +883,7 @@ class Featurizer:
         tuples flattened in (item, slot) order, stably sorted by atom (so an atom's entries ascend; a tuple that names an
         atom twice gives it two), entries whose atom is >= n_atoms dropped.  Cached per (n_atoms, device) on this instance;
         `.to` and `+` make instances without a cache."""
-        if isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0:
-            raise MdnoError(f"Featurizer.incidence: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        integer(n_atoms, "Featurizer.incidence: n_atoms", 0, None)
         device = self.pairs.device if device is None else torch.device(device)
         key = (n_atoms, str(device))
         hit = self._incidence.get(key)
@@ -967,8 +959,7 @@ def internal_coordinates(frames: torch.Tensor, featurizer: Featurizer, box=None,
     if wants_grad and radians:
         raise MdnoError("internal_coordinates: radians=True is not differentiable and frames requires grad (detach the frames, "
                         "or take the cosine and sine columns of the default mode)")
-    if not frames.is_cuda:
-        raise MdnoError("frames is a CPU tensor: the internal-coordinate kernels run on the GPU only (no CPU fallback exists)")
+    on_device(frames, "frames")
     owner = featurizer
     if featurizer.pairs.device != frames.device:
         featurizer = featurizer.to(frames.device)
@@ -990,7 +981,7 @@ class FeatureHistograms:
 
     def distribution(self) -> torch.Tensor:
         """counts / their sum per column, f64 (NaN for a column without a counted value)."""
-        return ForecastScore._ratio(self.counts, self.counts.sum(-1, keepdim=True).expand_as(self.counts))
+        return _ratio(self.counts, self.counts.sum(-1, keepdim=True).expand_as(self.counts))
 
     def total_variation(self, other: "FeatureHistograms") -> torch.Tensor:
         """Per column, 0.5 sum |p - q| over all bins + 2 bins: f64 [M, D] or [D]; the other's leading dimensions broadcast
@@ -1001,7 +992,7 @@ class FeatureHistograms:
 
     def outside(self) -> torch.Tensor:
         """The share of the counted values below lo or at or above hi, per column: f64 [M, D] or [D]."""
-        return ForecastScore._ratio(self.counts[..., 0] + self.counts[..., -1], self.counts.sum(-1))
+        return _ratio(self.counts[..., 0] + self.counts[..., -1], self.counts.sum(-1))
 
     def cpu(self) -> "FeatureHistograms":
         return FeatureHistograms(self.counts.cpu(), self.n_nan.cpu(), self.lo, self.hi)
@@ -1057,7 +1048,7 @@ class Assignment:
         r = radius.to(self.dist2.device, torch.float64) if torch.is_tensor(radius) else float(radius)
         inside = torch.sqrt(self.dist2) <= r                                        # (NaN: not inside; sqrt is monotone, so a
         #                                                                             frame AT the covering radius is inside)
-        return ForecastScore._ratio((~inside).sum(0), torch.full_like(inside.sum(0), self.dist2.shape[0] if self.dist2.dim() else 1))
+        return _ratio((~inside).sum(0), torch.full_like(inside.sum(0), self.dist2.shape[0] if self.dist2.dim() else 1))
 
     def populations(self, n_states: int) -> torch.Tensor:
         """The share of the labelled frames in each state, per member: f64 [M, n_states] ([n_states] for [F]); NaN for a
@@ -1067,7 +1058,7 @@ class Assignment:
         ok = (lab >= 0) & (lab < n_states)
         flat = (torch.arange(M, device=lab.device)[None] * n_states + lab)[ok]
         counts = torch.bincount(flat, minlength=M * n_states).reshape(M, n_states)
-        pops = ForecastScore._ratio(counts, counts.sum(1, keepdim=True).expand_as(counts))
+        pops = _ratio(counts, counts.sum(1, keepdim=True).expand_as(counts))
         return pops.reshape(self.labels.shape[1:] + (n_states,))
 
     def cpu(self) -> "Assignment":
@@ -1131,8 +1122,7 @@ def kmeans(X: torch.Tensor, k: int, iters: int = 10, init: Optional[torch.Tensor
     whose label round i changed (0: converged); it stays on the device, like everything inside the loop — nothing is read
     back."""
     rows, lead = _state_rows(X)
-    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
-        raise MdnoError(f"kmeans: iters = {iters!r}, expected an integer >= 0")
+    iters = integer(iters, "kmeans: iters", 0, None)
     if init is None:
         centres = kcenters(rows, k)[0]
     else:
@@ -1316,7 +1306,7 @@ class MarkovModel:
         """The implied timescales -lag / ln |lambda_i| in steps for i = 2 .. k + 1 (default: all), f64 [k]: inf at
         |lambda| = 1, 0 at lambda = 0."""
         a = self.eigenvalues.shape[0]
-        k = a - 1 if k is None else _check_k(k, max(a - 1, 0), "timescales") if a > 1 else _check_k(k, 0, "timescales (one active state)")
+        k = a - 1 if k is None else integer(k, "timescales: k" if a > 1 else "timescales (one active state): k", 1, max(a - 1, 0))
         mag = self.eigenvalues.abs()[1:k + 1].to(torch.float64)
         ts = -float(self.lag) / torch.log(mag)
         return torch.where(mag >= 1.0, torch.full_like(ts, float("inf")), torch.where(mag == 0.0, torch.zeros_like(ts), ts))
@@ -1443,8 +1433,8 @@ class DistanceConstraints:
 
     @staticmethod
     def of(pairs, lo, hi, weights=None, n_atoms: Optional[int] = None) -> "DistanceConstraints":
-        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
-            raise MdnoError(f"DistanceConstraints: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        if n_atoms is not None:
+            integer(n_atoms, "DistanceConstraints: n_atoms", 0, None)
         p = _index_array(pairs, 2, n_atoms, "pairs")
         n_c = int(p.shape[0])
         if n_c > ops.CST_MAX_CONSTRAINTS:
@@ -1490,8 +1480,7 @@ class DistanceConstraints:
     @staticmethod
     def chain(n_atoms: int, lo, hi, weights=None) -> "DistanceConstraints":
         """The n - 1 consecutive pseudo-bonds (i, i + 1) of a chain, each inside [lo, hi] (numbers, or one per bond)."""
-        if isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0:
-            raise MdnoError(f"DistanceConstraints.chain: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        integer(n_atoms, "DistanceConstraints.chain: n_atoms", 0, None)
         idx = torch.arange(n_atoms, dtype=torch.int64)
         bonds = torch.stack([idx[:-1], idx[1:]], 1) if n_atoms > 1 else torch.zeros((0, 2), dtype=torch.int64)
         return DistanceConstraints.of(bonds, lo, hi, weights, n_atoms)
@@ -1581,8 +1570,7 @@ def project_constraints(frames: torch.Tensor, constraints: DistanceConstraints, 
     if not torch.is_tensor(frames) or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
         raise MdnoError("project_constraints: frames must be [S, M, N, 3] or [F, N, 3]")
     constraints.check_frames(int(frames.shape[-2]))
-    if not frames.is_cuda:
-        raise MdnoError("frames is a CPU tensor: the projection kernel runs on the GPU only (no CPU fallback exists)")
+    on_device(frames, "frames")
     t = constraints.coloured(frames.device)
     res, sweeps, vin, vout = ops.project_constraints(frames.detach(), t.pairs, t.lo, t.hi, t.colour_ptr, t.weights, box=box,
                                                      iterations=iterations, tol=tol, out=out)
@@ -1591,12 +1579,6 @@ def project_constraints(frames: torch.Tensor, constraints: DistanceConstraints, 
 
 # ------------------------------------------------------------------------------------------------
 # Contact statistics over time (csrc/contacts.hip, include/mdno_contacts.h has the rule)
-def _nan_ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
-    """num / den in f64 (broadcast), NaN where den == 0; a NaN or Inf in num passes through."""
-    num, den = torch.broadcast_tensors(num.to(torch.float64), den.to(torch.float64))
-    return torch.where(den == 0, torch.full_like(den, float("nan")), num / torch.where(den == 0, torch.ones_like(den), den))
-
-
 @dataclass
 class PairStatistics:
     """Per-pair statistics over blocks of consecutive steps (ops.pair_statistics): `count` i32 [Bk, M, N, N], the frames of
@@ -1640,17 +1622,17 @@ class PairStatistics:
 
     def probability(self) -> torch.Tensor:
         """count / n_frames: f64 [..., M, N, N], the contact-probability map; NaN for a block without frames."""
-        return _nan_ratio(self.count, self._n())
+        return _ratio(self.count, self._n())
 
     def mean_distance(self) -> torch.Tensor:
         """sum_r / n_frames: f64 [..., M, N, N]; NaN for a block without frames or a pair with a non-finite distance."""
-        return _nan_ratio(self._moments("mean_distance")[0], self._n())
+        return _ratio(self._moments("mean_distance")[0], self._n())
 
     def distance_std(self) -> torch.Tensor:
         """sqrt(max(sum_r2 / n - (sum_r / n)^2, 0)): f64 [..., M, N, N], the population standard deviation of the distance."""
         sr, sr2 = self._moments("distance_std")
-        mean = _nan_ratio(sr, self._n())
-        var = _nan_ratio(sr2, self._n()) - mean * mean
+        mean = _ratio(sr, self._n())
+        var = _ratio(sr2, self._n()) - mean * mean
         return torch.sqrt(torch.where(var < 0, torch.zeros_like(var), var))          # (a NaN fails the test and stays)
 
     def difference(self, other: "PairStatistics") -> torch.Tensor:
@@ -1667,12 +1649,11 @@ class PairStatistics:
     def map_error(self, other: "PairStatistics", min_separation: int = 0) -> torch.Tensor:
         """The mean of |difference(other)| over the ordered pairs with |i - j| >= min_separation: f64 [..., M]; NaN where
         no pair is that far apart."""
-        if isinstance(min_separation, bool) or not isinstance(min_separation, int) or min_separation < 0:
-            raise MdnoError(f"map_error: min_separation={min_separation!r}: expected an integer >= 0")
+        integer(min_separation, "map_error: min_separation", 0, None)
         d = self.difference(other).abs()
         idx = torch.arange(d.shape[-1], device=d.device)
         keep = ((idx[:, None] - idx[None, :]).abs() >= min_separation).to(torch.float64)
-        return _nan_ratio((d * keep).sum((-2, -1)), keep.sum().expand(d.shape[:-2]))
+        return _ratio((d * keep).sum((-2, -1)), keep.sum().expand(d.shape[:-2]))
 
     def cpu(self) -> "PairStatistics":
         return PairStatistics(self.count.cpu(), None if self.sum_r is None else self.sum_r.cpu(),
@@ -1729,8 +1710,8 @@ class ContactPairs:
 
     @staticmethod
     def of(pairs, cut, n_atoms: Optional[int] = None) -> "ContactPairs":
-        if n_atoms is not None and (isinstance(n_atoms, bool) or not isinstance(n_atoms, int) or n_atoms < 0):
-            raise MdnoError(f"ContactPairs: n_atoms = {n_atoms!r}, expected a non-negative integer")
+        if n_atoms is not None:
+            integer(n_atoms, "ContactPairs: n_atoms", 0, None)
         p = _index_array(pairs, 2, n_atoms, "pairs")
         n_p = int(p.shape[0])
         try:      # (Python numbers straight to f64)
@@ -1752,8 +1733,7 @@ class ContactPairs:
 
     @staticmethod
     def _separated(n: int, min_separation) -> Tuple[torch.Tensor, torch.Tensor]:
-        if isinstance(min_separation, bool) or not isinstance(min_separation, int) or min_separation < 0:
-            raise MdnoError(f"ContactPairs: min_separation={min_separation!r}: expected an integer >= 0")
+        integer(min_separation, "ContactPairs: min_separation", 0, None)
         i, j = torch.triu_indices(n, n, 1)
         far = (j - i) >= min_separation
         return i[far], j[far]
@@ -1818,11 +1798,11 @@ class ContactCorrelation:
     def survival(self) -> torch.Tensor:
         """sum_p both / sum_p origins: f64 [M, L], P(contact at t + lag | contact at t) pooled over the pairs; NaN where no
         pair was ever in contact."""
-        return _nan_ratio(self.both.sum(1, dtype=torch.int64), self.origins.sum(1, dtype=torch.int64))
+        return _ratio(self.both.sum(1, dtype=torch.int64), self.origins.sum(1, dtype=torch.int64))
 
     def per_pair(self) -> torch.Tensor:
         """both / origins: f64 [M, P, L]; NaN for a pair that was never in contact at an origin."""
-        return _nan_ratio(self.both, self.origins)
+        return _ratio(self.both, self.origins)
 
     def lifetime(self, dt: float = 1.0) -> torch.Tensor:
         """The trapezoid sum of survival() over the given lags times `dt`: f64 [M], a contact lifetime (in steps for dt = 1)
@@ -1858,7 +1838,7 @@ class ContactSeries:
 
     def fraction(self) -> torch.Tensor:
         """per_frame / P: f64 [S, M], the fraction of the listed (native) contacts present — Q(t); NaN for an empty list."""
-        return _nan_ratio(self.per_frame, torch.full((), len(self.pairs), dtype=torch.float64, device=self.per_frame.device))
+        return _ratio(self.per_frame, torch.full((), len(self.pairs), dtype=torch.float64, device=self.per_frame.device))
 
     def series(self) -> torch.Tensor:
         """The bits unpacked: bool [M, P, S]."""
@@ -1895,8 +1875,7 @@ def contact_series(frames: torch.Tensor, contact_pairs: ContactPairs, box=None) 
     if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[-1] != 3:
         raise MdnoError("contact_series: frames must be [S, M, N, 3]")
     contact_pairs.check_frames(int(frames.shape[-2]))
-    if not frames.is_cuda:
-        raise MdnoError("frames is a CPU tensor: the contact kernels run on the GPU only (no CPU fallback exists)")
+    on_device(frames, "frames")
     if contact_pairs.pairs.device != frames.device:
         contact_pairs = contact_pairs.to(frames.device)
     S, M = int(frames.shape[0]), int(frames.shape[1])

@@ -4,12 +4,14 @@ tensors — there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
+from ._args import INT_MAX, check_dims, device_tensor, form_code, int_list, integer, operand, real, to_list
 from ._lib import AGGR, KernelNNParams, MdnoError, check, f32, ptr, raise_on_status, stream_ptr
 
 
@@ -68,23 +70,18 @@ def check_box(box, cutoff: float, what: str = "box"):
     """A periodic box (include/mdno_pbc.h) as three Python floats, or None for `box` None or all zero (no periodic
     axis: the open path).  Three finite lengths >= 0 (0 = open axis), every periodic one >= 2 * cutoff; anything else
     raises MdnoError — on the host, before any device work."""
-    import math
     if box is None:
         return None
-    if torch.is_tensor(box):
-        box = box.detach().cpu().reshape(-1).tolist()
+    box = to_list(box)
     try:
         vals = [float(v) for v in (box if hasattr(box, "__len__") else list(box))]
     except (TypeError, ValueError):
         raise MdnoError(f"{what}={box!r}: expected three lengths (Lx, Ly, Lz)") from None
     if len(vals) != 3:
         raise MdnoError(f"{what} has {len(vals)} entries, expected (Lx, Ly, Lz)")
-    cutoff = float(cutoff)
-    if not (math.isfinite(cutoff) and cutoff >= 0.0):
-        raise MdnoError(f"cutoff {cutoff} is not a finite non-negative number")
+    cutoff = real(cutoff, "cutoff", positive=False)
     for a, L in enumerate(vals):
-        if not (math.isfinite(L) and L >= 0.0):
-            raise MdnoError(f"{what}[{a}] = {L}: a finite length, or 0 for an open axis")
+        real(L, f"{what}[{a}] (a length, or 0 for an open axis)", positive=False)
         if L != 0.0 and not L >= 2.0 * cutoff:
             raise MdnoError(f"{what}[{a}] = {L} < 2 * cutoff = {2.0 * cutoff}: a pair would have more than one image "
                             f"inside the cutoff")
@@ -104,10 +101,8 @@ def radius_graph_pbc(pos: torch.Tensor, n_atoms: int, cutoff: float, box, edge_c
     vals = check_box(box, cutoff)
     if vals is None:
         vals = (0.0, 0.0, 0.0)      # no periodic axis: the open graph, with its attributes
-    if not torch.is_tensor(pos) or not pos.is_cuda:
-        raise MdnoError("radius_graph_pbc: pos must be a GPU tensor (no CPU fallback exists)")
+    pos = device_tensor(pos, "pos", None).reshape(-1, 3)
     lib = _lib.load()
-    pos = f32(pos).reshape(-1, 3)
     R = pos.shape[0]
     if n_atoms <= 0 or R == 0 or R % n_atoms:
         raise MdnoError(f"{R} rows is not a positive multiple of n_atoms={n_atoms}")
@@ -1090,7 +1085,7 @@ def _noise_ids(ids, dev, what: str) -> torch.Tensor:
     t = torch.as_tensor(ids).reshape(-1)
     if t.dtype.is_floating_point or t.dtype == torch.bool:
         raise MdnoError(f"{what} must be integers")
-    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 2 ** 31):
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) > INT_MAX):
         raise MdnoError(f"{what} must lie in [0, 2^31)")
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
@@ -1153,12 +1148,9 @@ def rigid_motions(seed: int, sample_ids, epoch: int, rotate: bool = True, transl
     first_frame f32 [B * n_atoms, 3]: the pivot is every sample's centroid in it; None: the origin.
     last_element < 65 shortens the rejection loop (tests reach the identity fallback with it)."""
     seed, epoch, last_element, translate = _noise_seed(seed), int(epoch), int(last_element), float(translate)
-    if not 2 <= last_element <= _lib.AUGMENT_LAST_ELEMENT:
-        raise MdnoError(f"last_element={last_element} outside [2, {_lib.AUGMENT_LAST_ELEMENT}]")
-    if not 0.0 <= translate < float("inf"):
-        raise MdnoError(f"translate={translate} must be finite and >= 0")
-    if not 0 <= epoch < 2 ** 48:
-        raise MdnoError(f"epoch={epoch} outside [0, 2^48)")
+    integer(last_element, "last_element", 2, _lib.AUGMENT_LAST_ELEMENT)
+    real(translate, "translate", positive=False)
+    integer(epoch, "epoch", 0, 2 ** 48 - 1)
     B = int(torch.as_tensor(sample_ids).numel())
     if first_frame is not None:
         n_atoms = int(n_atoms) if n_atoms is not None else 0
@@ -1192,12 +1184,12 @@ def rigid_apply(quaternion: torch.Tensor, pivot: torch.Tensor, shift: torch.Tens
         raise MdnoError("quaternion [B, 4], pivot [B, 3] and shift [B, 3] must be float64")
     if rows.dim() < 2 or rows.shape[-1] != 3 or rows.shape[-2] != B * N:
         raise MdnoError(f"rows shape {tuple(rows.shape)}: expected [..., B * N, 3] with B * N = {B} * {N}")
-    lib = _lib.load()
     x = f32(rows)
+    if out is not None:
+        operand(out, "out", torch.float32, tuple(x.shape), x.device)
+    lib = _lib.load()
     if out is None:
         out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device:
-        raise MdnoError("out must be a float32 tensor of the shape and device of rows")
     F = x.numel() // max(B * N * 3, 1)
     check(lib.mdnoaug_apply(ptr(quaternion), ptr(pivot), ptr(shift), B, N, F, int(bool(inverse)), ptr(x), ptr(out),
                             stream_ptr(x.device)), "mdnoaug_apply")
@@ -1364,14 +1356,7 @@ FORECAST_FORMS = {"auto": 0, "lds": 1, "tiled": 2}
 
 def _device_frames(t, what: str, ranks) -> torch.Tensor:
     """`t` as a contiguous f32 device tensor [..., N, 3] of one of the given ranks, or MdnoError (no device work)."""
-    if not torch.is_tensor(t):
-        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise MdnoError(f"{what} is a CPU tensor: scoring runs on the GPU only (no CPU fallback exists)")
-    if t.dim() not in ranks or t.shape[-1] != 3:
-        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected [{'..., ' if len(ranks) > 1 else 'S, M, '}N, 3] "
-                        f"of rank {' or '.join(str(r) for r in ranks)}")
-    return f32(t)
+    return device_tensor(t, what, ranks, last=3)
 
 
 def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.0, form: str = "auto", box=None):
@@ -1390,8 +1375,7 @@ def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.
     if tuple(truth.shape) != want:
         raise MdnoError(f"truth shape {tuple(truth.shape)} does not match frames {tuple(frames.shape)}: expected "
                         f"{(S, N, 3)} or {(S, M, N, 3)}")
-    if form not in FORECAST_FORMS:
-        raise MdnoError(f"form {form!r}: expected one of {sorted(FORECAST_FORMS)}")
+    code = form_code(form, FORECAST_FORMS)
     lib = _lib.load()
     dev = frames.device
     scored = S * M > 0 and N > 0
@@ -1402,11 +1386,11 @@ def forecast_score(frames: torch.Tensor, truth: torch.Tensor, cutoff: float = 8.
     counts = torch.empty((S, M, 3), dtype=torch.int64, device=dev) if scored else \
         torch.zeros((S, M, 3), dtype=torch.int64, device=dev)
     first = torch.empty(M, dtype=torch.int32, device=dev)
-    nbytes = lib.mdno_forecast_score_workspace_bytes(S, M, N, FORECAST_FORMS[form])
+    nbytes = lib.mdno_forecast_score_workspace_bytes(S, M, N, code)
     ws = _ws(nbytes, dev) if scored else None
     head = (ptr(frames) if scored else None, ptr(truth) if scored else None, int(truth.dim() == 4), S, M, N, float(cutoff))
     tail = (ptr(mse) if scored else None, ptr(rmsd) if scored else None, ptr(counts) if scored else None,
-            ptr(first) if M else None, FORECAST_FORMS[form], ptr(ws), ws.numel() if scored else 0, stream_ptr(dev))
+            ptr(first) if M else None, code, ptr(ws), ws.numel() if scored else 0, stream_ptr(dev))
     if box is None:
         check(lib.mdno_forecast_score(*head, *tail), "mdno_forecast_score")
     else:
@@ -1419,13 +1403,8 @@ def contact_maps(frames: torch.Tensor, cutoff: float = 8.0, box=None) -> torch.T
     pairs included): the dense map get_contact_map (graph_kernel.py:416-424) builds.  mdno_contact_maps.  `box` =
     (Lx, Ly, Lz): the minimum-image test of include/mdno_pbc.h (mdno_contact_maps_pbc)."""
     box = check_box(box, cutoff)
-    frames = _device_frames(frames, "frames", tuple(range(2, 9)))
+    frames, lead, F, N = _flat_frames(frames)
     lib = _lib.load()
-    N = frames.shape[-2]
-    lead = tuple(frames.shape[:-2])
-    F = 1
-    for d in lead:
-        F *= d
     maps = torch.empty(lead + (N, N), dtype=torch.uint8, device=frames.device)
     empty = F == 0 or N == 0
     if box is None:
@@ -1445,26 +1424,15 @@ MAX_HISTOGRAM_BINS = 4096
 def check_histogram_args(r_max, n_bins, box=None):
     """(r_max as float, n_bins as int, box as check_box returns it) for a pair histogram, or MdnoError: r_max finite and
     > 0, n_bins in 1 .. 4096, every periodic axis of the box >= 2 * r_max (include/mdno_observe.h).  Host only."""
-    import math
-    try:
-        r, nb = float(r_max), int(n_bins)
-    except (TypeError, ValueError):
-        raise MdnoError(f"pair_histogram: r_max={r_max!r}, n_bins={n_bins!r}: expected a number and an integer") from None
-    if not (math.isfinite(r) and r > 0.0):
-        raise MdnoError(f"pair_histogram: r_max {r} is not a finite positive number")
-    if nb != n_bins or not 1 <= nb <= MAX_HISTOGRAM_BINS:
-        raise MdnoError(f"pair_histogram: n_bins={n_bins!r} is outside 1 .. {MAX_HISTOGRAM_BINS}")
-    return r, nb, check_box(box, r)
+    r = real(r_max, "pair_histogram: r_max")
+    return r, integer(n_bins, "pair_histogram: n_bins", 1, MAX_HISTOGRAM_BINS, exact=True), check_box(box, r)
 
 
 def _flat_frames(frames):
     """(frames as contiguous f32 [..., N, 3] on the device, its leading shape, F, N), or MdnoError."""
-    frames = _device_frames(frames, "frames", tuple(range(2, 9)))
+    frames = _device_frames(frames, "frames", range(2, 9))
     lead = tuple(frames.shape[:-2])
-    F = 1
-    for d in lead:
-        F *= d
-    return frames, lead, F, frames.shape[-2]
+    return frames, lead, math.prod(lead), frames.shape[-2]
 
 
 def pair_histogram(frames: torch.Tensor, r_max: float, n_bins: int, box=None, form: str = "auto") -> torch.Tensor:
@@ -1474,16 +1442,15 @@ def pair_histogram(frames: torch.Tensor, r_max: float, n_bins: int, box=None, fo
     nothing is read back.  `form`: "auto" (one workgroup per frame up to 2,048 atoms, pair tiles above), "lds" or
     "tiled" to force one (the same counts)."""
     r_max, n_bins, box = check_histogram_args(r_max, n_bins, box)
-    if form not in FORECAST_FORMS:
-        raise MdnoError(f"form {form!r}: expected one of {sorted(FORECAST_FORMS)}")
+    code = form_code(form, FORECAST_FORMS)
     frames, lead, F, N = _flat_frames(frames)
     lib = _lib.load()
     dev = frames.device
     counts = torch.empty(lead + (n_bins,), dtype=torch.int64, device=dev)
-    nbytes = lib.mdno_pair_histogram_workspace_bytes(F, N, n_bins, FORECAST_FORMS[form])
+    nbytes = lib.mdno_pair_histogram_workspace_bytes(F, N, n_bins, code)
     ws = _ws(nbytes, dev) if nbytes else None
     check(lib.mdno_pair_histogram(ptr(frames) if F * N else None, F, N, r_max, n_bins, box_arg(box) if box else None,
-                                  ptr(counts) if F else None, FORECAST_FORMS[form], ptr(ws), nbytes, stream_ptr(dev)),
+                                  ptr(counts) if F else None, code, ptr(ws), nbytes, stream_ptr(dev)),
           "mdno_pair_histogram")
     return counts
 
@@ -1511,41 +1478,18 @@ def _trajectory(frames, what: str = "frames"):
     frames = _device_frames(frames, what, (3, 4))
     if frames.dim() == 3:
         frames = frames[:, None]
-    S, M, N = frames.shape[:3]
-    if max(S, M, N) >= 2 ** 31:
-        raise MdnoError(f"{what} has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
-    return frames, S, M, N
+    check_dims(what, frames.shape)
+    return (frames, *frames.shape[:3])
 
 
 def check_lags(lags, S: int, span: int = 0, what: str = "displacement_stats"):
     """`lags` as a list of Python ints: 1 .. 1024 integers in 0 .. S - 1 - span (include/mdno_dynamics.h), or MdnoError.
     Host only."""
-    if torch.is_tensor(lags):
-        lags = lags.detach().cpu().reshape(-1).tolist()
-    try:
-        lags = list(lags)
-        vals = [int(v) for v in lags]
-        same = all(v == w for v, w in zip(vals, lags))
-    except (TypeError, ValueError):
-        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
-    if not same:
-        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
-    if not 1 <= len(vals) <= MAX_LAGS:
-        raise MdnoError(f"{what}: {len(vals)} lags, expected 1 .. {MAX_LAGS}")
-    for v in vals:
-        if not 0 <= v <= S - 1 - span:
-            raise MdnoError(f"{what}: lag {v} is outside 0 .. {S - 1 - span} (S={S})")
-    return vals
+    return int_list(lags, what, "lag", (1, MAX_LAGS), 0, S - 1 - span)
 
 
 def check_origin_stride(origin_stride, what: str = "displacement_stats") -> int:
-    try:
-        st = int(origin_stride)
-    except (TypeError, ValueError):
-        raise MdnoError(f"{what}: origin_stride={origin_stride!r}: expected an integer >= 1") from None
-    if st != origin_stride or not 1 <= st < 2 ** 31:
-        raise MdnoError(f"{what}: origin_stride={origin_stride!r}: expected an integer >= 1")
-    return st
+    return integer(origin_stride, f"{what}: origin_stride", 1, exact=True)
 
 
 def n_origins(S: int, lag: int, origin_stride: int = 1, span: int = 0) -> int:
@@ -1565,24 +1509,11 @@ def displacement_stats(frames: torch.Tensor, lags, origin_stride: int = 1, remov
     and atoms, and (n_bins > 0) the histogram of the displacements below r_max (include/mdno_dynamics.h has the rule;
     mdno_displacement_stats).  `remove_com`: the centroid's displacement is subtracted.  Fixed summation order: the same
     bits on every run.  Asynchronous on the current stream, nothing is read back."""
-    import math
     frames, S, M, N = _trajectory(frames)
     stride = check_origin_stride(origin_stride)
-    try:
-        nb = int(n_bins)
-    except (TypeError, ValueError):
-        raise MdnoError(f"displacement_stats: n_bins={n_bins!r}: expected an integer") from None
-    if nb != n_bins or not 0 <= nb <= MAX_HISTOGRAM_BINS:
-        raise MdnoError(f"displacement_stats: n_bins={n_bins!r} is outside 0 .. {MAX_HISTOGRAM_BINS}")
-    r = 0.0
-    if nb > 0:
-        try:
-            r = float(r_max)
-        except (TypeError, ValueError):
-            raise MdnoError(f"displacement_stats: r_max={r_max!r}: expected a number (n_bins={nb})") from None
-        if not (math.isfinite(r) and r > 0.0):
-            raise MdnoError(f"displacement_stats: r_max {r} is not a finite positive number")
-    vals = check_lags(lags, S) if S > 0 else check_lags(lags, 1 << 30)
+    nb = integer(n_bins, "displacement_stats: n_bins", 0, MAX_HISTOGRAM_BINS, exact=True)
+    r = real(r_max, f"displacement_stats: r_max (with n_bins={nb})") if nb > 0 else 0.0
+    vals = check_lags(lags, S if S > 0 else 1 << 30)          # (no frames: any lag list of the right form passes)
     L = len(vals)
     lib = _lib.load()
     dev = frames.device
@@ -1606,7 +1537,7 @@ def velocity_autocorrelation(frames: torch.Tensor, lags, origin_stride: int = 1,
     what = "velocity_autocorrelation"
     frames, S, M, N = _trajectory(frames)
     stride = check_origin_stride(origin_stride, what)
-    vals = check_lags(lags, S, 1, what) if S > 0 else check_lags(lags, 1 << 30, 1, what)
+    vals = check_lags(lags, S if S > 0 else 1 << 30, 1, what)
     L = len(vals)
     lib = _lib.load()
     dev = frames.device
@@ -1662,14 +1593,12 @@ def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto"
     S, M, N, _ = frames.shape
     if tuple(truth.shape) != (S, N, 3):
         raise MdnoError(f"truth shape {tuple(truth.shape)} does not match frames {tuple(frames.shape)}: expected {(S, N, 3)}")
-    if form not in ENSEMBLE_FORMS:
-        raise MdnoError(f"form {form!r}: expected one of {sorted(ENSEMBLE_FORMS)}")
+    code = form_code(form, ENSEMBLE_FORMS)
     if not 1 <= M <= MAX_ENSEMBLE_MEMBERS:
         raise MdnoError(f"ensemble_score: {M} members, expected 1 .. {MAX_ENSEMBLE_MEMBERS}")
     if form == "registers" and M > MAX_REGISTER_MEMBERS:
         raise MdnoError(f"ensemble_score: form 'registers' holds at most {MAX_REGISTER_MEMBERS} members, got {M}")
-    if max(S, N) >= 2 ** 31:
-        raise MdnoError(f"frames has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
+    check_dims("frames", frames.shape)
     lib = _lib.load()
     dev = frames.device
     sums = torch.empty((S, 4), dtype=torch.float64, device=dev)
@@ -1681,7 +1610,7 @@ def ensemble_score(frames: torch.Tensor, truth: torch.Tensor, form: str = "auto"
     nbytes = lib.mdnoens_score_workspace_bytes(S, M, N)
     ws = _ws(nbytes, dev)
     check(lib.mdnoens_score(ptr(frames) if N else None, ptr(truth) if N else None, S, M, N, ptr(sums), ptr(rank_hist),
-                            ptr(n_invalid), ptr(n_ties), ENSEMBLE_FORMS[form], ptr(ws), nbytes, stream_ptr(dev)),
+                            ptr(n_invalid), ptr(n_ties), code, ptr(ws), nbytes, stream_ptr(dev)),
           "mdnoens_score")
     return sums, rank_hist, n_invalid, n_ties
 
@@ -1756,19 +1685,8 @@ def covariance_row_split(K: int, D: int, lag: int):
     return L, -(-K // L)
 
 
-def _device_matrix(t, what: str, ranks, dtype=torch.float32) -> torch.Tensor:
-    """`t` as a contiguous device tensor of `dtype` and one of the given ranks, or MdnoError (no device work)."""
-    if not torch.is_tensor(t):
-        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise MdnoError(f"{what} is a CPU tensor: essential dynamics runs on the GPU only (no CPU fallback exists)")
-    if t.dim() not in ranks:
-        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected rank {' or '.join(str(r) for r in ranks)}")
-    return (t if t.dtype == dtype else t.to(dtype)).contiguous()
-
-
 def _vector_f64(t, what: str, D: int, dev) -> torch.Tensor:
-    t = _device_matrix(t, what, (1,), torch.float64)
+    t = device_tensor(t, what, (1,), dtype=torch.float64)
     if t.shape[0] != D or t.device != dev:
         raise MdnoError(f"{what} has shape {tuple(t.shape)} on {t.device}: expected [{D}] on {dev}")
     return t
@@ -1802,10 +1720,9 @@ def feature_sums(x: torch.Tensor):
     """x f32 [R, D] (device) -> (sum f64 [D], n_invalid i64 [1]): the column sums over the rows in a fixed order and the
     number of rows that hold a NaN or Inf (such a row makes the columns it touches NaN); mdnopca_feature_sums.  The mean
     is sum / R.  Asynchronous on the current stream, nothing is read back."""
-    x = _device_matrix(x, "x", (2,))
+    x = device_tensor(x, "x", (2,))
     R, D = x.shape
-    if D >= 2 ** 31:
-        raise MdnoError(f"x has shape {tuple(x.shape)}: D exceeds 2^31 - 1")
+    check_dims("x", x.shape, (D,))
     lib = _lib.load()
     dev = x.device
     total = torch.empty(D, dtype=torch.float64, device=dev)
@@ -1817,13 +1734,11 @@ def feature_sums(x: torch.Tensor):
 
 def _features(x, what: str = "x"):
     """(x as contiguous f32 [S, M, D] on the device, S, M, D); [F, D] is M = 1."""
-    x = _device_matrix(x, what, (2, 3))
+    x = device_tensor(x, what, (2, 3))
     if x.dim() == 2:
         x = x[:, None]
-    S, M, D = x.shape
-    if max(S, M, D) >= 2 ** 31:
-        raise MdnoError(f"{what} has shape {tuple(x.shape)}: a dimension exceeds 2^31 - 1")
-    return x, S, M, D
+    check_dims(what, x.shape)
+    return (x, *x.shape)
 
 
 def feature_covariance(x: torch.Tensor, mean: torch.Tensor, lag: int = 0) -> torch.Tensor:
@@ -1833,8 +1748,7 @@ def feature_covariance(x: torch.Tensor, mean: torch.Tensor, lag: int = 0) -> tor
     centred in fp64 on the way in, no fp64 copy of x.  lag 0 is bitwise symmetric; lag >= S gives zeros.  Fixed summation
     order: the same bits on every run.  Asynchronous on the current stream."""
     x, S, M, D = _features(x)
-    if isinstance(lag, bool) or not isinstance(lag, int) or lag < 0 or lag >= 2 ** 31:
-        raise MdnoError(f"lag {lag!r}: expected an integer >= 0")
+    lag = integer(lag, "lag", 0)
     mean = _vector_f64(mean, "mean", D, x.device)
     lib = _lib.load()
     dev = x.device
@@ -1853,12 +1767,11 @@ def project_features(x: torch.Tensor, mean: torch.Tensor, vectors: torch.Tensor)
     """x f32 [R, D], mean f64 [D], vectors f64 [D, k] (1 <= k <= PCA_MAX_COMPONENTS) -> P f64 [R, k],
     P[r, c] = sum_a (x[r, a] - mean[a]) vectors[a, c], one running fp64 sum in ascending a (mdnopca_project).
     Asynchronous on the current stream."""
-    x = _device_matrix(x, "x", (2,))
+    x = device_tensor(x, "x", (2,))
     R, D = x.shape
-    if D >= 2 ** 31:
-        raise MdnoError(f"x has shape {tuple(x.shape)}: D exceeds 2^31 - 1")
+    check_dims("x", x.shape, (D,))
     mean = _vector_f64(mean, "mean", D, x.device)
-    vectors = _device_matrix(vectors, "vectors", (2,), torch.float64)
+    vectors = device_tensor(vectors, "vectors", (2,), dtype=torch.float64)
     if vectors.shape[0] != D or vectors.device != x.device:
         raise MdnoError(f"vectors has shape {tuple(vectors.shape)} on {vectors.device}: expected [{D}, k] on {x.device}")
     k = vectors.shape[1]
@@ -1889,22 +1802,13 @@ MSM_MAX_LAGS = MAX_LAGS             # MDNO_MSM_MAX_LAGS
 
 def _msm_matrix(t, what: str):
     """(`t` as a contiguous device matrix [R, D] of f32 or f64 — anything else is converted to f32 —, its dtype code)."""
-    if not torch.is_tensor(t):
-        raise MdnoError(f"{what} must be a torch tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise MdnoError(f"{what} is a CPU tensor: the Markov-model kernels run on the GPU only (no CPU fallback exists)")
-    if t.dim() != 2:
-        raise MdnoError(f"{what} has shape {tuple(t.shape)}, expected rank 2")
-    if t.shape[1] >= 2 ** 31:
-        raise MdnoError(f"{what} has shape {tuple(t.shape)}: D exceeds 2^31 - 1")
-    dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
-    return (t if t.dtype == dtype else t.to(dtype)).contiguous(), 1 if dtype == torch.float64 else 0
+    t = device_tensor(t, what, (2,), dtype="float")
+    check_dims(what, t.shape, t.shape[1:])
+    return t, int(t.dtype == torch.float64)
 
 
 def _msm_states(k, what: str, low: int = 1) -> int:
-    if isinstance(k, bool) or not isinstance(k, int) or not low <= k <= MSM_MAX_STATES:
-        raise MdnoError(f"{what} = {k!r}: expected an integer in {low} .. {MSM_MAX_STATES}")
-    return k
+    return integer(k, what, low, MSM_MAX_STATES)
 
 
 def assign_features(x: torch.Tensor, centres: torch.Tensor, origin: Optional[torch.Tensor] = None, labels: bool = True,
@@ -1953,8 +1857,7 @@ def kcenters(x: torch.Tensor, k: int, first: int = 0):
     k = _msm_states(k, "kcenters: k")
     if k > R:
         raise MdnoError(f"kcenters: k = {k} centres of {R} rows")
-    if isinstance(first, bool) or not isinstance(first, int) or not 0 <= first < R:
-        raise MdnoError(f"kcenters: first = {first!r}, expected an integer in 0 .. {R - 1}")
+    first = integer(first, "kcenters: first", 0, R - 1)
     lib = _lib.load()
     dev = x.device
     index = torch.empty(k, dtype=torch.int64, device=dev)
@@ -1973,11 +1876,7 @@ def centroid_sums(x: torch.Tensor, label: torch.Tensor, k: int):
     x, code = _msm_matrix(x, "x")
     R, D = x.shape
     k = _msm_states(k, "centroid_sums: k")
-    if not torch.is_tensor(label) or not label.is_cuda or label.device != x.device:
-        raise MdnoError("label is a CPU tensor or on another device than x: expected an int32 device tensor")
-    if label.dtype != torch.int32 or label.shape != (R,):
-        raise MdnoError(f"label is {label.dtype} {tuple(label.shape)}: expected int32 [{R}]")
-    label = label.contiguous()
+    label = operand(label, "label", torch.int32, (R,), x.device)
     lib = _lib.load()
     dev = x.device
     sums = torch.empty((k, D), dtype=torch.float64, device=dev)
@@ -1989,22 +1888,7 @@ def centroid_sums(x: torch.Tensor, label: torch.Tensor, k: int):
 
 def check_msm_lags(lags, what: str = "transition_counts"):
     """`lags` as a list of Python ints: 1 .. MAX_LAGS integers >= 1, or MdnoError.  Host only."""
-    if torch.is_tensor(lags):
-        lags = lags.detach().cpu().reshape(-1).tolist()
-    try:
-        lags = list(lags)
-        vals = [int(v) for v in lags]
-        same = all(v == w for v, w in zip(vals, lags))
-    except (TypeError, ValueError):
-        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
-    if not same:
-        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
-    if not 1 <= len(vals) <= MSM_MAX_LAGS:
-        raise MdnoError(f"{what}: {len(vals)} lags, expected 1 .. {MSM_MAX_LAGS}")
-    for v in vals:
-        if not 1 <= v < 2 ** 31:
-            raise MdnoError(f"{what}: lag {v} is below 1 (or exceeds 2^31 - 1)")
-    return vals
+    return int_list(lags, what, "lag", (1, MSM_MAX_LAGS), 1, INT_MAX)
 
 
 def transition_counts(label: torch.Tensor, n_states: int, lags, pooled: bool = False):
@@ -2012,20 +1896,16 @@ def transition_counts(label: torch.Tensor, n_states: int, lags, pooled: bool = F
     member (or pooled over the members) the number of origins t with label[t] = from and label[t + lag] = to, sliding
     window; a pair with a label outside 0 .. n - 1 is counted in n_skipped instead (mdnomsm_transition_counts).  Integer
     counts: exact.  Asynchronous on the current stream."""
-    if not torch.is_tensor(label):
-        raise MdnoError(f"label must be a torch tensor, got {type(label).__name__}")
-    if not label.is_cuda:
-        raise MdnoError("label is a CPU tensor: the Markov-model kernels run on the GPU only (no CPU fallback exists)")
+    label = device_tensor(label, "label", (1, 2), dtype=None)
+    if label.dtype != torch.int32:
+        raise MdnoError(f"label is {label.dtype} {tuple(label.shape)}: expected int32 [S, M]")
     if label.dim() == 1:
         label = label[:, None]
-    if label.dim() != 2 or label.dtype != torch.int32:
-        raise MdnoError(f"label is {label.dtype} {tuple(label.shape)}: expected int32 [S, M]")
     S, M = label.shape
-    if S >= 2 ** 31 or M > 65535:
+    if S > INT_MAX or M > 65535:
         raise MdnoError(f"label has shape {tuple(label.shape)}: expected S < 2^31 and M <= 65535")
     n = _msm_states(n_states, "transition_counts: n_states")
     vals = check_msm_lags(lags)
-    label = label.contiguous()
     lib = _lib.load()
     dev = label.device
     Mo = 1 if pooled else M
@@ -2060,15 +1940,9 @@ def _ic_indices(t, width: int, what: str, dev) -> torch.Tensor:
     """An index array as contiguous int32 [n, width] on `dev` (None: no entries)."""
     if t is None:
         return torch.zeros((0, width), dtype=torch.int32, device=dev)
-    if not torch.is_tensor(t):
-        raise MdnoError(f"{what} must be a torch tensor or None, got {type(t).__name__}")
-    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != width:
-        raise MdnoError(f"{what} is {t.dtype} {tuple(t.shape)}: expected int32 [n, {width}]")
-    if t.device != dev:
-        raise MdnoError(f"{what} is on {t.device}, the frames are on {dev}")
-    if t.shape[0] >= 2 ** 31:
-        raise MdnoError(f"{what} has {t.shape[0]} rows: more than 2^31 - 1")
-    return t.to(torch.int32).contiguous()
+    t = operand(t, what, (torch.int32, torch.int64), (None, width), dev)
+    check_dims(what, t.shape)
+    return t.to(torch.int32)
 
 
 def internal_features(frames: torch.Tensor, pairs=None, triples=None, quads=None, box=None, radians: bool = False,
@@ -2080,8 +1954,7 @@ def internal_features(frames: torch.Tensor, pairs=None, triples=None, quads=None
     open axis: bond vectors by the minimum image (no cutoff is tested).  An index outside 0 .. N - 1 gives NaN and reads
     nothing.  `form`: "auto" (frames staged in LDS up to IC_LDS_ATOMS atoms), "lds" or "global" to force one (the same
     bits).  Asynchronous on the current stream, nothing is read back."""
-    if form not in IC_FORMS:
-        raise MdnoError(f"form {form!r}: expected one of {sorted(IC_FORMS)}")
+    code = form_code(form, IC_FORMS)
     if dtype not in (torch.float32, torch.float64):
         raise MdnoError(f"dtype {dtype}: expected torch.float32 or torch.float64")
     box = check_box(box, 0.0)
@@ -2092,13 +1965,12 @@ def internal_features(frames: torch.Tensor, pairs=None, triples=None, quads=None
     pairs, triples, quads = (_ic_indices(t, w, n, dev) for t, w, n in ((pairs, 2, "pairs"), (triples, 3, "triples"), (quads, 4, "quads")))
     P, A, T = pairs.shape[0], triples.shape[0], quads.shape[0]
     D = P + A + (1 if radians else 2) * T
-    if D >= 2 ** 31:
-        raise MdnoError(f"{D} feature columns: more than 2^31 - 1")
+    check_dims("the feature tensor", lead + (D,), (D,))
     lib = _lib.load()
     out = torch.empty(lead + (D,), dtype=dtype, device=dev)
     check(lib.mdnoic_features(ptr(frames) if F * N else None, F, N, ptr(pairs) if P else None, P, ptr(triples) if A else None, A,
                               ptr(quads) if T else None, T, box_arg(box) if box else None, _lib.INTERNAL_RADIANS if radians else 0,
-                              _lib.INTERNAL_DTYPES[str(dtype).split(".")[-1]], ptr(out) if F * D else None, IC_FORMS[form],
+                              _lib.INTERNAL_DTYPES[str(dtype).split(".")[-1]], ptr(out) if F * D else None, code,
                               stream_ptr(dev)), "mdnoic_features")
     return out
 
@@ -2127,8 +1999,7 @@ def internal_features_bwd(frames: torch.Tensor, g: torch.Tensor, pairs, triples,
     the rule of include/mdno_internal_grad.h (mdnoicg_features_bwd).  An item whose g is exactly zero is skipped; every
     element is written.  `form` as in `internal_features` (the same bits).  Asynchronous on the current stream, nothing is
     read back."""
-    if form not in IC_FORMS:
-        raise MdnoError(f"form {form!r}: expected one of {sorted(IC_FORMS)}")
+    code = form_code(form, IC_FORMS)
     if dtype not in (torch.float32, torch.float64):
         raise MdnoError(f"dtype {dtype}: expected torch.float32 or torch.float64")
     box = check_box(box, 0.0)
@@ -2141,34 +2012,27 @@ def internal_features_bwd(frames: torch.Tensor, g: torch.Tensor, pairs, triples,
     D = P + A + 2 * T
     if P + A + T >= ICG_MAX_ITEMS:
         raise MdnoError(f"{P + A + T} index tuples: the incidence table holds fewer than 2^29")
-    if not torch.is_tensor(g) or g.dtype not in (torch.float32, torch.float64) or g.device != dev or tuple(g.shape) != lead + (D,):
-        what = f"{g.dtype} {tuple(g.shape)} on {g.device}" if torch.is_tensor(g) else type(g).__name__
-        raise MdnoError(f"g is {what}: expected float32 or float64 {lead + (D,)} on {dev}")
-    for t, n, what in ((atom_ptr, N + 1, "atom_ptr"), (inc, None, "inc")):
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):
-            raise MdnoError(f"{what}: expected an int32 vector{'' if n is None else f' of {n} entries'} on {dev}")
-    g, atom_ptr, inc = g.contiguous(), atom_ptr.contiguous(), inc.contiguous()
+    g = operand(g, "g", (torch.float32, torch.float64), lead + (D,), dev)
+    atom_ptr = operand(atom_ptr, "atom_ptr", torch.int32, (N + 1,), dev)
+    inc = operand(inc, "inc", torch.int32, (None,), dev)
     n_inc = inc.shape[0]
     lib = _lib.load()
     grad = torch.empty(lead + (N, 3), dtype=dtype, device=dev)
-    code = lambda t: _lib.INTERNAL_DTYPES[str(t).split(".")[-1]]
+    dtype_code = lambda t: _lib.INTERNAL_DTYPES[str(t).split(".")[-1]]
     check(lib.mdnoicg_features_bwd(ptr(frames) if F * N else None, F, N, ptr(pairs) if P else None, P, ptr(triples) if A else None, A,
                                    ptr(quads) if T else None, T, ptr(atom_ptr), ptr(inc) if n_inc else None, n_inc,
-                                   box_arg(box) if box else None, 0, ptr(g) if F * D else None, code(g.dtype),
-                                   ptr(grad) if F * N else None, code(dtype), IC_FORMS[form], stream_ptr(dev)), "mdnoicg_features_bwd")
+                                   box_arg(box) if box else None, 0, ptr(g) if F * D else None, dtype_code(g.dtype),
+                                   ptr(grad) if F * N else None, dtype_code(dtype), code, stream_ptr(dev)), "mdnoicg_features_bwd")
     return grad
 
 
 def check_column_ranges(lo, hi, n_bins, D: int):
     """(lo, hi as lists of Python floats — one entry: a range shared by all columns, else D —, n_bins as int) for a column
     histogram, or MdnoError: finite, hi > lo, n_bins in 1 .. IC_MAX_BINS.  Host only."""
-    import math
-    if isinstance(n_bins, bool) or not isinstance(n_bins, int) or not 1 <= n_bins <= IC_MAX_BINS:
-        raise MdnoError(f"column_histogram: n_bins={n_bins!r} is outside 1 .. {IC_MAX_BINS}")
+    n_bins = integer(n_bins, "column_histogram: n_bins", 1, IC_MAX_BINS)
     vals = []
     for name, v in (("lo", lo), ("hi", hi)):
-        if torch.is_tensor(v):
-            v = v.detach().cpu().reshape(-1).tolist()
+        v = to_list(v)
         try:
             v = [float(e) for e in v] if hasattr(v, "__len__") or hasattr(v, "__iter__") else [float(v)]
         except (TypeError, ValueError):
@@ -2192,8 +2056,8 @@ def column_histogram(x: torch.Tensor, lo, hi, n_bins: int, groups: int = 1):
     counts: exact.  Asynchronous on the current stream."""
     x, code = _msm_matrix(x, "x")
     R, width = x.shape
-    if isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups <= 65535 or width % groups:
-        raise MdnoError(f"column_histogram: groups={groups!r} for {width} columns: expected 1 .. 65535 groups of equally many columns")
+    if width % integer(groups, "column_histogram: groups", 1, 65535):
+        raise MdnoError(f"column_histogram: groups={groups!r} for {width} columns: expected groups of equally many columns")
     D = width // groups
     lo, hi, n_bins = check_column_ranges(lo, hi, n_bins, D)
     lib = _lib.load()
@@ -2227,32 +2091,19 @@ def check_constraint_table(pairs, lo, hi, colour_ptr, weights, n_atoms: int, dev
     """The coloured table of a projection as the C ABI takes it: pairs i32 [C, 2], lo / hi f64 [C], colour_ptr i32
     [n_colours + 1], weights f32 [n_atoms] or None, all contiguous on `dev`; MdnoError otherwise.  Shapes, dtypes and devices
     only: the values were validated on the host when the table was made (forecast.DistanceConstraints)."""
-    if not torch.is_tensor(pairs) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.device != dev:
-        raise MdnoError(f"pairs: expected int32 [C, 2] on {dev}")
+    pairs = operand(pairs, "pairs", torch.int32, (None, 2), dev)
     n_c = int(pairs.shape[0])
     if n_c > CST_MAX_CONSTRAINTS:
         raise MdnoError(f"{n_c} constraints: more than {CST_MAX_CONSTRAINTS}")
-    for t, what in ((lo, "lo"), (hi, "hi")):
-        if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != (n_c,) or t.device != dev:
-            raise MdnoError(f"{what}: expected float64 [{n_c}] on {dev}")
-    if not torch.is_tensor(colour_ptr) or colour_ptr.dtype != torch.int32 or colour_ptr.dim() != 1 or colour_ptr.shape[0] < 1 or \
-            colour_ptr.device != dev:
-        raise MdnoError(f"colour_ptr: expected int32 [n_colours + 1] on {dev}")
-    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (n_atoms,)
-                                or weights.device != dev):
-        raise MdnoError(f"weights: expected float32 [{n_atoms}] on {dev} or None")
-    return (pairs.contiguous(), lo.contiguous(), hi.contiguous(), colour_ptr.contiguous(),
-            None if weights is None else weights.contiguous())
+    lo, hi = operand(lo, "lo", torch.float64, (n_c,), dev), operand(hi, "hi", torch.float64, (n_c,), dev)
+    colour_ptr = operand(colour_ptr, "colour_ptr", torch.int32, (None,), dev)
+    if colour_ptr.shape[0] < 1:
+        raise MdnoError("colour_ptr is empty: expected int32 [n_colours + 1]")
+    return pairs, lo, hi, colour_ptr, operand(weights, "weights", torch.float32, (n_atoms,), dev, optional=True)
 
 
 def check_projection_args(iterations, tol):
-    import math
-    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations < 2 ** 31:
-        raise MdnoError(f"iterations={iterations!r}: expected an integer >= 0")
-    tol = float(tol)
-    if math.isnan(tol) or tol < 0.0:
-        raise MdnoError(f"tol={tol}: expected a number >= 0")
-    return iterations, tol
+    return integer(iterations, "iterations", 0), real(tol, "tol", positive=False, finite=False)
 
 
 def project_constraints(frames: torch.Tensor, pairs: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, colour_ptr: torch.Tensor,
@@ -2274,9 +2125,8 @@ def project_constraints(frames: torch.Tensor, pairs: torch.Tensor, lo: torch.Ten
     n_c, n_colours = int(pairs.shape[0]), int(colour_ptr.shape[0]) - 1
     if out is None:
         out = torch.empty(lead + (N, 3), dtype=torch.float32, device=dev)
-    elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != lead + (N, 3) or \
-            not out.is_contiguous():
-        raise MdnoError(f"out: expected a contiguous float32 {lead + (N, 3)} on {dev}")
+    elif operand(out, "out", torch.float32, lead + (N, 3), dev) is not out:          # (a contiguous tensor comes back as itself)
+        raise MdnoError(f"out has strides {out.stride()}: expected a contiguous tensor")
     elif out.data_ptr() != frames.data_ptr() and F * N and \
             out.data_ptr() < frames.data_ptr() + frames.numel() * 4 and frames.data_ptr() < out.data_ptr() + out.numel() * 4:
         raise MdnoError("out overlaps frames without being frames")
@@ -2301,24 +2151,15 @@ CM_MAX_LAGS = _lib.CONTACTS_MAX_LAGS
 def check_contact_args(threshold, box=None, block_len=1, what: str = "pair_statistics"):
     """(threshold as float, box as check_box returns it, block_len as int) or MdnoError: threshold finite and > 0, every
     periodic axis of the box >= 2 * threshold, block_len an integer >= 1 (include/mdno_contacts.h).  Host only."""
-    import math
-    try:
-        cut = float(threshold)
-    except (TypeError, ValueError):
-        raise MdnoError(f"{what}: threshold={threshold!r}: expected a number") from None
-    if not (math.isfinite(cut) and cut > 0.0):
-        raise MdnoError(f"{what}: threshold {cut} is not a finite positive number")
-    if isinstance(block_len, bool) or not isinstance(block_len, int) or not 1 <= block_len < 2 ** 31:
-        raise MdnoError(f"{what}: block_len={block_len!r}: expected an integer >= 1")
+    cut = real(threshold, f"{what}: threshold")
+    block_len = integer(block_len, f"{what}: block_len", 1)
     return cut, check_box(box, cut), block_len
 
 
 def _contact_frames(frames, what: str):
     frames = _device_frames(frames, "frames", (4,))
-    S, M, N = frames.shape[:3]
-    if max(S, M, N) >= 2 ** 31:
-        raise MdnoError(f"{what}: frames has shape {tuple(frames.shape)}: a dimension exceeds 2^31 - 1")
-    return frames, S, M, N
+    check_dims(f"{what}: frames", frames.shape)
+    return (frames, *frames.shape[:3])
 
 
 def pair_statistics(frames: torch.Tensor, threshold: float = 8.0, box=None, block_len: int = 64, moments: bool = True):
@@ -2356,9 +2197,7 @@ def contact_bits(frames: torch.Tensor, pairs: torch.Tensor, cut: torch.Tensor, c
     dev = frames.device
     pairs = _ic_indices(pairs, 2, "pairs", dev)
     P = pairs.shape[0]
-    if not torch.is_tensor(cut) or cut.dtype != torch.float64 or tuple(cut.shape) != (P,) or cut.device != dev:
-        raise MdnoError(f"cut: expected float64 [{P}] on {dev}")
-    cut = cut.contiguous()
+    cut = operand(cut, "cut", torch.float64, (P,), dev)
     lib = _lib.load()
     Wd = -(-S // 64)
     bits = torch.empty((M, P, Wd), dtype=torch.int64, device=dev)
@@ -2373,22 +2212,7 @@ def contact_bits(frames: torch.Tensor, pairs: torch.Tensor, cut: torch.Tensor, c
 
 def check_contact_lags(lags, S: int, what: str = "contact_correlation"):
     """`lags` as a list of Python ints: at most CM_MAX_LAGS integers in 0 .. S - 1, or MdnoError.  Host only."""
-    if torch.is_tensor(lags):
-        lags = lags.detach().cpu().reshape(-1).tolist()
-    try:
-        lags = list(lags)
-        vals = [int(v) for v in lags]
-        same = all(v == w for v, w in zip(vals, lags))
-    except (TypeError, ValueError):
-        raise MdnoError(f"{what}: lags={lags!r}: expected a sequence of integers") from None
-    if not same:
-        raise MdnoError(f"{what}: lags={list(lags)!r}: expected integers")
-    if len(vals) > CM_MAX_LAGS:
-        raise MdnoError(f"{what}: {len(vals)} lags, expected at most {CM_MAX_LAGS}")
-    for v in vals:
-        if not 0 <= v < S:
-            raise MdnoError(f"{what}: lag {v} is outside 0 .. {S - 1} (S={S})")
-    return vals
+    return int_list(lags, what, "lag", (0, CM_MAX_LAGS), 0, S - 1)
 
 
 def contact_correlation(bits: torch.Tensor, S: int, lags):
@@ -2396,16 +2220,11 @@ def contact_correlation(bits: torch.Tensor, S: int, lags):
     for every member, pair and lag the steps t < S - lag at which the pair is in contact, and those at which it is in
     contact at t and at t + lag (include/mdno_contacts.h (c); mdnocm_contact_correlation).  Integers, exact.  Asynchronous
     on the current stream, nothing is read back."""
-    if not torch.is_tensor(bits):
-        raise MdnoError(f"bits must be a torch tensor, got {type(bits).__name__}")
-    if not bits.is_cuda:
-        raise MdnoError("bits is a CPU tensor: the contact kernels run on the GPU only (no CPU fallback exists)")
-    if isinstance(S, bool) or not isinstance(S, int) or not 0 <= S < 2 ** 31:
-        raise MdnoError(f"contact_correlation: S={S!r}: expected an integer >= 0")
+    bits = device_tensor(bits, "bits", None, dtype=None)
+    S = integer(S, "contact_correlation: S", 0)
     if bits.dtype != torch.int64 or bits.dim() != 3 or bits.shape[2] != -(-S // 64):
         raise MdnoError(f"bits is {bits.dtype} {tuple(bits.shape)}: expected int64 [M, P, {-(-S // 64)}] for S={S}")
     vals = check_contact_lags(lags, S)
-    bits = bits.contiguous()
     M, P, _ = bits.shape
     L = len(vals)
     lib = _lib.load()

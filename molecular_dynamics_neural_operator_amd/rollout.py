@@ -19,6 +19,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib, forecast, ops
+from ._args import INT_MAX
 from ._lib import MdnoError, STATUS_EDGE_OVERFLOW, check, f32, ptr, raise_on_status, require_gpu
 
 
@@ -264,7 +265,7 @@ class RolloutEngine(_ProducedFrames):
         if not (0.0 <= self.noise_sigma < float("inf")) or not 0 <= self.noise_seed < 2 ** 64:
             raise MdnoError(f"noise_sigma={noise_sigma} must be finite and >= 0, noise_seed={noise_seed} in [0, 2^64)")
         ids = list(range(self.M)) if member_ids is None else [int(i) for i in member_ids]
-        if len(ids) != self.M or any(not 0 <= i < 2 ** 31 for i in ids):
+        if len(ids) != self.M or any(not 0 <= i <= INT_MAX for i in ids):
             raise MdnoError(f"member_ids: expected {self.M} ids in [0, 2^31), got {ids[:8]}{'..' if len(ids) > 8 else ''}")
         self.member_ids = ids
         self._member_ids_dev = None      # int32 [M] on the device, made when noise is on (the plan keeps its address)

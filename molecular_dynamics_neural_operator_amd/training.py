@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from ._args import INT_MAX
 from ._lib import MdnoError
 from .dataset import PairData
 from .graph_kernel import LpLoss
@@ -503,7 +504,7 @@ def draw_motions(batch: PairData, augment: RigidAugment, epoch: int = 0) -> Rigi
     # the indices go up through pinned memory without blocking the host (a pageable source is copied synchronously:
     # measured, that stall cost a training step more than the five launches)
     ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
-    if ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31):
+    if ids.size and (ids.min() < 0 or ids.max() > INT_MAX):
         raise MdnoError("sample_ids must lie in [0, 2^31)")
     if x.is_cuda:
         ids = torch.from_numpy(ids.astype(np.int32)).pin_memory().to(x.device, non_blocking=True)

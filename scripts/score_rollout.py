@@ -225,8 +225,8 @@ def main() -> None:
         far = (torch.arange(N, device=dev)[:, None] - torch.arange(N, device=dev)[None, :]).abs() >= a.contacts
         native_map = (tru.probability() >= 0.5) & far                                # [1, N, N]
         own_map = (run.probability() >= 0.5) & far                                   # [M, N, N]
-        kept = fc._nan_ratio((own_map & native_map).sum((1, 2)), native_map.sum((1, 2)).expand(M))
-        spurious = fc._nan_ratio((own_map & ~native_map).sum((1, 2)), own_map.sum((1, 2)))
+        kept = fc._ratio((own_map & native_map).sum((1, 2)), native_map.sum((1, 2)).expand(M))
+        spurious = fc._ratio((own_map & ~native_map).sum((1, 2)), own_map.sum((1, 2)))
         native = fc.ContactPairs.from_statistics(tru, 0.5, a.contacts)              # the one read-back
         q_run, q_truth = eng.contact_series(native), fc.contact_series(truth[:, None], native, box=eng.box)
         some = [l for l in (0, 1, 2, 5, 10, 20, 50, 100, 200, 500) if l < S]

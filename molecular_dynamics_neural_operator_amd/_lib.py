@@ -300,6 +300,18 @@ CONTACTS_SIGNATURES = {
     "mdnocm_contact_correlation": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
 }
 
+# include/mdno_surface.h: Shrake-Rupley counts of exposed sphere points per atom and frame (the solvent-accessible surface).
+# Prefix mdnosa_.  `box` is a HOST pointer to three doubles; `R` and the point table `U` lie on the device.  The forms are
+# those of mdno.h (ops.FORECAST_FORMS).
+SURFACE_MAX_POINTS = 1024           # MDNOSA_MAX_POINTS
+SURFACE_STAGED_ATOMS = 2048         # MDNOSA_STAGED_ATOMS: the largest N whose frame is staged in LDS
+SURFACE_TILE = 256                  # MDNOSA_TILE
+SURFACE_CHUNK = 64                  # MDNOSA_CHUNK
+SURFACE_SIGNATURES = {
+    "mdnosa_workspace_bytes": (_SZ, [_L, _I, _I, _I]),
+    "mdnosa_exposed_points": (_I, [_P, _L, _I, _P, _P, _I, _P, _D, _P, _I, _P, _SZ, _P]),
+}
+
 # THE REGISTRY of the C ABI: every header under include/ with its table.  The contract, for all of them alike:
 #   * a header's declarations are its table's names, with the table's arities, and every one is exported by libmdno.so;
 #     the library exports no other name that starts with mdno;
@@ -329,6 +341,7 @@ TABLES = (
     ("mdno_pbc_train.h", PBC_TRAIN_SIGNATURES),
     ("mdno_contacts.h", CONTACTS_SIGNATURES),
     ("mdno_augment.h", AUGMENT_SIGNATURES),
+    ("mdno_surface.h", SURFACE_SIGNATURES),
 )
 
 

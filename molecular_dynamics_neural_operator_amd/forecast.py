@@ -117,6 +117,16 @@ steps, one bit per (member, pair, step); include/mdno_contacts.h has the rule):
     cs.fraction()                                               # Q(t), f64 [S, M]
     cc = cs.correlation()                                       # ContactCorrelation over ~33 log-spaced lags
     cc.survival(), cc.lifetime(dt)                              # f64 [M, L]: P(contact at t + lag | contact at t); f64 [M]
+
+Solvent-accessible surface.  A chain can stay connected, keep its contact map and its radius of gyration and still turn its
+core inside out: which SIDE of an atom is covered is asked of Shrake and Rupley's count of exposed sphere points per atom
+(csrc/surface.hip: one wave per atom, neighbours compacted by ballot, one buried bit per point; include/mdno_surface.h has the
+rule):
+
+    sp = Spheres(radii, probe=1.4, n_points=96)                 # expanded radii, the golden-section spiral, reach — on the host
+    area = eng.surface_area(sp)                                 # SurfaceArea: counts i32 [S, M, N], -1 for a non-finite atom
+    area.total(), area.per_group(residue, n_residues)           # f64 [S, M], [S, M, n_residues]: 4 pi R^2 count / P summed
+    area.difference(surface_area(truth[:, None], sp))           # f64 [M]: RMS over the atoms of the mean burial against the truth's
 """
 from __future__ import annotations
 
@@ -1885,6 +1895,185 @@ def contact_series(frames: torch.Tensor, contact_pairs: ContactPairs, box=None) 
                              torch.zeros((S, M), dtype=torch.int32, device=frames.device), S, contact_pairs)
     bits, per_frame = ops.contact_bits(frames, contact_pairs.pairs, contact_pairs.cut, contact_pairs.cut_max, box)
     return ContactSeries(bits, per_frame, S, contact_pairs)
+
+
+# ------------------------------------------------------------------------------------------------
+# Solvent-accessible surface (csrc/surface.hip, include/mdno_surface.h has the rule)
+def golden_spiral(n_points: int) -> torch.Tensor:
+    """The default point table, f64 [n_points, 3], formed in numpy fp64 on the host: for k = 0 .. P - 1
+        z = 1 - (2 k + 1) / P,   rho = sqrt(1 - z z),   phi = k * pi * (3 - sqrt(5))
+        U[k] = (rho cos(phi), rho sin(phi), z)
+    — equal steps in z (equal areas) and the golden angle between neighbours."""
+    import numpy as np
+    n_points = integer(n_points, "Spheres: n_points", 1, ops.SA_MAX_POINTS, exact=True)
+    k = np.arange(n_points, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / float(n_points)
+    rho = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return torch.from_numpy(np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1))
+
+
+class Spheres:
+    """The spheres a surface is taken of: `R` f64 [N], the EXPANDED radii r_i + probe; `points` f64 [P, 3], the sphere table;
+    `reach` = 2 * max(R), a Python float (what a periodic box is checked against); `radii` and `probe` as given.  Built and
+    validated on the host; `.to(device)` uploads once per device and hands the same object back after that.
+
+    `radii`: a number (with `n_atoms`), a sequence or a CPU tensor of N van der Waals radii, each finite and > 0.  `probe`:
+    finite and >= 0 (1.4 A: water).  `points`: any table f64 [P, 3] (P in 1 .. 1,024), by default `golden_spiral(n_points)`."""
+
+    def __init__(self, radii, probe: float = 1.4, n_points: int = 96, points=None, n_atoms: Optional[int] = None):
+        try:
+            probe = float(probe)
+        except (TypeError, ValueError):
+            raise MdnoError(f"Spheres: probe = {probe!r}: expected a number") from None
+        if not (math.isfinite(probe) and probe >= 0.0):
+            raise MdnoError(f"Spheres: probe = {probe}: expected a finite number >= 0")
+        try:      # (Python numbers straight to f64)
+            r = radii.detach().cpu().to(torch.float64) if torch.is_tensor(radii) else torch.as_tensor(radii, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise MdnoError("Spheres: radii is not a number or an array of numbers") from None
+        if r.dim() == 0:
+            if n_atoms is None:
+                raise MdnoError("Spheres: one radius for every atom needs n_atoms")
+            r = r.expand(integer(n_atoms, "Spheres: n_atoms", 0, exact=True))
+        elif r.dim() != 1 or (n_atoms is not None and r.numel() != n_atoms):
+            raise MdnoError(f"Spheres: radii has shape {tuple(r.shape)}, expected [N]" + ("" if n_atoms is None else f" with N = {n_atoms}"))
+        r = r.contiguous().clone()
+        if r.numel() and not (bool(torch.isfinite(r).all()) and bool((r > 0).all())):
+            raise MdnoError("Spheres: every radius must be finite and > 0")
+        if points is None:
+            table = golden_spiral(n_points)
+        else:
+            try:
+                table = points.detach().cpu().to(torch.float64) if torch.is_tensor(points) else torch.as_tensor(points, dtype=torch.float64)
+            except (TypeError, ValueError, RuntimeError):
+                raise MdnoError("Spheres: points is not an array of numbers") from None
+            if table.dim() != 2 or table.shape[1] != 3 or not 1 <= table.shape[0] <= ops.SA_MAX_POINTS:
+                raise MdnoError(f"Spheres: points has shape {tuple(table.shape)}, expected [P, 3] with P in 1 .. {ops.SA_MAX_POINTS}")
+            if not bool(torch.isfinite(table).all()):
+                raise MdnoError("Spheres: points must be finite")
+            table = table.contiguous().clone()
+        self.radii, self.probe = r, probe
+        self.R = r + probe                       # fp64, one add per atom: the R of the rule
+        self.points = table
+        self.reach = 2.0 * float(self.R.max()) if r.numel() else 0.0
+        if r.numel() and not math.isfinite(self.reach):
+            raise MdnoError("Spheres: radius + probe overflows")
+        self._on = {}
+
+    @property
+    def n_atoms(self) -> int:
+        return int(self.R.shape[0])
+
+    @property
+    def n_points(self) -> int:
+        return int(self.points.shape[0])
+
+    def to(self, device) -> "Spheres":
+        device = torch.device(device)
+        if device == self.R.device:
+            return self
+        if device not in self._on:
+            s = object.__new__(Spheres)
+            s.radii, s.probe, s.reach = self.radii, self.probe, self.reach
+            s.R, s.points = self.R.to(device), self.points.to(device)
+            s._on = self._on
+            self._on[device] = s
+        return self._on[device]
+
+    def check_frames(self, n_atoms: int) -> None:
+        if n_atoms != self.n_atoms:
+            raise MdnoError(f"the spheres were built for frames of {self.n_atoms} atoms, these have {n_atoms}")
+
+
+@dataclass
+class SurfaceArea:
+    """Exposed-point counts of a run (ops.exposed_points): `counts` i32 [S, M, N] (or the frames' leading shape + [N]), -1 for
+    an atom with a non-finite coordinate; `R` f64 [N], the expanded radii, on the device of the counts; `n_points` = P.  The
+    area of a sphere's exposed part is 4 pi R_i^2 * count / P.  Every method is a few torch operations in fp64 on the device
+    of `counts` and reads nothing back."""
+    counts: torch.Tensor
+    R: torch.Tensor
+    n_points: int
+
+    def _fraction(self) -> torch.Tensor:
+        c = self.counts.to(torch.float64)
+        return torch.where(self.counts < 0, torch.full_like(c, float("nan")), c) / float(self.n_points)
+
+    def per_atom(self) -> torch.Tensor:
+        """4 pi R_i^2 * counts / P: f64 like `counts`; NaN where the count is -1."""
+        return (4.0 * math.pi) * (self.R * self.R) * self._fraction()
+
+    def total(self) -> torch.Tensor:
+        """The sum of per_atom() over the atoms: f64 [S, M]; NaN for a frame that holds a -1."""
+        return self.per_atom().sum(-1)
+
+    def per_group(self, index, n_groups: int) -> torch.Tensor:
+        """The sum of per_atom() over the atoms of every group (residue): `index` [N], integers in 0 .. n_groups - 1 ->
+        f64 [..., n_groups]; NaN for a group that holds a -1."""
+        n_groups = integer(n_groups, "per_group: n_groups", 0, None)
+        idx = (index.detach() if torch.is_tensor(index) else torch.as_tensor(index)).reshape(-1).cpu()
+        if idx.numel() != self.counts.shape[-1] or idx.dtype.is_floating_point or idx.dtype == torch.bool or \
+                (idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < n_groups)):
+            raise MdnoError(f"per_group: index must hold {self.counts.shape[-1]} integers in 0 .. {n_groups - 1}")
+        a = self.per_atom()
+        out = torch.zeros(a.shape[:-1] + (n_groups,), dtype=torch.float64, device=a.device)
+        return out.index_add_(-1, idx.to(torch.int64).to(a.device), a)
+
+    def burial(self) -> torch.Tensor:
+        """1 - counts / P: f64 like `counts`, the covered share of every sphere; NaN where the count is -1."""
+        return 1.0 - self._fraction()
+
+    def mean(self) -> torch.Tensor:
+        """per_atom() averaged over the steps (the first axis): f64 [M, N]; NaN without steps."""
+        a = self.per_atom()
+        return _ratio(a.sum(0), torch.full((), a.shape[0], dtype=torch.float64, device=a.device))
+
+    def mean_burial(self) -> torch.Tensor:
+        """burial() averaged over the steps: f64 [M, N]."""
+        b = self.burial()
+        return _ratio(b.sum(0), torch.full((), b.shape[0], dtype=torch.float64, device=b.device))
+
+    def difference(self, other: "SurfaceArea") -> torch.Tensor:
+        """The RMS over the atoms of mean_burial() - other.mean_burial(): f64 [M] — 0 = every atom as buried, on average, as
+        in the other run.  `other` may hold one member (the truth), which is broadcast against this one's M."""
+        if not isinstance(other, SurfaceArea):
+            raise MdnoError(f"difference: other is a {type(other).__name__}")
+        a, b = self.mean_burial(), other.mean_burial()
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or (a.shape[0] != b.shape[0] and 1 not in (a.shape[0], b.shape[0])):
+            raise MdnoError(f"difference: mean burials of shape {tuple(a.shape)} and {tuple(b.shape)}, expected [M, N] each")
+        d = a - b
+        return torch.sqrt(_ratio((d * d).sum(1), torch.full((), d.shape[1], dtype=torch.float64, device=d.device)))
+
+    def cpu(self) -> "SurfaceArea":
+        return SurfaceArea(self.counts.cpu(), self.R.cpu(), self.n_points)
+
+    @staticmethod
+    def cat(parts: Sequence["SurfaceArea"]) -> "SurfaceArea":
+        """Counts of disjoint member ranges of the same steps and spheres, members in order."""
+        return SurfaceArea(torch.cat([q.counts for q in parts], -2), parts[0].R, parts[0].n_points)
+
+
+def surface_area(frames: torch.Tensor, spheres: Spheres, box=None, form: str = "auto") -> SurfaceArea:
+    """frames f32 [S, M, N, 3] (or any [..., N, 3], device) and `Spheres` -> `SurfaceArea`: the Shrake-Rupley count of every
+    atom of every frame (include/mdno_surface.h has the rule).  `box` = (Lx, Ly, Lz), 0 for an open axis: neighbours by the
+    minimum image; every periodic axis must be >= 2 * spheres.reach.  Asynchronous on the current stream, nothing is read
+    back; CPU tensors and bad arguments raise `MdnoError` before any device work."""
+    if not torch.is_tensor(frames) or frames.dim() < 2 or frames.shape[-1] != 3:
+        raise MdnoError("surface_area: frames must be [..., N, 3]")
+    if not isinstance(spheres, Spheres):
+        raise MdnoError(f"surface_area: spheres is a {type(spheres).__name__}")
+    spheres.check_frames(int(frames.shape[-2]))
+    if spheres.n_atoms == 0:            # (no sphere, no reach to check a box against: nothing to launch)
+        ops.check_box(box, 0.0)
+        ops.form_code(form, ops.FORECAST_FORMS)
+        on_device(frames, "frames")
+        return SurfaceArea(torch.zeros(tuple(frames.shape[:-1]), dtype=torch.int32, device=frames.device),
+                           spheres.to(frames.device).R, spheres.n_points)
+    ops.check_surface_args(spheres.reach, box, form)
+    on_device(frames, "frames")
+    sp = spheres.to(frames.device)
+    return SurfaceArea(ops.exposed_points(frames, sp.R, sp.points, box, sp.reach, form), sp.R, sp.n_points)
 
 
 def gather_scores(local_score: ForecastScore, total_members: int, group=None) -> ForecastScore:

@@ -2236,3 +2236,47 @@ def contact_correlation(bits: torch.Tensor, S: int, lags):
                                          ptr(origins) if work else None, ptr(both) if work else None, stream_ptr(dev)),
           "mdnocm_contact_correlation")
     return origins, both
+
+
+# ------------------------------------------------------------------------------------------------
+# Solvent-accessible surface (include/mdno_surface.h, csrc/surface.hip)
+SA_MAX_POINTS = _lib.SURFACE_MAX_POINTS         # MDNOSA_MAX_POINTS
+SA_STAGED_ATOMS = _lib.SURFACE_STAGED_ATOMS     # MDNOSA_STAGED_ATOMS: the largest N of the staged form
+SA_TILE = _lib.SURFACE_TILE                     # MDNOSA_TILE
+SA_CHUNK = _lib.SURFACE_CHUNK                   # MDNOSA_CHUNK
+
+
+def check_surface_args(reach, box=None, form: str = "auto"):
+    """(reach as float, box as check_box returns it, the form's code) or MdnoError: reach finite and > 0, every periodic axis
+    of the box >= 2 * reach, form one of FORECAST_FORMS (include/mdno_surface.h).  Host only."""
+    reach = real(reach, "exposed_points: reach")
+    return reach, check_box(box, reach), form_code(form, FORECAST_FORMS)
+
+
+def exposed_points(frames: torch.Tensor, R: torch.Tensor, points: torch.Tensor, box=None, reach=None, form: str = "auto") -> torch.Tensor:
+    """frames f32 [..., N, 3], R f64 [N] (the EXPANDED radii r_i + probe) and points f64 [P, 3] (the sphere table, P in
+    1 .. 1,024) on the same device -> i32 [..., N]: per atom the points of R_i * points that no neighbour's sphere covers, -1
+    for an atom with a non-finite coordinate (include/mdno_surface.h has the rule; mdnosa_exposed_points).  `box` =
+    (Lx, Ly, Lz), 0 for an open axis: differences by the minimum image, every periodic axis >= 2 * reach.  `reach` is
+    2 * max(R); `forecast.Spheres` carries it on the host, and only where it is left None is it read back from R (the one
+    synchronisation this call can make).  Otherwise asynchronous on the current stream, nothing is read back.  `form`:
+    "auto" (the frame staged in LDS up to 2,048 atoms, 256-atom tiles above), "lds" or "tiled" to force one (the same
+    counts)."""
+    frames, lead, F, N = _flat_frames(frames)
+    check_dims("exposed_points: frames", frames.shape, (F, N))
+    dev = frames.device
+    R = operand(R, "R", torch.float64, (N,), dev)
+    points = operand(points, "points", torch.float64, (None, 3), dev)
+    P = integer(points.shape[0], "exposed_points: the number of points", 1, SA_MAX_POINTS)
+    if reach is None:
+        reach = 2.0 * float(R.max()) if N else 1.0
+    reach, box, code = check_surface_args(reach, box, form)
+    lib = _lib.load()
+    counts = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+    nbytes = lib.mdnosa_workspace_bytes(F, N, P, code)
+    ws = _ws(nbytes, dev) if nbytes else None
+    work = F * N > 0
+    check(lib.mdnosa_exposed_points(ptr(frames) if work else None, F, N, ptr(R) if work else None, ptr(points), P,
+                                    box_arg(box) if box else None, reach, ptr(counts) if work else None, code, ptr(ws), nbytes,
+                                    stream_ptr(dev)), "mdnosa_exposed_points")
+    return counts

@@ -212,6 +212,15 @@ class _ProducedFrames:
         return self._per_member(lambda x: forecast.contact_series(x, contact_pairs, box=self.box),
                                 forecast.ContactSeries.cat, first_step, steps)
 
+    def surface_area(self, spheres, first_step: int = 0, steps: Optional[int] = None):
+        """Per member: `forecast.surface_area` (the Shrake-Rupley count of exposed sphere points of every atom of every
+        frame) in the engine's own box -> `forecast.SurfaceArea`, counts i32 [steps, M, N]."""
+        if not isinstance(spheres, forecast.Spheres):
+            raise MdnoError(f"surface_area: spheres is a {type(spheres).__name__}")
+        ops.check_box(self.box, spheres.reach)
+        return self._per_member(lambda x: forecast.surface_area(x, spheres, box=self.box), forecast.SurfaceArea.cat,
+                                first_step, steps)
+
     def covariance(self, reference: torch.Tensor, mean: Optional[torch.Tensor] = None, lag: int = 0, first_step: int = 0,
                    steps: Optional[int] = None):
         """Pooled: `forecast.covariance` over the 3 N coordinates after the superposition onto reference f32 [N, 3] ->

@@ -41,12 +41,15 @@ are not native, the mean Q over the run beside the truth's own, and the contact 
 rigid motions on the start windows (training.equivariance_error): K seeded motions (a uniform rotation about every member's
 centroid, plus `--equivariance-translate A`), the mean and the largest per-member RMS of |f(g x) - g f(x)| in Angstrom and the
 same relative to the size of the step |f(x) - x_last| (INTEGRATION.md "Training on rigid motions / how equivariant is the
-model?" reads them).
+model?" reads them).  With `--sasa [RADIUS PROBE N_POINTS]` also the solvent-accessible surface of the run
+(forecast.surface_area: Shrake-Rupley counts, one RADIUS for every atom, default 1.9 1.4 96): per member the mean and the
+standard deviation over the steps of the total area beside the truth's, and the RMS over the atoms of the difference between
+its per-atom mean burial and the truth's (INTEGRATION.md "Does the run keep its core buried?" reads them).
 
     python scripts/score_rollout.py [--members 64] [--atoms 504] [--steps 1000] [--window 10] [--reps 5] [--rdf 8.0 200]
                                     [--msd 4.0 64] [--ensemble] [--noise-sigma 0.05] [--coverage 2.0]
                                     [--pca 10] [--tica 10] [--msm 100 10] [--internal 3 4] [--constrain 0.1] [--contacts 3]
-                                    [--equivariance 8]
+                                    [--equivariance 8] [--sasa 1.9 1.4 96]
 """
 import argparse
 import json
@@ -109,7 +112,13 @@ def main() -> None:
                          "motions (and over the members) of the RMS of |f(g x) - g f(x)|, absolute and relative to the step")
     ap.add_argument("--equivariance-translate", type=float, default=0.0, metavar="A",
                     help="with --equivariance: also translate by up to A Angstrom per axis")
+    ap.add_argument("--sasa", nargs="*", metavar="RADIUS PROBE N_POINTS", default=None,
+                    help="also the solvent-accessible surface area of the run (Shrake-Rupley, one RADIUS for every atom; default "
+                         "1.9 1.4 96): per member the mean and standard deviation of the total area beside the truth's, and the "
+                         "per-atom RMS of its mean burial against the truth's")
     a = ap.parse_args()
+    if a.sasa is not None and len(a.sasa) not in (0, 3):
+        ap.error("--sasa takes no values or RADIUS PROBE N_POINTS")
     if a.equivariance is not None and (a.equivariance < 1 or not a.equivariance_translate >= 0.0):
         ap.error("--equivariance takes K >= 1 (and --equivariance-translate A >= 0)")
     if a.contacts is not None and a.contacts < 0:
@@ -237,6 +246,18 @@ def main() -> None:
                      "q_mean": finite(q_run.fraction().mean(0).cpu()), "q_mean_truth": finite(q_truth.fraction().mean(0).cpu())[0],
                      "contact_survival_lags": some, "contact_survival_mean": finite(s_run.nanmean(0).cpu()),
                      "contact_survival_truth": finite(s_truth[0].cpu())})
+
+    if a.sasa is not None and S > 0:
+        from molecular_dynamics_neural_operator_amd import forecast as fs
+        radius, probe, n_points = (float(a.sasa[0]), float(a.sasa[1]), int(a.sasa[2])) if a.sasa else (1.9, 1.4, 96)
+        spheres = fs.Spheres(radius, probe=probe, n_points=n_points, n_atoms=N)
+        run, tru = eng.surface_area(spheres), fs.surface_area(truth[:, None], spheres, box=eng.box)
+        total, total_truth = run.total(), tru.total()                                # f64 [S, M], [S, 1]
+        dist.update({"sasa_radius_probe_points": [radius, probe, n_points],
+                     "sasa_total_mean": finite(total.mean(0).cpu()), "sasa_total_std": finite(total.std(0, unbiased=False).cpu()),
+                     "sasa_total_mean_truth": finite(total_truth.mean(0).cpu())[0],
+                     "sasa_total_std_truth": finite(total_truth.std(0, unbiased=False).cpu())[0],
+                     "sasa_burial_rms_difference": finite(run.difference(tru).cpu())})
 
     if a.equivariance is not None:
         from molecular_dynamics_neural_operator_amd import ops
